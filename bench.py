@@ -15,12 +15,17 @@ so the N-shard run of a job scans the very reads of its 1-GPU run.
                     --batches batches over 2 slots (H2D of batch i+1 overlaps the scan of batch i): configs[3]'s
                     "async batch pipeline"; reports the H2D rate per rank and in total
 
-The default run also carries, measured OUTSIDE the timed region and compactly (the driver's record keeps ~6 kB):
+A plain run sets up, warms up, times the K steps and prints the headline line (its roofline from the timed
+steps' HIP events and the committed profile), nothing else.  With --full the line also carries, measured
+OUTSIDE the timed region and compactly (the driver's record keeps ~6 kB):
   at every N   legs      `pipe` (se, pipeline), `mix` (mixed, resident), `mixpipe` (mixed, pipeline): aggregates
                          over the ranks, each leg between barriers, max-over-ranks time
   at N = 1     roofline.peak_measured, cpu_baseline, variants (tools/variants.py names the shapes), e2e (this
                CLI against the compiled reference CLI: 10 M pairs compared byte for byte, 50 M pairs = 100 M reads
                = configs[3] with the reference extrapolated per read), e2e_mixed (configs[4] through both CLIs)
+
+--dump-outputs DIR writes, after the timed steps, the cuts of the last timed step (see dump_outputs) as .npy files;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Launch: `python bench.py` (N=1) or
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -214,6 +219,9 @@ class ResidentSE:
         bases_kept = int((self.out[:, 1] - self.out[:, 0]).clamp_(min=0).sum().item())
         return [kept, self.n - kept, bases_kept, self.n]
 
+    def host_cuts(self):
+        return self.out.cpu().numpy()
+
 
 class ResidentMixed:
     """This rank's mixed-length reads (configs[4]) resident in HBM in the segmented layout, scanned with -n."""
@@ -255,6 +263,9 @@ class ResidentMixed:
         kept = int((self.out[:, 1] >= 0).sum().item())
         bases_kept = int((self.out[:, 1] - self.out[:, 0]).clamp_(min=0).sum().item())
         return [kept, self.n - kept, bases_kept, self.n]
+
+    def host_cuts(self):
+        return self.out.cpu().numpy()
 
 
 class Pipeline:
@@ -337,6 +348,9 @@ class Pipeline:
                 kept += int((out[:, 1] >= 0).sum())
                 bases_kept += int(self.np.clip(out[:, 1] - out[:, 0], 0, None).sum())
         return [kept, self.n - kept, bases_kept, self.n]
+
+    def host_cuts(self):
+        return self.np.concatenate([out for _, _, out, _ in self.items]) if self.items else self.np.zeros((0, 2), self.np.int32)
 
     def close(self):
         for p in self.raw:
@@ -448,14 +462,18 @@ def parse_args(argv=None):
                     help="strong scaling: this many reads in all, split into contiguous shards over the ranks (100000000 = BASELINE configs[3])")
     ap.add_argument("--mixed-reads", type=int, default=8_000_000, help="reads of the mixed job (always strong scaling)")
     ap.add_argument("--len", type=int, default=150)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline (+ cpu_baseline) only: no legs, variants, e2e")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: peak_measured, cpu_baseline (+ parity), legs, variants, e2e")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline (+ peak_measured, cpu_baseline) only: no legs, variants, e2e")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: no e2e")
     ap.add_argument("--e2e-pairs", type=int, default=10_000_000, help="pairs both CLIs run, outputs compared")
     ap.add_argument("--e2e-big-pairs", type=int, default=50_000_000, help="pairs this CLI alone runs on (configs[3] size); 0 = skip")
     ap.add_argument("--e2e-mixed-pairs", type=int, default=4_000_000, help="pairs of the configs[4] run; 0 = skip")
-    ap.add_argument("--full", action="store_true", help="long form of the variants (workload text, min/max): for profiles/, not for the driver")
+    ap.add_argument("--long-variants", action="store_true", help="with --full: long form of the variants (workload text, min/max): for profiles/, not for the driver")
     ap.add_argument("--variant", default="", help="time ONE kernel variant (tools/variants.py) instead of the headline: for rocprofv3 runs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the cuts of the last timed step to DIR/*.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args(argv)
     if args.settle < 0:
         args.settle = 150 if args.mode == "resident" else 1
@@ -496,6 +514,26 @@ def run_leg(torch, capi, ctx, device, stream, args, rank, world, dist, reduce_de
     if device.type == "cuda":
         torch.cuda.empty_cache()
     return res
+
+
+DUMP_ROWS = 1 << 21  # rows of cuts dumped in all: 2 M x (8 B of cuts + 8 B of index) = 32 MB
+
+
+def dump_outputs(path, cuts, counts, lo, rank, world):
+    """What a caller of the timed path receives, from its last step: the (n, 2) int32 cut pairs of this rank's reads.
+    cuts.npy (float32, exact for any cut) holds every row, or beyond DUMP_ROWS / world rows a fixed sample of rows
+    drawn with SEED; cuts_index.npy (float64) the job-wide read number of each row.  counts.npy (float64, rank 0)
+    is the job-wide [kept, discarded, bases kept, reads] over every row.  With N ranks the cut files end in .rank<r>."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(cuts)
+    m = max(1, DUMP_ROWS // world)
+    idx = np.arange(n) if n <= m else np.sort(np.random.default_rng(SEED).choice(n, m, replace=False))
+    suffix = "" if world == 1 else ".rank%d" % rank
+    np.save(os.path.join(path, "cuts%s.npy" % suffix), cuts[idx].astype(np.float32))
+    np.save(os.path.join(path, "cuts_index%s.npy" % suffix), (idx + lo).astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "counts.npy"), np.asarray(counts, dtype=np.float64))
 
 
 def gather_floats(torch, dist, x, device):
@@ -570,8 +608,11 @@ def main():
     res = None
     if rank == 0:
         res = headline(args, plan, world, counts, tmax, kern_ms, work.kernel, work.algo_bytes, counts[4], h2d)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, work.host_cuts(), counts[:4], plan["lo"], rank, world)
+    # everything below the headline (other measurements, checks, legs, variants, e2e) only with --full
     default_run = args.mode == "resident" and args.workload == "se"
-    if rank == 0 and world == 1 and default_run:
+    if args.full and rank == 0 and world == 1 and default_run:
         achieved = res["roofline"]["achieved"]
         # the second denominator: what a read-only stream of this very buffer gets on this device
         try:
@@ -597,7 +638,7 @@ def main():
     del work
     torch.cuda.empty_cache()
 
-    if default_run and not args.no_extras:
+    if args.full and default_run and not args.no_extras:
         # the legs every rank takes part in: configs[3]'s async batch pipeline and configs[4]'s mixed batch
         legs = {}
         for key, wk, md, st in (("pipe", "se", "pipeline", 3), ("mix", "mixed", "resident", 30), ("mixpipe", "mixed", "pipeline", 3)):
@@ -610,9 +651,9 @@ def main():
         if rank == 0:
             res["legs"] = legs
             res["legs_are"] = "pipe: se via sk_submit/sk_wait (host buffers); mix: configs[4] batch resident, -n; mixpipe: the same via sk_submit/sk_wait"
-    if rank == 0 and world == 1 and default_run and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and default_run and not args.no_extras:
         import variants
-        res["variants"] = run_variants(torch, capi, ctx, device, stream, variants.NAMES, 30, full=args.full)
+        res["variants"] = run_variants(torch, capi, ctx, device, stream, variants.NAMES, 30, full=args.long_variants)
         res["variants_are"] = "tools/variants.py; k kernel, ms per scan, GBps algorithmic, frac of 8 TB/s"
         if not args.no_e2e:
             import e2e_bench

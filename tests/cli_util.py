@@ -25,6 +25,12 @@ def build_hostcheck():
     return HOSTCHECK_BIN
 
 
+def ref_soak_record(seed):
+    """The compiled reference's side of tests/soak_cli.py's run with `seed`, as make_golden.py --only-ref-fuzz
+    recorded it (tests/golden/ref_soak_cli.json)."""
+    return json.load(open(os.path.join(GOLD, "ref_soak_cli.json")))[str(seed)]
+
+
 def md5_file(path):
     h = hashlib.md5()
     with open(path, "rb") as f:

@@ -13,6 +13,9 @@ Outputs (all data, no reference source):
     cuts_edge.npz       their cuts over a flag grid
     errors.json         range-error cases: exit status + the reference's stderr text
     e2e.json            `sickle pe -a 1` runs: argv, exit status, md5/size of each output, stdout
+    ref_fuzz.npz, ref_error_fuzz.json, ref_soak_cli.json (--only-ref-fuzz)
+                        the reference's side of the seeded fuzz tests (tests/test_oracle_golden.py) and of the CLI
+                        soaks of tests/test_cli_host.py / test_cli_gpu.py (tests/soak_cli.py), for runs without it
 """
 import gzip
 import hashlib
@@ -283,7 +286,36 @@ def thread_order_goldens(tmp):
     return out
 
 
+def ref_fuzz_goldens():
+    """ref_fuzz.npz, ref_error_fuzz.json, ref_soak_cli.json: what the reference does on the seeded inputs of the
+    tests that compare with it, so that they run where oracle/_ref is absent."""
+    import cli_util as cu
+    import soak_cli
+    from test_oracle_golden import error_fuzz_reads, fuzz_batches
+    cuts = {}
+    for trial, p, qual, seq, offs in fuzz_batches():
+        c = ob.ref_trim_batch(p, qual, seq, offsets=offs, threads=2)
+        assert np.abs(c).max() < 2 ** 15
+        cuts["t%d" % trial] = c.astype(np.int16)
+    np.savez_compressed(os.path.join(HERE, "ref_fuzz.npz"), **cuts)
+    errs = []
+    for trial, p, qual, seq in error_fuzz_reads():
+        rc, cut, text = ob.ref_sliding_window_forked(p, b"@fz", seq.tobytes(), qual.tobytes())
+        errs.append({"rc": rc, "cut": list(cut), "stderr": text.decode("latin-1")})
+    json.dump(errs, open(os.path.join(HERE, "ref_error_fuzz.json"), "w"), indent=1)
+    soak_cli.NEW = cu.build_hostcheck()
+    soak = {}
+    for iters, seed in ((80, 404), (40, 505)):  # test_cli_host.py, test_cli_gpu.py
+        soak[str(seed)] = []
+        soak_cli.run(iters, seed, verbose=False, record=soak[str(seed)])
+    json.dump(soak, open(os.path.join(HERE, "ref_soak_cli.json"), "w"), indent=1)
+
+
 def main():
+    if "--only-ref-fuzz" in sys.argv:  # (re)writes ref_fuzz.npz, ref_error_fuzz.json, ref_soak_cli.json only
+        assert ob.have_ref()
+        ref_fuzz_goldens()
+        return
     if "--only-thread-order" in sys.argv:  # adds / refreshes e2e.json["thread_order"], leaves the rest alone
         assert ob.have_ref()
         e2e = json.load(open(os.path.join(HERE, "e2e.json")))

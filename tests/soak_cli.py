@@ -5,9 +5,12 @@ behind the CLI); every encoding; -q, -l, -x, -n.  The expectation is DERIVED (te
 batch-cut rule + the oracle's cuts -> the output chunk of every ingest batch): this CLI must write the chunks in
 batch order, byte for byte; the reference -- whose per-batch output threads race each other for the files, and
 whose main thread does not wait for the last of them -- must write a permutation of exactly those chunks in at
-least one of six runs (which pins the derivation to the reference), and its summary must equal ours.
+least one of six runs (which pins the derivation to the reference), and its summary must equal ours.  Where the
+compiled reference is absent, what it did is taken from a record of these checks (run(..., golden=...): per
+iteration the inputs' md5, every output's chunks as a sorted multiset, the summary), which run(..., record=[])
+writes where it is present (tests/golden/make_golden.py --only-ref-fuzz -> tests/golden/ref_soak_cli.json).
 usage: soak_cli.py [iterations] [seed]"""
-import gzip, os, subprocess, sys, tempfile, time
+import gzip, hashlib, os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -37,7 +40,21 @@ def records(rng, n, lens, lo, hi, mid, tag, mate):
     return out
 
 
-def run(iters=20, seed=1, verbose=True):
+def chunk_multiset(chunks):
+    """md5 of the chunks sorted: the same for every permutation of them."""
+    h = hashlib.md5()
+    for c in sorted(chunks):
+        h.update(b"%d:" % len(c) + c)
+    return h.hexdigest()
+
+
+def run(iters=20, seed=1, verbose=True, golden=None, record=None):
+    """golden: the record of the reference's side for (iters, seed), checked against; without it the compiled
+    reference must be present.  record: a list the reference's side is appended to (needs the reference)."""
+    live = os.path.exists(REF)
+    assert live or golden is not None, "needs the compiled reference (oracle/_ref/sickle) or its record"
+    assert record is None or live
+    assert golden is None or len(golden) == iters
     rng = np.random.default_rng(seed)
     t0 = time.time()
     races = 0
@@ -116,36 +133,47 @@ def run(iters=20, seed=1, verbose=True):
             for o in outs:
                 got = open(os.path.join(d, "new_" + o), "rb").read() if os.path.exists(os.path.join(d, "new_" + o)) else b""
                 assert got == b"".join(c[idx[o]] for c in chunks), (it, o, argv(""), len(got))
-            same = False
-            for attempt in range(6):
-                for o in outs:
-                    if os.path.exists(os.path.join(d, "ref_" + o)):
-                        os.remove(os.path.join(d, "ref_" + o))
-                pr = subprocess.run([REF] + argv("ref_"), capture_output=True, timeout=120)
-                assert pr.returncode == 0, (it, argv(""), pr.returncode, pr.stderr[-300:])
-                same = True
-                for o in outs:
-                    b = open(os.path.join(d, "ref_" + o), "rb").read() if os.path.exists(os.path.join(d, "ref_" + o)) else b""
-                    same = same and is_permutation_of_chunks(b, [c[idx[o]] for c in chunks])
-                if same:
-                    break
-                races += 1
-            assert same, (it, argv(""), "six reference runs, none a permutation of the derived chunks")
-            # The summaries: equal line by line, except "Total input FastQ records", which in the reference is the size
-            # of whichever batch its racing output threads finished LAST (src/trim_paired.cpp:593) -- here the last
-            # batch in order.  Both must name the size of one of the batches.
+            # what the reference must have written: every output a permutation of exactly these chunks
+            side = {"inputs_md5": hashlib.md5(b"".join(datas)).hexdigest(),
+                    "chunks": {o: chunk_multiset([c[idx[o]] for c in chunks]) for o in outs}}
             sn = cu.summary_block(pn.stdout.decode("latin-1")).replace("new_", "").split("\n")
-            sr = cu.summary_block(pr.stdout.decode("latin-1")).replace("ref_", "").split("\n")
-            # (chatter of the racing output threads can lose its [DEBUGGING] tag to interleaving: the summary starts
-            # at its first own line)
-            first = next((i for i, x in enumerate(sr) if x.startswith(("PE ", "SE ", "Total input"))), 0)
-            sr = sr[first:]
             sizes = [len(b) // 4 * (1 if inter else 2) for b in b1] or [0]
             tn = [x for x in sn if x.startswith("Total input")]
-            tr = [x for x in sr if x.startswith("Total input")]
-            assert [x for x in sn if x not in tn] == [x for x in sr if x not in tr], (it, argv(""), sn, sr)
             assert tn == ["Total input FastQ records: %d (%d pairs)" % (sizes[-1], sizes[-1] // 2)], (it, tn, sizes)
-            assert len(tr) == 1 and any(tr[0] == "Total input FastQ records: %d (%d pairs)" % (z, z // 2) for z in sizes), (it, tr, sizes)
+            if golden is not None:
+                g = golden[it]
+                assert side == {"inputs_md5": g["inputs_md5"], "chunks": g["chunks"]}, (it, argv(""), side, g)
+                assert [x.replace(d, "{d}") for x in sn if x not in tn] == g["summary"], (it, argv(""), sn, g["summary"])
+                assert any(g["total"] == "Total input FastQ records: %d (%d pairs)" % (z, z // 2) for z in sizes), (it, g["total"], sizes)
+            if live:
+                same = False
+                for attempt in range(6):
+                    for o in outs:
+                        if os.path.exists(os.path.join(d, "ref_" + o)):
+                            os.remove(os.path.join(d, "ref_" + o))
+                    pr = subprocess.run([REF] + argv("ref_"), capture_output=True, timeout=120)
+                    assert pr.returncode == 0, (it, argv(""), pr.returncode, pr.stderr[-300:])
+                    same = True
+                    for o in outs:
+                        b = open(os.path.join(d, "ref_" + o), "rb").read() if os.path.exists(os.path.join(d, "ref_" + o)) else b""
+                        same = same and is_permutation_of_chunks(b, [c[idx[o]] for c in chunks])
+                    if same:
+                        break
+                    races += 1
+                assert same, (it, argv(""), "six reference runs, none a permutation of the derived chunks")
+                # The summaries: equal line by line, except "Total input FastQ records", which in the reference is the size
+                # of whichever batch its racing output threads finished LAST (src/trim_paired.cpp:593) -- here the last
+                # batch in order.  Both must name the size of one of the batches.
+                sr = cu.summary_block(pr.stdout.decode("latin-1")).replace("ref_", "").split("\n")
+                # (chatter of the racing output threads can lose its [DEBUGGING] tag to interleaving: the summary starts
+                # at its first own line)
+                first = next((i for i, x in enumerate(sr) if x.startswith(("PE ", "SE ", "Total input"))), 0)
+                sr = sr[first:]
+                tr = [x for x in sr if x.startswith("Total input")]
+                assert [x for x in sn if x not in tn] == [x for x in sr if x not in tr], (it, argv(""), sn, sr)
+                assert len(tr) == 1 and any(tr[0] == "Total input FastQ records: %d (%d pairs)" % (z, z // 2) for z in sizes), (it, tr, sizes)
+                if record is not None:
+                    record.append(dict(side, summary=[x.replace(d, "{d}") for x in sr if x not in tr], total=tr[0]))
             if it % 5 == 0:  # -g: the outputs as gzip (BGZF blocks; deflated on the GPU on every other turn), same content
                 env = dict(os.environ, SICKLE_GZ_LEVEL="gpu") if it % 10 == 0 else None
                 pg = subprocess.run([NEW] + argv("gz_") + ["-g"], capture_output=True, timeout=120, env=env)

@@ -54,13 +54,11 @@ def test_reference_runs_in_one_process_on_gpu(workdir, name):
 
 def test_cli_soak_against_reference_on_gpu():
     """tests/soak_cli.py with the product binary: 40 random paired inputs against the chunks derived from the
-    oracle and against the compiled reference (which travels to the box as oracle/_ref)."""
-    import oracle_bind as ob
-    if not ob.have_ref():
-        pytest.skip("needs the compiled reference (oracle/_ref)")
+    oracle and against the compiled reference's side (recorded in tests/golden/ref_soak_cli.json, and run now
+    where oracle/_ref exists)."""
     import soak_cli
     soak_cli.NEW = cu.PRODUCT_BIN
-    assert soak_cli.run(40, 505, verbose=False) == 40
+    assert soak_cli.run(40, 505, verbose=False, golden=cu.ref_soak_record(505)) == 40
 
 
 def test_se_on_gpu_equals_selfpaired_reference(workdir):

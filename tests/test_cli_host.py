@@ -87,14 +87,14 @@ def test_front_process_with_closed_standard_descriptors(hostcheck, workdir):
             assert pr.returncode == 1, (env, redirect, pr.returncode)
 
 
-@pytest.mark.skipif(not ob.have_ref(), reason="needs the compiled reference (oracle/_ref)")
 def test_cli_soak_against_reference(hostcheck):
     """tests/soak_cli.py, 80 random paired inputs (two files / interleaved; equal, mixed, long and tiny reads;
     every encoding; -q -l -x -n): this CLI writes the per-batch chunks derived from the oracle in batch order, the
-    compiled reference a permutation of exactly those chunks, the summaries agree."""
+    compiled reference a permutation of exactly those chunks, the summaries agree (the reference's side as
+    recorded in tests/golden/ref_soak_cli.json, and run now where oracle/_ref exists)."""
     import soak_cli
     soak_cli.NEW = hostcheck
-    assert soak_cli.run(80, 404, verbose=False) == 80
+    assert soak_cli.run(80, 404, verbose=False, golden=cu.ref_soak_record(404)) == 80
 
 
 def se_expected(path, qt, q=20, l=20, no5=False, trunc_n=False, threads=1, batch_lines=None):

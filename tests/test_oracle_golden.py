@@ -1,6 +1,7 @@
 """CPU: the oracle (oracle/sk_oracle.c) against the golden vectors generated from the compiled
-reference (tests/golden/make_golden.py), and -- where oracle/_ref exists -- against the
-reference itself on fresh random inputs.  This is what pins the oracle."""
+reference (tests/golden/make_golden.py): fixed grids, and seeded random inputs whose reference
+results are stored too -- where oracle/_ref exists, also against the reference itself.  This is
+what pins the oracle."""
 import json
 import os
 
@@ -76,8 +77,8 @@ def test_fixed_stride_and_ragged_layouts_agree():
     assert (a == b).all() and (a == c).all()
 
 
-@pytest.mark.skipif(not ob.have_ref(), reason="compiled reference (oracle/_ref) not present")
-def test_fuzz_against_compiled_reference():
+def fuzz_batches():
+    """The fuzz batches, seeded: (trial, params, qual, seq, offsets)."""
     rng = np.random.default_rng(2024)
     for trial in range(40):
         qt = ["sanger", "solexa", "illumina"][trial % 3]
@@ -91,16 +92,11 @@ def test_fuzz_against_compiled_reference():
         qual = np.clip(center + rng.integers(-12, 13, size=tot), lo, hi - 1).astype(np.uint8)
         seq = rng.choice(np.frombuffer(b"ACGTACGTACGTNn", dtype=np.uint8), size=tot)
         p = ob.make_params(qt, int(rng.integers(0, 50)), int(rng.integers(0, 150)), trial % 2, (trial // 2) % 2)
-        a, err = ob.oracle_trim_batch(p, qual, seq, offsets=offs)
-        assert err is None
-        b = ob.ref_trim_batch(p, qual, seq, offsets=offs, threads=2)
-        assert (a == b).all(), trial
+        yield trial, p, qual, seq, offs
 
 
-@pytest.mark.skipif(not ob.have_ref(), reason="compiled reference (oracle/_ref) not present")
-def test_error_fuzz_against_compiled_reference():
-    """Random reads with one illegal char at a random place: the oracle raises exactly when the
-    reference exits, with the same message."""
+def error_fuzz_reads():
+    """The error fuzz reads, seeded: (trial, params, qual, seq), one illegal char each."""
     rng = np.random.default_rng(77)
     for trial in range(60):
         L = int(rng.integers(1, 200))
@@ -111,8 +107,34 @@ def test_error_fuzz_against_compiled_reference():
         qual[int(rng.integers(0, L))] = int(rng.choice([10, 32, 127, 200]))
         seq = np.frombuffer(b"A" * L, dtype=np.uint8)
         p = ob.make_params("sanger", 20, int(rng.choice([0, 20, 60])), trial % 3 == 0, False)
-        rc, cut, text = ob.ref_sliding_window_forked(p, b"@fz", seq.tobytes(), qual.tobytes())
-        got, err = ob.oracle_trim_batch(p, qual, seq, offsets=np.array([0, L], dtype=np.uint64))
+        yield trial, p, qual, seq
+
+
+def test_fuzz_against_compiled_reference():
+    """The oracle on the fuzz batches against the reference's cuts (golden/ref_fuzz.npz) and, where
+    oracle/_ref exists, against the reference run now."""
+    want = np.load(os.path.join(GOLD, "ref_fuzz.npz"))
+    assert len(want.files) == 40
+    for trial, p, qual, seq, offs in fuzz_batches():
+        a, err = ob.oracle_trim_batch(p, qual, seq, offsets=offs)
+        assert err is None
+        assert (a == want["t%d" % trial].astype(np.int32)).all(), trial
+        if ob.have_ref():
+            b = ob.ref_trim_batch(p, qual, seq, offsets=offs, threads=2)
+            assert (a == b).all(), trial
+
+
+def test_error_fuzz_against_compiled_reference():
+    """Random reads with one illegal char at a random place: the oracle raises exactly when the
+    reference exits, with the same message (the reference's outcomes: golden/ref_error_fuzz.json,
+    and where oracle/_ref exists, the reference run now)."""
+    want = json.load(open(os.path.join(GOLD, "ref_error_fuzz.json")))
+    assert len(want) == 60
+    for trial, p, qual, seq in error_fuzz_reads():
+        rc, cut, text = want[trial]["rc"], tuple(want[trial]["cut"]), want[trial]["stderr"].encode("latin-1")
+        if ob.have_ref():
+            assert ob.ref_sliding_window_forked(p, b"@fz", seq.tobytes(), qual.tobytes()) == (rc, cut, text), trial
+        got, err = ob.oracle_trim_batch(p, qual, seq, offsets=np.array([0, len(qual)], dtype=np.uint64))
         if rc == 0:
             assert err is None and tuple(got[0]) == cut, trial
         else:

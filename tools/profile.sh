@@ -7,9 +7,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-# the trace + stats pass runs the SAME command as the plain bench (default steps/warmup, CPU baseline
-# included); the counter passes only need a few launches
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --no-e2e $* > "$OUT/trace_bench.json" 2> "$OUT/trace.err" || { tail -5 "$OUT/trace.err"; exit 1; }
+# the trace + stats pass runs the SAME command as the full bench without e2e (default steps/warmup, CPU
+# baseline included); the counter passes only need a few launches
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --full --no-e2e $* > "$OUT/trace_bench.json" 2> "$OUT/trace.err" || { tail -5 "$OUT/trace.err"; exit 1; }
 BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-extras --steps 10 --warmup 2 --settle 20 $*"
 echo "trace done"
 i=0
