@@ -76,7 +76,8 @@ enum {
     SK_EINVAL = -1,
     SK_ENODEV = -2, /* no usable gfx950 device */
     SK_EHIP = -3,   /* a HIP runtime call failed: see sk_last_error() */
-    SK_EBUSY = -4   /* slot still in flight */
+    SK_EBUSY = -4,  /* slot still in flight */
+    SK_ESPACE = -5  /* sk_trim_device_finish: an output's buffers are too small (counts say what it needs) */
 };
 
 #define SK_TILE_MAX_STRIDE 512u /* two LDS buffers of 64 reads per wave must fit the 160 KiB of a CU */
@@ -185,7 +186,8 @@ void sk_host_free(sk_ctx *ctx, void *p);
 int sk_scan_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch,
                          sk_cut *out, void *hip_stream);
 /* Waits for the stream and reports (and clears) the range error of the scans enqueued on it
- * since the previous finish: SK_OK, or SK_ERANGE with *err filled. */
+ * since the previous finish: SK_OK, or SK_ERANGE with *err filled.  After SK_ERANGE the cuts of the scan are
+ * undefined, and so is what sk_trim_device_async made of them. */
 int sk_scan_device_finish(sk_ctx *ctx, void *hip_stream, sk_err *err);
 
 /*
@@ -243,6 +245,62 @@ typedef struct {
 int sk_count_pairs_device_async(sk_ctx *ctx, const sk_cut *cuts, uint64_t n_pairs, uint8_t *classes, void *hip_stream);
 /* Waits for the stream, returns and clears the counts accumulated on it since the last finish. */
 int sk_count_pairs_device_finish(sk_ctx *ctx, void *hip_stream, sk_pair_counts *counts);
+
+/*
+ * Trimming on the device: the cuts of a scan applied to a device-resident batch, the kept records packed back to back.
+ * Reference src/trim_single.cpp:374-428 (output_single: substr + filter) and src/trim_paired.cpp:506-567 (output_paired:
+ * the pair routing), without the FASTQ text: for reads that go on to more GPU work.  Every pointer is a DEVICE pointer.
+ *
+ * A read is kept iff its three >= 0 (src/trim_single.cpp:368, src/trim_paired.cpp:500,502); its record is bytes
+ * [five, three) of its qual (and seq).  Records stay in read order.  In the PE modes the mates of pair k are reads 2k and
+ * 2k+1 (n_reads must be even) and the pair rule of sk_count_pairs_device_async routes them: both kept -> the paired
+ * output(s), one kept -> out[2] (singles), none -> dropped.
+ *   SK_TRIM_SE              out[0]: every kept read                                       (out[1], out[2] unused)
+ *   SK_TRIM_PE_SPLIT        out[0]: mate 1 of the pairs with both kept, out[1]: their mate 2, out[2]: singles
+ *   SK_TRIM_PE_INTERLEAVED  out[0]: both mates of such pairs (2k, then 2k+1), out[2]: singles   (out[1] unused)
+ * An output is produced iff its `offsets` is not NULL; then offsets[0..records] are its record boundaries (offsets[0] = 0,
+ * offsets[records] = bytes), so (qual, seq, offsets) is an `offsets` sk_batch of `records` reads as it stands, and
+ * read_index[j] (if not NULL) is the input read of record j.  qual / seq may each be NULL (no bytes written); seq must be
+ * NULL when batch->seq is.
+ * Capacity: an output whose records exceed record_capacity, or (with qual or seq given) whose bytes exceed
+ * byte_capacity, gets NOTHING written, not even offsets; sk_trim_device_finish then returns SK_ESPACE with the counts,
+ * so the caller can size its buffers and call again.  With every offsets NULL the call only counts.
+ * Batches: `offsets` and fixed-stride layouts (read_len or lengths), reads up to SK_MAX_READ_LEN, input pointers of any
+ * alignment.  Segmented batches (tiles != NULL) are SK_EINVAL.  out[].qual / seq must be 16-byte aligned, offsets /
+ * read_index 8-byte aligned, cuts 8-byte aligned.
+ * Invalid kept cuts (five < 0, five > three or three > the read's length; a scan never writes one, hand-made cuts can
+ * hold them) make finish return SK_EINVAL with bad_read = the lowest such read, and nothing is written to any output.
+ *
+ * sk_trim_device_async only enqueues four kernels on hip_stream (no allocation, no copy, no synchronisation: it may be
+ * captured into a graph); every bit of scratch and the counts live in `workspace` (device, 16-byte aligned, at least
+ * sk_trim_workspace_bytes(n_reads) bytes: 128 + 64 * ceil(n_reads / 2048) + 8 * n_reads, i.e. below
+ * 8.04 bytes per read + 192 bytes).  sk_trim_device_finish is the only call that waits: it reads the counts out of the
+ * workspace after the stream's work.  Two trims in flight at once need two workspaces.
+ */
+typedef struct {
+    uint8_t *qual;            /* device, 16-byte aligned, or NULL (then no bytes are written) */
+    uint8_t *seq;             /* device, 16-byte aligned, or NULL; must be NULL if batch->seq is NULL */
+    uint64_t *offsets;        /* device, record_capacity + 1 entries (offsets[0] = 0), or NULL = output not produced */
+    uint64_t *read_index;     /* device, record_capacity entries: the input read number of each record, or NULL */
+    uint64_t byte_capacity;   /* bytes available in qual (and in seq) */
+    uint64_t record_capacity; /* entries available in read_index; offsets holds record_capacity + 1 */
+} sk_trim_output;
+
+enum { SK_TRIM_SE = 0, SK_TRIM_PE_SPLIT = 1, SK_TRIM_PE_INTERLEAVED = 2 };
+
+typedef struct {
+    uint64_t records[3], bytes[3]; /* what each output needs, also when it was not produced or did not fit */
+    uint64_t bad_read;             /* lowest read with an invalid kept cut, or UINT64_MAX */
+} sk_trim_counts;
+
+size_t sk_trim_workspace_bytes(uint64_t n_reads);
+/* Enqueues the trim of `batch` by `cuts` (n_reads entries, e.g. the output of sk_scan_device_async on the same stream).
+ * Returns SK_EINVAL for bad arguments, without enqueueing anything. */
+int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts, int mode, const sk_trim_output out[3],
+                         void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts from the workspace: SK_OK, SK_ESPACE (a produced output did not fit) or
+ * SK_EINVAL (an invalid kept cut, counts->bad_read). */
+int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_trim_counts *counts);
 
 /* Measurement aid (bench.py's second roofline denominator): streams `bytes` of device memory at
  * dev_buf through a read-only kernel (16-byte nt loads, nothing written) `launches` times on

@@ -3,4 +3,6 @@ pentalpha/sickle (reference src/trim.cpp:3-116) behind its `sickle se` / `sickle
 
 The product is native: sickle_amd/csrc/ holds the HIP kernels, the C-ABI library
 (include/sickle_amd.h -> libsickle_amd.so) and the C++ host pipeline (`sickle` binary).
-This Python package is only the ctypes view of that C ABI used by tests and bench.py."""
+This Python package is the ctypes view of that C ABI: tests and bench.py use it, and
+capi.Context.trim_reads_device gives torch users the trimmed reads of a device-resident
+batch (scan, sk_trim_device_async, finish) without leaving the device."""

@@ -9,7 +9,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsickle_amd.so")
 
-SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY = 0, 1, -1, -2, -3, -4
+SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE = 0, 1, -1, -2, -3, -4, -5
+SK_TRIM_SE, SK_TRIM_PE_SPLIT, SK_TRIM_PE_INTERLEAVED = 0, 1, 2
+TRIM_MODES = {"se": SK_TRIM_SE, "pe_split": SK_TRIM_PE_SPLIT, "pe_interleaved": SK_TRIM_PE_INTERLEAVED}
 QUALTYPES = {"phred": 0, "sanger": 1, "solexa": 2, "illumina": 3}
 
 # every entry point include/sickle_amd.h declares
@@ -18,7 +20,7 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_scan_device_async", "sk_scan_device_finish", "sk_trim_batch", "sk_submit", "sk_wait",
            "sk_kernel_for", "sk_kernel_name", "sk_seg_classes", "sk_probe_read_bandwidth",
            "sk_count_pairs_device_async", "sk_count_pairs_device_finish", "sk_bgzf_deflate", "sk_bgzf_host_alloc", "sk_bgzf_host_free",
-           "sk_bgzf_last_error")
+           "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish")
 
 
 class Params(C.Structure):
@@ -61,8 +63,28 @@ class PairCounts(C.Structure):
     _fields_ = [("both", C.c_uint64), ("only_first", C.c_uint64), ("only_second", C.c_uint64), ("none", C.c_uint64)]
 
 
+class TrimOutput(C.Structure):
+    _fields_ = [("qual", C.c_void_p), ("seq", C.c_void_p), ("offsets", C.c_void_p), ("read_index", C.c_void_p),
+                ("byte_capacity", C.c_uint64), ("record_capacity", C.c_uint64)]
+
+
+class TrimCounts(C.Structure):
+    _fields_ = [("records", C.c_uint64 * 3), ("bytes", C.c_uint64 * 3), ("bad_read", C.c_uint64)]
+
+    def as_dict(self):
+        return {"records": list(self.records), "bytes": list(self.bytes), "bad_read": int(self.bad_read)}
+
+
 class SickleError(RuntimeError):
     pass
+
+
+class TrimError(SickleError):
+    """sk_trim_device_finish returned SK_ESPACE or SK_EINVAL: `rc` says which, `counts` (dict) what it needs."""
+
+    def __init__(self, msg, rc, counts):
+        super().__init__(msg)
+        self.rc, self.counts = rc, counts
 
 
 class RangeError(SickleError):
@@ -134,6 +156,13 @@ def lib():
         L.sk_bgzf_deflate.restype = C.c_int
         L.sk_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.sk_bgzf_last_error.restype = C.c_char_p
+        L.sk_trim_workspace_bytes.restype = C.c_size_t
+        L.sk_trim_workspace_bytes.argtypes = [C.c_uint64]
+        L.sk_trim_device_async.restype = C.c_int
+        L.sk_trim_device_async.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int, C.POINTER(TrimOutput),
+                                           C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_trim_device_finish.restype = C.c_int
+        L.sk_trim_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TrimCounts)]
         _lib = L
     return _lib
 
@@ -240,6 +269,75 @@ class Context:
     def scan_device_finish(self, stream=None):
         err = Err()
         self._check(lib().sk_scan_device_finish(self._h, stream, C.byref(err)), err)
+
+    def trim_device_async(self, cuts_ptr, n_reads, outs, workspace_ptr, workspace_bytes, mode="se", qual_ptr=None,
+                          seq_ptr=None, offsets_ptr=None, stride=0, read_len=0, lengths_ptr=None, stream=None):
+        """sk_trim_device_async on raw device pointers; outs: up to three TrimOutput (missing ones are not produced)."""
+        arr = (TrimOutput * 3)(*list(outs)[:3])
+        b = Batch(qual_ptr, seq_ptr, offsets_ptr, stride, read_len, lengths_ptr, n_reads)
+        self._check(lib().sk_trim_device_async(self._h, C.byref(b), cuts_ptr, TRIM_MODES.get(mode, mode), arr,
+                                               workspace_ptr, workspace_bytes, stream))
+
+    def trim_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_device_finish -> counts (dict); raises TrimError (with .counts) on SK_ESPACE / SK_EINVAL."""
+        c = TrimCounts()
+        rc = lib().sk_trim_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc in (SK_ESPACE, SK_EINVAL):
+            raise TrimError("trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc)
+        return c.as_dict()
+
+    def trim_device(self, cuts_ptr, n_reads, outs, workspace_ptr, workspace_bytes, mode="se", stream=None, **batch):
+        """trim_device_async + trim_device_finish: the counts, or TrimError."""
+        self.trim_device_async(cuts_ptr, n_reads, outs, workspace_ptr, workspace_bytes, mode=mode, stream=stream, **batch)
+        return self.trim_device_finish(workspace_ptr, stream)
+
+    def trim_reads_device(self, params, qual, seq=None, offsets=None, stride=0, read_len=0, lengths=None, mode="se",
+                          cuts=None):
+        """Scan (unless `cuts`, a device int32 [n, 2] tensor, is given), trim and finish a device-resident batch of torch
+        tensors (uint8 qual / seq, uint64-valued int64 offsets, int32 lengths) on the current stream.  Returns a tuple of
+        three entries, one per output of the mode (None where the mode has no such output): (qual, seq, offsets,
+        read_index) tensors narrowed to their counts (seq None without seq).  A count-only pass sizes the outputs."""
+        import torch
+        dev = qual.device
+        if offsets is not None:
+            n = offsets.numel() - 1
+        elif lengths is not None:
+            n = lengths.numel()
+        else:
+            n = qual.numel() // stride if stride else 0
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        batch = dict(qual_ptr=ptr(qual), seq_ptr=ptr(seq), offsets_ptr=ptr(offsets), stride=stride, read_len=read_len,
+                     lengths_ptr=ptr(lengths))
+        if cuts is None:
+            cuts = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+            if n:
+                self.scan_device_async(params, ptr(qual), cuts.data_ptr(), n, stride=stride, read_len=read_len,
+                                       seq_ptr=ptr(seq) if params.trunc_n else None, offsets_ptr=ptr(offsets),
+                                       lengths_ptr=ptr(lengths), stream=stream)
+                self.scan_device_finish(stream)
+        ws_bytes = lib().sk_trim_workspace_bytes(n)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        counts = self.trim_device(cuts.data_ptr(), n, [TrimOutput() for _ in range(3)], ws.data_ptr(), ws_bytes,
+                                  mode=mode, stream=stream, **batch)
+        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        bufs, outs = [None] * 3, [TrimOutput() for _ in range(3)]
+        for o in used:
+            R, B = counts["records"][o], counts["bytes"][o]
+            q = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)
+            s = torch.empty(max(B, 1), dtype=torch.uint8, device=dev) if seq is not None else None
+            off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+            idx = torch.empty(max(R, 1), dtype=torch.int64, device=dev)
+            bufs[o] = (q, s, off, idx)
+            outs[o] = TrimOutput(q.data_ptr(), ptr(s), off.data_ptr(), idx.data_ptr(), B, R)
+        counts = self.trim_device(cuts.data_ptr(), n, outs, ws.data_ptr(), ws_bytes, mode=mode, stream=stream, **batch)
+        res = [None] * 3
+        for o in used:
+            q, s, off, idx = bufs[o]
+            R, B = counts["records"][o], counts["bytes"][o]
+            res[o] = (q[:B], None if s is None else s[:B], off, idx[:R])
+        return tuple(res)
 
 
 BGZF_INPUT = 65280   # bytes of text per BGZF block

@@ -681,6 +681,74 @@ int sk_count_pairs_device_finish(sk_ctx *ctx, void *hip_stream, sk_pair_counts *
     return SK_OK;
 }
 
+size_t sk_trim_workspace_bytes(uint64_t n_reads)
+{
+    const uint64_t blocks = (n_reads + SK_TRIM_BLOCK_READS - 1) / SK_TRIM_BLOCK_READS;
+    return (size_t)(8 * (SK_TRIM_HDR_WORDS + SK_TRIM_BLOCK_WORDS * blocks + n_reads));
+}
+
+int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts, int mode, const sk_trim_output out[3],
+                         void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+#define SK_TRIM_BAD(...)              \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!batch || !out) SK_TRIM_BAD("sk_trim_device_async: batch and out are required");
+    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_TRIM_BAD("trim mode %d is unknown", mode);
+    const uint64_t n = batch->n_reads;
+    if (batch->tiles) SK_TRIM_BAD("trim: segmented batches are not supported");
+    if (mode != SK_TRIM_SE && (n & 1)) SK_TRIM_BAD("trim: a paired mode needs an even number of reads, not %llu", (unsigned long long)n);
+    if (n && (!batch->qual || !cuts)) SK_TRIM_BAD("trim: qual and cuts are required");
+    if (reinterpret_cast<uintptr_t>(cuts) & 7) SK_TRIM_BAD("trim: cuts must be 8-byte aligned");
+    if (!batch->offsets) {
+        if (batch->stride == 0 || (!batch->lengths && (batch->read_len > batch->stride || batch->read_len > SK_MAX_READ_LEN)))
+            SK_TRIM_BAD("trim: fixed-stride batch: need stride >= read_len (<= %u), or lengths", SK_MAX_READ_LEN);
+    }
+    for (int o = 0; o < 3; ++o) {
+        const bool used = o == 0 || (mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2);
+        if (!used || !out[o].offsets) continue;
+        if ((reinterpret_cast<uintptr_t>(out[o].qual) | reinterpret_cast<uintptr_t>(out[o].seq)) & 15)
+            SK_TRIM_BAD("trim: out[%d].qual and out[%d].seq must be 16-byte aligned", o, o);
+        if ((reinterpret_cast<uintptr_t>(out[o].offsets) | reinterpret_cast<uintptr_t>(out[o].read_index)) & 7)
+            SK_TRIM_BAD("trim: out[%d].offsets and out[%d].read_index must be 8-byte aligned", o, o);
+        if (n && out[o].seq && !batch->seq) SK_TRIM_BAD("trim: out[%d].seq needs batch->seq", o);
+    }
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < sk_trim_workspace_bytes(n))
+        SK_TRIM_BAD("trim: workspace must be 16-byte aligned and hold sk_trim_workspace_bytes(%llu) = %zu bytes",
+                    (unsigned long long)n, sk_trim_workspace_bytes(n));
+#undef SK_TRIM_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_trim(batch, reinterpret_cast<const sk_cut_dev *>(cuts), mode, out, workspace, ctx->cu_count,
+                               static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_trim_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[SK_TRIM_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    int rc = SK_OK;
+    for (int o = 0; o < 3; ++o) {
+        counts->records[o] = h[SK_TRIM_H_RECORDS + o];
+        counts->bytes[o] = h[SK_TRIM_H_BYTES + o];
+        if (h[SK_TRIM_H_PRODUCED + o] && !h[SK_TRIM_H_FIT + o]) rc = SK_ESPACE;
+    }
+    counts->bad_read = h[SK_TRIM_H_BAD];
+    if (counts->bad_read != UINT64_MAX) {
+        set_error(ctx, "trim: read %llu has an invalid kept cut", (unsigned long long)counts->bad_read);
+        return SK_EINVAL;
+    }
+    if (rc == SK_ESPACE) set_error(ctx, "trim: an output's buffers are too small for what it needs");
+    return rc;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

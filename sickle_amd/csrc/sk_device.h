@@ -119,6 +119,21 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sorted(con
                                        unsigned long long *errword, const sk_scan_args *a, int cu_count, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_pair_count(const sk_cut_dev *cuts, uint64_t n_pairs, uint8_t *classes,
                                            unsigned long long *counters, int cu_count, hipStream_t stream);
+// device-side trimming (sk_trim.hip).  The caller's workspace, in 8-byte words: the header (SK_TRIM_HDR_WORDS), the table of
+// the count kernel (SK_TRIM_BLOCK_WORDS per block of SK_TRIM_BLOCK_READS reads: records[3], bytes[3], lowest bad read; the
+// scan turns records and bytes into the block's exclusive bases), then one source delta per record of the three outputs.
+#define SK_TRIM_BLOCK_READS 2048u
+#define SK_TRIM_BLOCK_WORDS 8u
+#define SK_TRIM_HDR_WORDS 16u
+#define SK_TRIM_H_RECORDS 0  // [3]
+#define SK_TRIM_H_BYTES 3    // [3]
+#define SK_TRIM_H_BAD 6      // lowest read with an invalid kept cut, or ~0
+#define SK_TRIM_H_PRODUCED 7 // [3] offsets != NULL for an output of the mode
+#define SK_TRIM_H_FIT 10     // [3] produced, no bad cut, and within its capacities: the place and gather kernels write it
+#define SK_TRIM_GATHER_WG_PER_CU 7u // the gather kernel's occupancy (SGPR-bound): a persistent grid with no second round
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const sk_batch *b, const sk_cut_dev *cuts, int mode,
+                                                                           const sk_trim_output *out, void *workspace,
+                                                                           int cu_count, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
