@@ -77,7 +77,8 @@ enum {
     SK_ENODEV = -2, /* no usable gfx950 device */
     SK_EHIP = -3,   /* a HIP runtime call failed: see sk_last_error() */
     SK_EBUSY = -4,  /* slot still in flight */
-    SK_ESPACE = -5  /* sk_trim_device_finish: an output's buffers are too small (counts say what it needs) */
+    SK_ESPACE = -5, /* sk_trim_device_finish: an output's buffers are too small (counts say what it needs) */
+    SK_EFORMAT = -6 /* sk_trim_fastq_device_finish: a malformed FASTQ record (counts say which and why) */
 };
 
 #define SK_TILE_MAX_STRIDE 512u /* two LDS buffers of 64 reads per wave must fit the 160 KiB of a CU */
@@ -301,6 +302,84 @@ int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts,
 /* Waits for hip_stream and fills *counts from the workspace: SK_OK, SK_ESPACE (a produced output did not fit) or
  * SK_EINVAL (an invalid kept cut, counts->bad_read). */
 int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_trim_counts *counts);
+
+/*
+ * FASTQ text on the device: the whole of a trim, from FASTQ text in device memory to the trimmed FASTQ text, byte-identical
+ * to the files of the reference at -a 1.  Every pointer in the structs below is a DEVICE pointer.
+ *
+ * Lines end at '\n' only; a '\r' belongs to its line (as in the reference: a CRLF quality line is a range error).  A last
+ * line without '\n' ends at the end of the text (the CLI's reader drops its last character instead, DESIGN 1: the library
+ * trims the records it is handed).  A record is four consecutive lines counted from the start of the text; lines after
+ * the last complete record are counted in tail_lines and not trimmed (the CLI drops lines still carried at EOF).
+ * Checks per record, in the order of reference src/FQEntry.cpp:53-97, the first failing one is its reason: the name line
+ * has at most 1 byte (SK_FQ_ID_SHORT), it does not start with '@' (SK_FQ_ID_NO_AT), the seq line is empty
+ * (SK_FQ_SEQ_EMPTY), the qual line is empty (SK_FQ_QUAL_EMPTY), their lengths differ (SK_FQ_LENGTHS); then a qual line
+ * longer than SK_MAX_READ_LEN (SK_FQ_TOO_LONG).  The '+' line is not checked and is copied verbatim.  The lowest
+ * malformed record in read order makes finish return SK_EFORMAT.
+ * Modes (sk_trim_device_async's): SK_TRIM_SE and SK_TRIM_PE_INTERLEAVED read text[0]; SK_TRIM_PE_SPLIT reads mate 1 from
+ * text[0] and mate 2 from text[1], which must frame to the same record count (else SK_EFORMAT with SK_FQ_PAIR_COUNT at the
+ * first record without a mate: the CLI's "Batch2 and Batch1 have different lengths").  SK_TRIM_PE_INTERLEAVED with an odd
+ * record count drops the last record (dropped_unpaired = 1) after checking it, as the CLI does.
+ * Read numbers (range.read, record_index): SE and interleaved: the record number; split: record k of text[0] is read 2k,
+ * record k of text[1] is read 2k + 1.
+ * The scan is sk_scan_device_async with `params` on the qual (and, with trunc_n, seq) lines packed into an `offsets`
+ * batch in the workspace, with in->max_read_len as its length hint (0 = unknown); a range error makes finish return
+ * SK_ERANGE with counts->range (what the CLI prints).  A format error beats a range error (the reference frames a whole
+ * batch before it scans it).  On either error nothing is written to any output.
+ * Emission: every kept record as name '\n' seq[five:three] '\n' plus '\n' qual[five:three] '\n' (reference
+ * src/trim_single.cpp:393-396), in read order (the -a 1 order), routed by the pair rule of sk_trim_device_async:
+ *   SK_TRIM_SE              out[0]: every kept record
+ *   SK_TRIM_PE_SPLIT        out[0]: mate 1 of the pairs with both kept, out[1]: their mate 2, out[2]: singles
+ *   SK_TRIM_PE_INTERLEAVED  out[0]: both mates of such pairs, out[2]: singles
+ * An output is produced iff its text is not NULL (16-byte aligned); record_index (8-byte aligned, or NULL) then gets the
+ * read number of each record.  An output whose bytes exceed capacity, or whose records exceed record_capacity while
+ * record_index is given, gets nothing written; finish then returns SK_ESPACE with the counts.  With every text NULL the
+ * call only counts.  Inputs may have any alignment and any size (64-bit offsets); a text of 32 GiB or more is SK_EINVAL
+ * (the packed batch would reach 2^32 reads).
+ *
+ * sk_trim_fastq_device_async only enqueues kernels on hip_stream: no copy, no synchronisation, no allocation beyond the
+ * one sk_scan_device_async makes on its own (the regrouping scratch of a context's first big mixed batch).  All scratch
+ * lives in `workspace` (device, 16-byte aligned), sized without a look at the text by the most records and qual bytes a
+ * valid text of T = bytes[0] + bytes[1] bytes can hold.  With H = floor((T + 2) / 16):
+ *   sk_trim_fastq_workspace_bytes(T, trunc_n) = 544 + 144 H + 16 floor(T / 65536) + 64 ceil((H + 1) / 1024)
+ *                                               + (trunc_n ? 2 : 1) * 16 ceil(T / 32)
+ * i.e. about 9.5 bytes per text byte (10 with trunc_n).  It holds for any text, malformed ones included.  finish is the
+ * only call that waits: it reads the counts out of the workspace and reads and clears the stream's range-error word (a
+ * later sk_scan_device_finish on that stream does not report it again).  Two calls in flight need two workspaces.
+ */
+enum { SK_FQ_OK = 0, SK_FQ_ID_SHORT = 1, SK_FQ_ID_NO_AT = 2, SK_FQ_SEQ_EMPTY = 3, SK_FQ_QUAL_EMPTY = 4, SK_FQ_LENGTHS = 5,
+       SK_FQ_TOO_LONG = 6, SK_FQ_PAIR_COUNT = 7 };
+
+typedef struct {
+    const uint8_t *text[2]; /* device, any alignment; text[1] only (and required) for SK_TRIM_PE_SPLIT */
+    uint64_t bytes[2];
+    uint32_t max_read_len;  /* optional hint, 0 = unknown: the stride (longest-read hint) of the packed batch */
+} sk_fastq_input;
+
+typedef struct {
+    uint8_t *text;            /* device, 16-byte aligned, or NULL = output not produced */
+    uint64_t capacity;        /* bytes */
+    uint64_t *record_index;   /* device, 8-byte aligned, or NULL: the read number of each emitted record */
+    uint64_t record_capacity;
+} sk_fastq_output;
+
+typedef struct {
+    uint64_t records_in[2];        /* complete records framed per input */
+    uint64_t tail_lines[2];        /* lines after the last complete record: not trimmed, not an error */
+    uint64_t dropped_unpaired;     /* SK_TRIM_PE_INTERLEAVED with an odd record count: 1 */
+    uint64_t records[3], bytes[3]; /* what each output needs, also when not produced or too small (0 after an error) */
+    int32_t format_error;          /* SK_FQ_* of the lowest malformed record, SK_FQ_OK if none */
+    uint32_t format_input;         /* 0 / 1 */
+    uint64_t format_record;        /* 0-based record number within that input */
+    sk_err range;                  /* filled on SK_ERANGE; range.read in the read numbering above */
+} sk_fastq_counts;
+
+size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n);
+/* Enqueues the trim of the FASTQ text(s) of *in.  Returns SK_EINVAL for bad arguments, without enqueueing anything. */
+int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                               const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts: SK_OK, SK_EFORMAT, SK_ERANGE or SK_ESPACE (in this order of precedence). */
+int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts);
 
 /* Measurement aid (bench.py's second roofline denominator): streams `bytes` of device memory at
  * dev_buf through a read-only kernel (16-byte nt loads, nothing written) `launches` times on

@@ -9,7 +9,10 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsickle_amd.so")
 
-SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE = 0, 1, -1, -2, -3, -4, -5
+SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE, SK_EFORMAT = 0, 1, -1, -2, -3, -4, -5, -6
+# why a FASTQ record is malformed (sk_trim_fastq_device_finish), in the order the reference checks
+(SK_FQ_OK, SK_FQ_ID_SHORT, SK_FQ_ID_NO_AT, SK_FQ_SEQ_EMPTY, SK_FQ_QUAL_EMPTY, SK_FQ_LENGTHS, SK_FQ_TOO_LONG,
+ SK_FQ_PAIR_COUNT) = range(8)
 SK_TRIM_SE, SK_TRIM_PE_SPLIT, SK_TRIM_PE_INTERLEAVED = 0, 1, 2
 TRIM_MODES = {"se": SK_TRIM_SE, "pe_split": SK_TRIM_PE_SPLIT, "pe_interleaved": SK_TRIM_PE_INTERLEAVED}
 QUALTYPES = {"phred": 0, "sanger": 1, "solexa": 2, "illumina": 3}
@@ -20,7 +23,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_scan_device_async", "sk_scan_device_finish", "sk_trim_batch", "sk_submit", "sk_wait",
            "sk_kernel_for", "sk_kernel_name", "sk_seg_classes", "sk_probe_read_bandwidth",
            "sk_count_pairs_device_async", "sk_count_pairs_device_finish", "sk_bgzf_deflate", "sk_bgzf_host_alloc", "sk_bgzf_host_free",
-           "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish")
+           "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish",
+           "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish")
 
 
 class Params(C.Structure):
@@ -75,6 +79,28 @@ class TrimCounts(C.Structure):
         return {"records": list(self.records), "bytes": list(self.bytes), "bad_read": int(self.bad_read)}
 
 
+class FastqInput(C.Structure):
+    _fields_ = [("text", C.c_void_p * 2), ("bytes", C.c_uint64 * 2), ("max_read_len", C.c_uint32)]
+
+
+class FastqOutput(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("capacity", C.c_uint64), ("record_index", C.c_void_p),
+                ("record_capacity", C.c_uint64)]
+
+
+class FastqCounts(C.Structure):
+    _fields_ = [("records_in", C.c_uint64 * 2), ("tail_lines", C.c_uint64 * 2), ("dropped_unpaired", C.c_uint64),
+                ("records", C.c_uint64 * 3), ("bytes", C.c_uint64 * 3), ("format_error", C.c_int32),
+                ("format_input", C.c_uint32), ("format_record", C.c_uint64), ("range", Err)]
+
+    def as_dict(self):
+        return {"records_in": list(self.records_in), "tail_lines": list(self.tail_lines),
+                "dropped_unpaired": int(self.dropped_unpaired), "records": list(self.records),
+                "bytes": list(self.bytes), "format_error": int(self.format_error),
+                "format_input": int(self.format_input), "format_record": int(self.format_record),
+                "range": (int(self.range.read), int(self.range.pos), int(self.range.ch))}
+
+
 class SickleError(RuntimeError):
     pass
 
@@ -85,6 +111,14 @@ class TrimError(SickleError):
     def __init__(self, msg, rc, counts):
         super().__init__(msg)
         self.rc, self.counts = rc, counts
+
+
+class FormatError(SickleError):
+    """sk_trim_fastq_device_finish returned SK_EFORMAT: `reason` (SK_FQ_*) of record `record` of input `input`."""
+
+    def __init__(self, reason, input, record, counts=None):
+        super().__init__("malformed FASTQ record %d of input %d (reason %d)" % (record, input, reason))
+        self.reason, self.input, self.record, self.counts = reason, input, record, counts
 
 
 class RangeError(SickleError):
@@ -163,6 +197,13 @@ def lib():
                                            C.c_void_p, C.c_size_t, C.c_void_p]
         L.sk_trim_device_finish.restype = C.c_int
         L.sk_trim_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TrimCounts)]
+        L.sk_trim_fastq_workspace_bytes.restype = C.c_size_t
+        L.sk_trim_fastq_workspace_bytes.argtypes = [C.c_uint64, C.c_int32]
+        L.sk_trim_fastq_device_async.restype = C.c_int
+        L.sk_trim_fastq_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput), C.c_int,
+                                                 C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_trim_fastq_device_finish.restype = C.c_int
+        L.sk_trim_fastq_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts)]
         _lib = L
     return _lib
 
@@ -338,6 +379,61 @@ class Context:
             R, B = counts["records"][o], counts["bytes"][o]
             res[o] = (q[:B], None if s is None else s[:B], off, idx[:R])
         return tuple(res)
+
+    # ---- FASTQ text on the device -------------------------------------------------------------
+    def trim_fastq_device_async(self, params, text_ptrs, text_bytes, outs, workspace_ptr, workspace_bytes, mode="se",
+                                max_read_len=0, stream=None):
+        """sk_trim_fastq_device_async on raw device pointers; text_ptrs / text_bytes: one or two entries, outs: up to
+        three FastqOutput (missing ones are not produced)."""
+        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bytes) + [0] * (2 - len(text_bytes))
+        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
+        arr = (FastqOutput * 3)(*list(outs)[:3])
+        self._check(lib().sk_trim_fastq_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
+                                                     arr, workspace_ptr, workspace_bytes, stream))
+
+    def trim_fastq_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_fastq_device_finish -> counts (dict); raises FormatError, RangeError or TrimError (SK_ESPACE)."""
+        c = FastqCounts()
+        rc = lib().sk_trim_fastq_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc == SK_EFORMAT:
+            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), c.as_dict())
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc, c.range)
+        return c.as_dict()
+
+    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False):
+        """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
+        current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
+        three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
+        record_index=True a pair (text, index) with the read number of each record (int64).  Raises FormatError,
+        RangeError or TrimError."""
+        import torch
+        dev = text.device
+        texts = [text] if text2 is None else [text, text2]
+        ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        run = lambda outs: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                                         max_read_len=max_read_len, stream=stream),
+                            self.trim_fastq_device_finish(ws.data_ptr(), stream))[1]
+        counts = run([FastqOutput() for _ in range(3)])
+        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        bufs, outs = [None] * 3, [FastqOutput() for _ in range(3)]
+        for o in used:
+            R, B = counts["records"][o], counts["bytes"][o]
+            t = torch.empty(max(B, 16), dtype=torch.uint8, device=dev)
+            idx = torch.empty(max(R, 1), dtype=torch.int64, device=dev) if record_index else None
+            bufs[o] = (t, idx)
+            outs[o] = FastqOutput(t.data_ptr(), B, idx.data_ptr() if record_index else None, R)
+        counts = run(outs)
+        res = [None] * 3
+        for o in used:
+            t, idx = bufs[o]
+            R, B = counts["records"][o], counts["bytes"][o]
+            res[o] = (t[:B], idx[:R]) if record_index else t[:B]
+        return tuple(res), counts
 
 
 BGZF_INPUT = 65280   # bytes of text per BGZF block

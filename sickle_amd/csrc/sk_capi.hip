@@ -749,6 +749,107 @@ int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_tri
     return rc;
 }
 
+size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n)
+{
+    sk_fq_layout L;
+    sk_fq_layout_of(text_bytes, trunc_n, &L);
+    return (size_t)L.total;
+}
+
+int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                               const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+#define SK_FQ_BAD(...)                \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!params || !in || !out) SK_FQ_BAD("sk_trim_fastq_device_async: params, in and out are required");
+    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_FQ_BAD("trim mode %d is unknown", mode);
+    const bool split = mode == SK_TRIM_PE_SPLIT;
+    if (split && !in->text[1]) SK_FQ_BAD("fastq: SK_TRIM_PE_SPLIT needs text[1]");
+    if (!split && (in->text[1] || in->bytes[1])) SK_FQ_BAD("fastq: text[1] is only for SK_TRIM_PE_SPLIT");
+    for (int i = 0; i < (split ? 2 : 1); ++i)
+        if (!in->text[i] && in->bytes[i]) SK_FQ_BAD("fastq: text[%d] is NULL with %llu bytes", i, (unsigned long long)in->bytes[i]);
+    for (int o = 0; o < 3; ++o) {
+        if (reinterpret_cast<uintptr_t>(out[o].text) & 15) SK_FQ_BAD("fastq: out[%d].text must be 16-byte aligned", o);
+        if (reinterpret_cast<uintptr_t>(out[o].record_index) & 7) SK_FQ_BAD("fastq: out[%d].record_index must be 8-byte aligned", o);
+    }
+    const uint64_t T = in->bytes[0] + (split ? in->bytes[1] : 0);
+    if (sk_fq_pack_reads(in->bytes[0], split ? in->bytes[1] : 0, mode) >= (1ull << 32))
+        SK_FQ_BAD("fastq: %llu bytes of text is beyond what one call takes", (unsigned long long)T);
+    const size_t need = sk_trim_fastq_workspace_bytes(T, params->trunc_n);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
+        SK_FQ_BAD("fastq: workspace must be 16-byte aligned and hold sk_trim_fastq_workspace_bytes(%llu, %d) = %zu bytes",
+                  (unsigned long long)T, params->trunc_n, need);
+#undef SK_FQ_BAD
+    sk_scan_args chk;
+    const uint64_t no_reads = 0;
+    sk_batch probe = {};
+    probe.offsets = &no_reads; // an empty `offsets` batch: only params is checked
+    int rc = make_args(ctx, params, &probe, &chk); // the parameter checks of the scan, before anything is enqueued
+    if (rc != SK_OK) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    sk_batch packed;
+    sk_cut_dev *cuts;
+    SK_HIP(ctx, sk_launch_fastq_front(in, mode, params->trunc_n, workspace, ctx->cu_count, stream, &packed, &cuts));
+    rc = sk_scan_device_async(ctx, params, &packed, reinterpret_cast<sk_cut *>(cuts), hip_stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, out, workspace, d_err, ctx->cu_count, stream));
+    return SK_OK;
+}
+
+int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    int rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    uint64_t h[SK_FQ_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipMemcpyAsync(h_err, d_err, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    rc = reset_error_word(ctx, d_err, stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    *counts = sk_fastq_counts{};
+    for (int i = 0; i < 2; ++i) {
+        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
+        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] & 3;
+    }
+    const uint64_t fmt = h[SK_FQ_H_FMT];
+    const bool bad = fmt != ~0ull, split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
+    counts->dropped_unpaired = h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
+    for (int o = 0; o < 3; ++o) {
+        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
+        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
+    }
+    if (bad) {
+        const uint64_t read = fmt >> 3;
+        counts->format_error = (int32_t)(fmt & 7);
+        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
+        counts->format_record = split ? read >> 1 : read;
+        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
+                  (unsigned long long)counts->format_record, counts->format_error);
+        return SK_EFORMAT;
+    }
+    if (decode_error(*h_err, &counts->range) == SK_ERANGE) {
+        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
+                  counts->range.pos + 1);
+        return SK_ERANGE;
+    }
+    for (int o = 0; o < 3; ++o)
+        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
+    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
+    return rc;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

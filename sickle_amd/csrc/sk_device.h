@@ -134,6 +134,67 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_pair_count
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const sk_batch *b, const sk_cut_dev *cuts, int mode,
                                                                            const sk_trim_output *out, void *workspace,
                                                                            int cu_count, hipStream_t stream);
+// FASTQ text on the device (sk_fastq.hip).  The caller's workspace (16-byte sections, sizes in bytes, T = text bytes of all
+// inputs, H = (T + 2) / 16):
+//   header    SK_FQ_HDR_WORDS words
+//   chunks    16 per framing chunk of SK_FQ_CHUNK_BYTES (T / 65536 + 3 chunks at most over both inputs): '\n' count, last '\n'
+//   desc      40 per record slot, 2H + 4 slots: name start and the end of each of the four lines of record k
+//   offsets   8 * (N + 2), N = 2H + 2: the packed batch's offsets (n_pack + 1 of them)
+//   cuts      8 * N
+//   blocks    64 per block of SK_FQ_BLOCK_READS packed reads (the pack's, then the emission's block table)
+//   emit      16 * N: output offset and read of every emitted record
+//   qual, seq 16 * ceil(T / 32) each (seq only with trunc_n): the packed batch
+// Sizing by the worst case, without a look at the text: a valid record is at least 8 bytes ("@a\nA\n+\nI\n"; 7 for an
+// unterminated last one), so text i of b bytes holds at most (b + 1) / 8 valid records and at most b / 2 bytes of qual.
+// It gets (b + 1) / 8 + 1 slots: the first slots records cannot all be valid in a text with more, so a record that gets
+// no slot is never the lowest malformed one, and a text with more records than the packed batch holds is SK_EFORMAT.
+#define SK_FQ_CHUNK_BYTES 65536u
+#define SK_FQ_BLOCK_READS 2048u
+#define SK_FQ_BLOCK_WORDS 8u
+#define SK_FQ_HDR_WORDS 32u
+#define SK_FQ_H_LINES 0        // [2] lines of each input
+#define SK_FQ_H_RECORDS 2      // [2] complete records of each input
+#define SK_FQ_H_FMT 4          // (read << 3) | SK_FQ_* of the lowest malformed record, or ~0
+#define SK_FQ_H_NREAL 5        // reads of the packed batch that are records (the rest are empty)
+#define SK_FQ_H_PACKED 6       // bytes of the packed qual (and seq)
+#define SK_FQ_H_OUT_RECORDS 7  // [3]
+#define SK_FQ_H_OUT_BYTES 10   // [3]
+#define SK_FQ_H_FIT 13         // [3] produced, no error, within its capacities: the emission writes it
+#define SK_FQ_H_PRODUCED 16    // [3] out[o].text != NULL for an output of the mode
+#define SK_FQ_H_RANGE 19       // the stream's range-error word as the emission saw it
+#define SK_FQ_H_MODE 20        // the call's mode
+struct sk_fq_layout {
+    uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
+};
+static inline uint64_t sk_fq_slots(uint64_t bytes) { return (bytes + 1) / 8 + 1; }
+// reads of the packed batch: the most valid records the text(s) can hold
+static inline uint64_t sk_fq_pack_reads(uint64_t bytes0, uint64_t bytes1, int mode)
+{
+    const uint64_t r0 = (bytes0 + 1) / 8, r1 = (bytes1 + 1) / 8;
+    return mode == SK_TRIM_PE_SPLIT ? 2 * (r0 < r1 ? r0 : r1) : r0;
+}
+static inline void sk_fq_layout_of(uint64_t text_bytes, int trunc_n, sk_fq_layout *L)
+{
+    const uint64_t H = (text_bytes + 2) / 16, S = 2 * H + 4, N = 2 * H + 2;
+    const uint64_t NC = text_bytes / SK_FQ_CHUNK_BYTES + 3, NB = (N + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
+    const uint64_t Q = 16 * ((text_bytes + 31) / 32);
+    L->chunks = 8 * SK_FQ_HDR_WORDS;
+    L->desc = L->chunks + 16 * NC;
+    L->offsets = L->desc + 40 * S;
+    L->cuts = L->offsets + 8 * (N + 2);
+    L->blocks = L->cuts + 8 * N;
+    L->emit = L->blocks + 64 * NB;
+    L->qual = L->emit + 16 * N;
+    L->seq = L->qual + Q;
+    L->total = L->seq + (trunc_n ? Q : 0);
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                  void *workspace, int cu_count, hipStream_t stream,
+                                                                                  sk_batch *packed, sk_cut_dev **cuts);
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                 const sk_fastq_output *out, void *workspace,
+                                                                                 const unsigned long long *errword, int cu_count,
+                                                                                 hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif

@@ -1,0 +1,828 @@
+// sk_fastq.hip -- FASTQ text on the device (sk_trim_fastq_device_async): frame the text into records, check them the way
+// reference src/FQEntry.cpp:53-97 does, pack qual (and seq) into an `offsets` batch for the scan, and write the kept
+// records back as FASTQ text in the record format of src/trim_single.cpp:393-396, routed by the pair rule.
+//
+// Launches on one stream, no inter-workgroup waiting (workgroup dispatch order is undefined):
+//   frame   1 count  per 64 KiB chunk of text: '\n' count and the last '\n'
+//           2 scan   one workgroup: chunk bases (first line number, last '\n' before the chunk), the unterminated last
+//                    line, line / record totals, the pair-count verdict
+//           3 lines  per chunk again: every '\n' gives the end of line ln and the start of line ln + 1; the line ends of
+//                    record ln / 4 go to its descriptor slot
+//           4 check  the checks of every framed record, the lowest failing (read, reason) by a global atomicMin
+//   pack    5 count / 6 scan / 7 place   qual lengths -> offsets[] of the packed batch (reduce-then-scan over blocks)
+//           8 gather qual (and seq) of every record into the workspace: output-partitioned, aligned 16-byte stores
+//   (the scan: sk_scan_device_async on the packed batch, launched by sk_capi.hip)
+//   emit    9 count / 10 scan / 11 place  the pair rule over the cuts: output offset and read of every kept record
+//           12 gather the records' bytes: name line, seq[five:three], '\n', '+' line, qual[five:three], '\n'
+// The workspace layout and the header words are in sk_device.h.  The gathers build aligned 16-byte granules from aligned
+// 16-byte loads funnel-shifted by v_alignbyte (fq_load_window, a copy of sk_trim.hip's load_window), so the text may
+// have any alignment and no load touches a 16-byte block without a wanted byte.
+#include <hip/hip_runtime.h>
+
+#include "sk_device.h"
+
+namespace {
+
+typedef unsigned fq_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned __int128 fq_u128;
+
+#define FQ_THREADS 256
+#define FQ_SUB (FQ_THREADS * 16u)                        // text bytes of one pass of a framing workgroup
+#define FQ_PER_THREAD (SK_FQ_BLOCK_READS / FQ_THREADS)  // consecutive reads of one lane (even: pairs stay whole)
+#define FQ_GPL 2                                         // 16-byte granules per lane and chunk of a gather
+#define FQ_GCHUNK (FQ_THREADS * 16u * FQ_GPL)
+#define FQ_WIN 128 // records of a gather chunk staged in LDS (further ones are searched in global memory)
+
+static_assert(SK_FQ_CHUNK_BYTES % FQ_SUB == 0, "a framing chunk is whole passes");
+static_assert(FQ_PER_THREAD % 2 == 0, "a lane must hold whole pairs");
+
+struct fq_out {
+    uint8_t *text;
+    uint64_t cap;
+    uint64_t *index;
+    uint64_t rec_cap;
+};
+
+struct fq_args {
+    const uint8_t *text[2];
+    uint64_t bytes[2];
+    uint64_t n_chunks[2];
+    uint64_t slots[2];
+    int32_t mode;
+    int32_t trunc_n;
+    uint64_t n_pack, n_blocks;
+    uint64_t *hdr;
+    uint64_t *chunks; // 2 words per chunk, input 0's chunks first
+    uint64_t *desc[2]; // 5 words per slot: name start, then the end ('\n' or end of text) of each of the four lines
+    uint64_t *offsets; // n_pack + 1
+    sk_cut_dev *cuts;
+    uint64_t *blk;  // SK_FQ_BLOCK_WORDS per block of SK_FQ_BLOCK_READS packed reads (pack, then emit)
+    uint64_t *emit; // 2 words per kept record: output offset, read
+    uint8_t *pq, *ps;
+    const unsigned long long *errword;
+    fq_out out[3];
+};
+
+// ------------------------------------------------------------------------------------------
+// shared pieces
+// ------------------------------------------------------------------------------------------
+// the '\n' bytes of the aligned 16-byte block at q (offset from the aligned base of text i) that lie inside the text:
+// bit b = byte q + b.  A block without a byte of the text is not loaded.
+__device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t q)
+{
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, span = sh + a.bytes[i];
+    if (q + 16 <= sh || q >= span) return 0;
+    const fq_u4 *blk = reinterpret_cast<const fq_u4 *>((reinterpret_cast<uintptr_t>(a.text[i]) & ~(uintptr_t)15) + q);
+    const fq_u4 v = __builtin_nontemporal_load(blk);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t x = w[j] ^ 0x0a0a0a0au;                              // '\n' -> 0
+        const uint32_t z = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu); // exact: 0x80 in every zero byte
+        const uint32_t b = z >> 7;                                            // bits 0, 8, 16, 24
+        m |= ((b | (b >> 7) | (b >> 14) | (b >> 21)) & 0xfu) << (4 * j);
+    }
+    const uint32_t lo = q < sh ? (uint32_t)(sh - q) : 0u, hi = span - q < 16 ? (uint32_t)(span - q) : 16u;
+    return m & (((1u << hi) - 1u) & ~((1u << lo) - 1u));
+}
+
+// exclusive prefix sum of s and exclusive prefix max of m over the workgroup, and both totals.  lds: 8 words.
+__device__ __forceinline__ void fq_scan2(uint64_t s, uint64_t m, uint64_t &s_ex, uint64_t &m_ex, uint64_t &s_tot,
+                                         uint64_t &m_tot, uint64_t *lds)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint64_t is = s, im = m;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t ts = __shfl_up(is, d), tm = __shfl_up(im, d);
+        if (lane >= d) {
+            is += ts;
+            im = max(im, tm);
+        }
+    }
+    uint64_t pm = __shfl_up(im, 1);
+    if (lane == 0) pm = 0;
+    if (lane == 63) {
+        lds[2 * w] = is;
+        lds[2 * w + 1] = im;
+    }
+    __syncthreads();
+    uint64_t bs = 0, bm = 0, ts = 0, tm = 0;
+#pragma unroll
+    for (int ww = 0; ww < FQ_THREADS / 64; ++ww) {
+        const uint64_t x = lds[2 * ww], y = lds[2 * ww + 1];
+        if (ww < w) {
+            bs += x;
+            bm = max(bm, y);
+        }
+        ts += x;
+        tm = max(tm, y);
+    }
+    s_ex = bs + is - s;
+    m_ex = max(bm, pm);
+    s_tot = ts;
+    m_tot = tm;
+    __syncthreads();
+}
+
+// exclusive prefix sums of N values over the workgroup; total[] = the sums over it.  lds: 4 * N words.  (== block_scan
+// of sk_trim.hip)
+template <int N>
+__device__ __forceinline__ void fq_block_scan(uint64_t (&v)[N], uint64_t (&total)[N], uint64_t *lds)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint64_t inc[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) inc[i] = v[i];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const uint64_t t = __shfl_up(inc[i], d);
+            if (lane >= d) inc[i] += t;
+        }
+    }
+    if (lane == 63)
+#pragma unroll
+        for (int i = 0; i < N; ++i) lds[w * N + i] = inc[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        uint64_t base = 0, tot = 0;
+#pragma unroll
+        for (int ww = 0; ww < FQ_THREADS / 64; ++ww) {
+            const uint64_t x = lds[ww * N + i];
+            base += ww < w ? x : 0;
+            tot += x;
+        }
+        v[i] = base + inc[i] - v[i];
+        total[i] = tot;
+    }
+    __syncthreads();
+}
+
+// line ln of text i spans [start, end): its end goes to the slot of record ln / 4 (the name line's start too)
+__device__ __forceinline__ void fq_put_line(const fq_args &a, int i, uint64_t ln, uint64_t start, uint64_t end)
+{
+    const uint64_t r = ln >> 2;
+    if (r >= a.slots[i]) return; // only in a text with a malformed record below this one (sk_device.h)
+    uint64_t *d = a.desc[i] + 5 * r;
+    if ((ln & 3) == 0) d[0] = start;
+    d[1 + (ln & 3)] = end;
+}
+
+// read number -> (input, record of that input)
+__device__ __forceinline__ int fq_input_of(const fq_args &a, uint64_t read, uint64_t &rec)
+{
+    if (a.mode == SK_TRIM_PE_SPLIT) {
+        rec = read >> 1;
+        return (int)(read & 1);
+    }
+    rec = read;
+    return 0;
+}
+
+struct fq_rec {
+    const uint8_t *text;
+    uint64_t s0, e0, e1, e2, e3; // name start, line ends
+};
+
+__device__ __forceinline__ fq_rec fq_record(const fq_args &a, uint64_t read)
+{
+    uint64_t k;
+    const int i = fq_input_of(a, read, k);
+    const uint64_t *d = a.desc[i] + 5 * k;
+    return {a.text[i], d[0], d[1], d[2], d[3], d[4]};
+}
+
+// ------------------------------------------------------------------------------------------
+// 1 frame: count
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_count_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[8];
+    const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
+    const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15;
+    uint64_t cnt = 0, last = 0; // last: position + 1 of the lane's last '\n', 0 = none
+    for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
+        const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
+        const uint32_t m = fq_nl_mask(a, i, q);
+        cnt += __builtin_popcount(m);
+        if (m) last = q + (31 - __builtin_clz(m)) - sh + 1;
+    }
+    uint64_t s_ex, m_ex, s_tot, m_tot;
+    fq_scan2(cnt, last, s_ex, m_ex, s_tot, m_tot, lds);
+    if (threadIdx.x == 0) {
+        a.chunks[2 * blockIdx.x] = s_tot;
+        a.chunks[2 * blockIdx.x + 1] = m_tot;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 2 frame: scan of the chunk table (one workgroup), the unterminated last line, totals
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_scan_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[8];
+    uint64_t lines[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) {
+        const uint64_t nc = a.n_chunks[i];
+        uint64_t *tab = a.chunks + 2 * (i ? a.n_chunks[0] : 0);
+        const uint64_t per = (nc + FQ_THREADS - 1) / FQ_THREADS, c0 = min(nc, per * threadIdx.x), c1 = min(nc, c0 + per);
+        uint64_t s = 0, m = 0;
+        for (uint64_t c = c0; c < c1; ++c) {
+            s += tab[2 * c];
+            m = max(m, tab[2 * c + 1]);
+        }
+        uint64_t s_ex, m_ex, s_tot, m_tot;
+        fq_scan2(s, m, s_ex, m_ex, s_tot, m_tot, lds);
+        for (uint64_t c = c0; c < c1; ++c) {
+            const uint64_t x = tab[2 * c], y = tab[2 * c + 1];
+            tab[2 * c] = s_ex;
+            tab[2 * c + 1] = m_ex;
+            s_ex += x;
+            m_ex = max(m_ex, y);
+        }
+        lines[i] = s_tot;
+        // a last line without '\n' ends at the end of the text
+        if (threadIdx.x == 0 && a.bytes[i] && a.text[i][a.bytes[i] - 1] != '\n') {
+            fq_put_line(a, i, s_tot, m_tot, a.bytes[i]);
+            lines[i] += 1;
+        }
+        __syncthreads(); // lds reuse
+    }
+    if (threadIdx.x == 0) {
+        uint64_t *h = a.hdr;
+        const uint64_t r0 = lines[0] >> 2, r1 = lines[1] >> 2;
+        h[SK_FQ_H_LINES] = lines[0];
+        h[SK_FQ_H_LINES + 1] = lines[1];
+        h[SK_FQ_H_RECORDS] = r0;
+        h[SK_FQ_H_RECORDS + 1] = r1;
+        uint64_t fmt = ~0ull, real;
+        if (a.mode == SK_TRIM_PE_SPLIT) {
+            // the first record without a mate: the CLI's "Batch2 and Batch1 have different lengths"
+            if (r0 != r1) fmt = ((r0 < r1 ? 2 * r0 + 1 : 2 * r1) << 3) | SK_FQ_PAIR_COUNT;
+            real = 2 * min(r0, r1);
+        } else {
+            real = a.mode == SK_TRIM_PE_INTERLEAVED ? (r0 & ~1ull) : r0;
+        }
+        h[SK_FQ_H_FMT] = fmt;
+        h[SK_FQ_H_MODE] = (uint64_t)a.mode;
+        h[SK_FQ_H_NREAL] = min(real, a.n_pack); // more only in a text with a malformed record (sk_device.h)
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 3 frame: every line's end into its record's slot
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_lines_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[8];
+    const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
+    const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15;
+    uint64_t ln0 = a.chunks[2 * blockIdx.x], prev = a.chunks[2 * blockIdx.x + 1]; // prev: start of the chunk's first line
+    for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
+        const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
+        uint32_t m = fq_nl_mask(a, i, q);
+        const uint64_t last = m ? q + (31 - __builtin_clz(m)) - sh + 1 : 0;
+        uint64_t s_ex, m_ex, s_tot, m_tot;
+        fq_scan2(__builtin_popcount(m), last, s_ex, m_ex, s_tot, m_tot, lds);
+        uint64_t ln = ln0 + s_ex, start = max(prev, m_ex);
+        while (m) {
+            const int b = __builtin_ctz(m);
+            m &= m - 1;
+            const uint64_t p = q + b - sh;
+            fq_put_line(a, i, ln, start, p);
+            ++ln;
+            start = p + 1;
+        }
+        ln0 += s_tot;
+        prev = max(prev, m_tot);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 4 check: reference src/FQEntry.cpp:53-97, in its order; the first failing check of a record is its lowest reason
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_check_kernel(fq_args a)
+{
+    const uint64_t *h = a.hdr;
+    const uint64_t n0 = min(h[SK_FQ_H_RECORDS], a.slots[0]), n1 = min(h[SK_FQ_H_RECORDS + 1], a.slots[1]);
+    uint64_t best = ~0ull;
+    for (uint64_t g = (uint64_t)blockIdx.x * FQ_THREADS + threadIdx.x; g < n0 + n1; g += (uint64_t)gridDim.x * FQ_THREADS) {
+        const int i = g < n0 ? 0 : 1;
+        const uint64_t r = g - (i ? n0 : 0);
+        const uint64_t *d = a.desc[i] + 5 * r;
+        const uint64_t s0 = d[0], e0 = d[1], e1 = d[2], e2 = d[3], e3 = d[4];
+        const uint64_t name = e0 - s0, seq = e1 - e0 - 1, qual = e3 - e2 - 1;
+        uint64_t why = SK_FQ_OK;
+        if (name <= 1) why = SK_FQ_ID_SHORT;
+        else if (a.text[i][s0] != '@') why = SK_FQ_ID_NO_AT;
+        else if (seq == 0) why = SK_FQ_SEQ_EMPTY;
+        else if (qual == 0) why = SK_FQ_QUAL_EMPTY;
+        else if (qual != seq) why = SK_FQ_LENGTHS;
+        else if (qual > SK_MAX_READ_LEN_DEV) why = SK_FQ_TOO_LONG;
+        if (why != SK_FQ_OK) {
+            const uint64_t read = a.mode == SK_TRIM_PE_SPLIT ? 2 * r + i : r;
+            best = min(best, (read << 3) | why);
+        }
+    }
+    if (best != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.hdr + SK_FQ_H_FMT), (unsigned long long)best);
+}
+
+// ------------------------------------------------------------------------------------------
+// 5-7 pack: the packed batch's offsets
+// ------------------------------------------------------------------------------------------
+// qual length of packed read r (0 beyond the framed records and for every read of a malformed text)
+__device__ __forceinline__ uint64_t fq_pack_len(const fq_args &a, uint64_t r, uint64_t n_real, bool bad)
+{
+    if (bad || r >= n_real) return 0;
+    const fq_rec x = fq_record(a, r);
+    return x.e3 - x.e2 - 1;
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_count_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4];
+    const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    uint64_t v[1] = {0}, tot[1];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) v[0] += fq_pack_len(a, first + j, n_real, bad);
+    fq_block_scan<1>(v, tot, lds);
+    if (threadIdx.x == 0) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS] = tot[0];
+}
+
+// one workgroup: the block table's first `nv` words -> exclusive bases in place; the totals
+template <int N>
+__device__ __forceinline__ void fq_scan_blocks(const fq_args &a, uint64_t (&run)[N], uint64_t *lds)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) run[i] = 0;
+    for (uint64_t b0 = 0; b0 < a.n_blocks; b0 += FQ_THREADS) {
+        const uint64_t b = b0 + threadIdx.x;
+        uint64_t v[N], tot[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = b < a.n_blocks ? a.blk[b * SK_FQ_BLOCK_WORDS + i] : 0;
+        fq_block_scan<N>(v, tot, lds);
+        if (b < a.n_blocks)
+#pragma unroll
+            for (int i = 0; i < N; ++i) a.blk[b * SK_FQ_BLOCK_WORDS + i] = run[i] + v[i];
+#pragma unroll
+        for (int i = 0; i < N; ++i) run[i] += tot[i];
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_scan_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4];
+    uint64_t run[1];
+    fq_scan_blocks<1>(a, run, lds);
+    if (threadIdx.x == 0) {
+        a.hdr[SK_FQ_H_PACKED] = run[0];
+        a.offsets[a.n_pack] = run[0];
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_place_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4];
+    const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    uint64_t len[FQ_PER_THREAD];
+    uint64_t v[1] = {0}, tot[1];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        len[j] = fq_pack_len(a, first + j, n_real, bad);
+        v[0] += len[j];
+    }
+    fq_block_scan<1>(v, tot, lds);
+    uint64_t b = v[0] + a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        if (first + j < a.n_pack) a.offsets[first + j] = b;
+        b += len[j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 9-11 emit: the pair rule over the cuts
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int fq_dest(int mode, bool kept, bool mate_kept, bool second)
+{
+    if (!kept) return -1;
+    if (mode == SK_TRIM_SE) return 0;
+    if (!mate_kept) return 2;
+    return (mode == SK_TRIM_PE_SPLIT && second) ? 1 : 0;
+}
+
+struct fq_emit_read {
+    int dest;
+    uint64_t bytes;
+};
+
+// the FQ_PER_THREAD reads of this lane (first even): destination and bytes of the emitted record
+__device__ __forceinline__ void fq_emit_load(const fq_args &a, uint64_t first, uint64_t n_real, bool bad,
+                                             fq_emit_read (&rd)[FQ_PER_THREAD])
+{
+    bool kept[FQ_PER_THREAD];
+    sk_cut_dev c[FQ_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        const uint64_t r = first + j;
+        c[j] = {-1, -1};
+        if (!bad && r < n_real) c[j] = a.cuts[r];
+        kept[j] = c[j].three >= 0; // src/trim_single.cpp:368, src/trim_paired.cpp:500,502
+    }
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        rd[j].dest = fq_dest(a.mode, kept[j], kept[j ^ 1], j & 1);
+        rd[j].bytes = 0;
+        if (rd[j].dest >= 0) {
+            const fq_rec x = fq_record(a, first + j);
+            rd[j].bytes = (x.e0 - x.s0 + 1) + (x.e2 - x.e1) + 2 * (uint64_t)(c[j].three - c[j].five + 1);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_count_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4 * 6];
+    const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    fq_emit_read rd[FQ_PER_THREAD];
+    fq_emit_load(a, first, n_real, bad, rd);
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int o = 0; o < 3; ++o)
+            if (rd[j].dest == o) {
+                v[o] += 1;
+                v[3 + o] += rd[j].bytes;
+            }
+    fq_block_scan<6>(v, tot, lds);
+    if (threadIdx.x < 6) {
+        uint64_t x = 0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x = threadIdx.x == k ? tot[k] : x; // no runtime index into tot[]
+        a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS + threadIdx.x] = x;
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_scan_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4 * 6];
+    uint64_t run[6];
+    fq_scan_blocks<6>(a, run, lds);
+    if (threadIdx.x < 3) {
+        const int o = threadIdx.x;
+        const fq_out &out = a.out[o];
+        const unsigned long long range = *a.errword;
+        const bool ok = a.hdr[SK_FQ_H_FMT] == ~0ull && range == ~0ull;
+        const uint64_t recs = o == 0 ? run[0] : o == 1 ? run[1] : run[2], bytes = o == 0 ? run[3] : o == 1 ? run[4] : run[5];
+        const bool produced = out.text != nullptr;
+        const bool fit = produced && ok && bytes <= out.cap && (!out.index || recs <= out.rec_cap);
+        a.hdr[SK_FQ_H_OUT_RECORDS + o] = recs;
+        a.hdr[SK_FQ_H_OUT_BYTES + o] = bytes;
+        a.hdr[SK_FQ_H_PRODUCED + o] = produced;
+        a.hdr[SK_FQ_H_FIT + o] = fit;
+        if (o == 0) a.hdr[SK_FQ_H_RANGE] = range;
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_place_kernel(fq_args a)
+{
+    __shared__ uint64_t lds[4 * 6];
+    const uint64_t *h = a.hdr;
+    const bool fit[3] = {h[SK_FQ_H_FIT] != 0, h[SK_FQ_H_FIT + 1] != 0, h[SK_FQ_H_FIT + 2] != 0};
+    if (!fit[0] && !fit[1] && !fit[2]) return; // uniform
+    const uint64_t n_real = h[SK_FQ_H_NREAL];
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    fq_emit_read rd[FQ_PER_THREAD];
+    fq_emit_load(a, first, n_real, false, rd);
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int o = 0; o < 3; ++o)
+            if (rd[j].dest == o) {
+                v[o] += 1;
+                v[3 + o] += rd[j].bytes;
+            }
+    fq_block_scan<6>(v, tot, lds);
+    const uint64_t *blk = a.blk + blockIdx.x * SK_FQ_BLOCK_WORDS;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] += blk[k];
+    const uint64_t dbase[3] = {0, h[SK_FQ_H_OUT_RECORDS], h[SK_FQ_H_OUT_RECORDS] + h[SK_FQ_H_OUT_RECORDS + 1]};
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int o = 0; o < 3; ++o)
+            if (rd[j].dest == o) {
+                const uint64_t k = v[o], b = v[3 + o];
+                v[o] += 1;
+                v[3 + o] += rd[j].bytes;
+                if (!fit[o]) continue;
+                a.emit[2 * (dbase[o] + k)] = b;
+                a.emit[2 * (dbase[o] + k) + 1] = first + j;
+                if (a.out[o].index) a.out[o].index[k] = first + j;
+            }
+}
+
+// ------------------------------------------------------------------------------------------
+// 8, 12 gathers
+// ------------------------------------------------------------------------------------------
+// the n (1..16) bytes at p as the first bytes of a granule, from aligned 16-byte loads only (== load_window of
+// sk_trim.hip): both blocks touched hold a byte of [p, p + n)
+__device__ __forceinline__ fq_u4 fq_load_window(const uint8_t *p, int n)
+{
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
+    const fq_u4 *blk = reinterpret_cast<const fq_u4 *>(ad & ~(uintptr_t)15);
+    const int sh = (int)(ad & 15);
+    const fq_u4 lo = blk[0];
+    if (sh == 0) return lo;
+    const fq_u4 hi = sh + n > 16 ? blk[1] : lo;
+    const int s4 = sh >> 2, sb = sh & 3;
+    const uint32_t x0 = lo.x, x1 = lo.y, x2 = lo.z, x3 = lo.w, x4 = hi.x, x5 = hi.y, x6 = hi.z, x7 = hi.w;
+    const uint32_t y0 = s4 == 0 ? x0 : s4 == 1 ? x1 : s4 == 2 ? x2 : x3;
+    const uint32_t y1 = s4 == 0 ? x1 : s4 == 1 ? x2 : s4 == 2 ? x3 : x4;
+    const uint32_t y2 = s4 == 0 ? x2 : s4 == 1 ? x3 : s4 == 2 ? x4 : x5;
+    const uint32_t y3 = s4 == 0 ? x3 : s4 == 1 ? x4 : s4 == 2 ? x5 : x6;
+    const uint32_t y4 = s4 == 0 ? x4 : s4 == 1 ? x5 : s4 == 2 ? x6 : x7;
+    fq_u4 r;
+    r.x = __builtin_amdgcn_alignbyte(y1, y0, sb);
+    r.y = __builtin_amdgcn_alignbyte(y2, y1, sb);
+    r.z = __builtin_amdgcn_alignbyte(y3, y2, sb);
+    r.w = __builtin_amdgcn_alignbyte(y4, y3, sb);
+    return r;
+}
+
+__device__ __forceinline__ fq_u128 fq_to_u128(fq_u4 v)
+{
+    return (fq_u128)v.x | ((fq_u128)v.y << 32) | ((fq_u128)v.z << 64) | ((fq_u128)v.w << 96);
+}
+
+__device__ __forceinline__ fq_u4 fq_from_u128(fq_u128 v)
+{
+    fq_u4 r;
+    r.x = (uint32_t)v;
+    r.y = (uint32_t)(v >> 32);
+    r.z = (uint32_t)(v >> 64);
+    r.w = (uint32_t)(v >> 96);
+    return r;
+}
+
+// bytes [0, n) of x to bytes [d, d + n) of acc (d + n <= 16)
+__device__ __forceinline__ void fq_place(fq_u128 &acc, fq_u128 x, int d, int n)
+{
+    const fq_u128 m = n >= 16 ? ~(fq_u128)0 : (((fq_u128)1 << (8 * n)) - 1);
+    acc |= (x & m) << (8 * d);
+}
+
+__device__ __forceinline__ void fq_store_granule(uint8_t *dst, uint64_t g, fq_u128 x, int n)
+{
+    if (n == 16) {
+        __builtin_nontemporal_store(fq_from_u128(x), reinterpret_cast<fq_u4 *>(dst + g));
+    } else {
+        for (int i = 0; i < n; ++i) dst[g + i] = (uint8_t)(x >> (8 * i));
+    }
+}
+
+// one piece of a record: bytes [0, len) at src, or a '\n' (src == nullptr, len 1)
+struct fq_piece {
+    const uint8_t *src;
+    uint64_t len;
+};
+
+// bytes [rel, rel + n) of a record made of np pieces to bytes [d, d + n) of acc
+template <int NP>
+__device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, int d, int n, fq_u128 &acc)
+{
+    uint64_t ps = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint64_t pe = ps + pc[j].len;
+        if (n > 0 && rel < pe && rel >= ps) {
+            const int t = (int)min((uint64_t)n, pe - rel);
+            if (pc[j].src)
+                fq_place(acc, fq_to_u128(fq_load_window(pc[j].src + (rel - ps), t)), d, t);
+            else
+                fq_place(acc, (fq_u128)'\n', d, 1);
+            rel += t;
+            d += t;
+            n -= t;
+        }
+        ps = pe;
+    }
+}
+
+// kind 0: packed qual, 1: packed seq, 2..4: emitted output kind - 2
+struct fq_job {
+    uint8_t *dst;
+    uint64_t total, R;
+    const uint64_t *off; // record k starts at off[k * ostride]
+    uint32_t ostride;
+    int kind;
+};
+
+// bytes [rel, rel + n) of record k of the job to bytes [d, d + n) of acc
+__device__ __forceinline__ void fq_record_bytes(const fq_args &a, const fq_job &j, uint64_t k, uint64_t rel, int d, int n,
+                                                fq_u128 &acc)
+{
+    if (j.kind < 2) {
+        const fq_rec x = fq_record(a, k);
+        const fq_piece pc[1] = {{x.text + (j.kind == 0 ? x.e2 : x.e0) + 1, x.e3 - x.e2 - 1}};
+        fq_fill<1>(pc, rel, d, n, acc);
+        return;
+    }
+    const uint64_t read = j.off[k * 2 + 1];
+    const fq_rec x = fq_record(a, read);
+    const sk_cut_dev c = a.cuts[read];
+    const uint64_t m = (uint64_t)(c.three - c.five);
+    const fq_piece pc[6] = {{x.text + x.s0, x.e0 - x.s0 + 1}, {x.text + x.e0 + 1 + c.five, m}, {nullptr, 1},
+                            {x.text + x.e1 + 1, x.e2 - x.e1}, {x.text + x.e2 + 1 + c.five, m}, {nullptr, 1}};
+    fq_fill<6>(pc, rel, d, n, acc);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int emit)
+{
+    __shared__ uint64_t s_off[FQ_WIN + 1];
+    __shared__ uint64_t s_cur;
+    const int t = threadIdx.x, lane = t & 63;
+    const uint64_t *h = a.hdr;
+    const int n_jobs = emit ? 3 : (a.trunc_n ? 2 : 1);
+    uint64_t dbase = 0;
+    for (int jb = 0; jb < n_jobs; ++jb) {
+        fq_job j;
+        if (emit) {
+            const uint64_t R = h[SK_FQ_H_OUT_RECORDS + jb];
+            j = {a.out[jb].text, h[SK_FQ_H_OUT_BYTES + jb], R, a.emit + 2 * dbase, 2, 2 + jb};
+            dbase += R;
+            if (!h[SK_FQ_H_FIT + jb]) continue; // uniform
+        } else {
+            j = {jb ? a.ps : a.pq, h[SK_FQ_H_PACKED], a.n_pack, a.offsets, 1, jb};
+        }
+        if (j.total == 0) continue;
+        const uint64_t n_chunks = (j.total + FQ_GCHUNK - 1) / FQ_GCHUNK;
+        const uint64_t per = (n_chunks + gridDim.x - 1) / gridDim.x;
+        const uint64_t c0 = (uint64_t)blockIdx.x * per, c1 = min(c0 + per, n_chunks);
+        if (c0 >= c1) continue;
+        // offset of record k (k <= R; off(R) = total)
+        auto off = [&](uint64_t k) { return k < j.R ? j.off[k * j.ostride] : j.total; };
+        // the record holding the span's first byte: a 64-ary search by wave 0 (the last k < R with off(k) <= x)
+        if (t < 64) {
+            const uint64_t x = c0 * FQ_GCHUNK;
+            uint64_t lo = 0, hi = j.R;
+            while (hi - lo > 1) {
+                const uint64_t step = (hi - lo + 63) / 64, p = lo + lane * step;
+                const uint64_t mk = __builtin_amdgcn_ballot_w64(p < hi && off(p) <= x); // lane 0's probe always holds
+                lo += (uint64_t)(63 - __builtin_clzll(mk)) * step;
+                hi = min(hi, lo + step);
+            }
+            if (t == 0) s_cur = lo;
+        }
+        __syncthreads();
+        uint64_t cur = s_cur;
+        for (uint64_t c = c0; c < c1; ++c) {
+            if (t <= FQ_WIN) s_off[t] = cur + t <= j.R ? off(cur + t) : ~0ull;
+            __syncthreads();
+            const uint64_t win_end = s_off[FQ_WIN];
+            uint64_t k_last = cur;
+#pragma unroll
+            for (int u = 0; u < FQ_GPL; ++u) {
+                const uint64_t g = c * FQ_GCHUNK + (uint64_t)u * (FQ_THREADS * 16) + 16u * t;
+                if (g >= j.total) break;
+                uint64_t k;
+                if (g < win_end) {
+                    int lo = 0, hi = FQ_WIN; // s_off[lo] <= g < s_off[hi]
+                    while (hi - lo > 1) {
+                        const int mid = (lo + hi) >> 1;
+                        if (s_off[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    k = cur + lo;
+                } else {
+                    uint64_t lo = cur + FQ_WIN, hi = j.R; // off(lo) <= g < off(hi)
+                    while (hi - lo > 1) {
+                        const uint64_t mid = lo + ((hi - lo) >> 1);
+                        if (off(mid) <= g) lo = mid; else hi = mid;
+                    }
+                    k = lo;
+                }
+                k_last = k;
+                const uint64_t end = min(g + 16, j.total);
+                fq_u128 acc = 0;
+                uint64_t pos = g;
+                while (pos < end) {
+                    const uint64_t i = k - cur;
+                    const uint64_t b = i < FQ_WIN ? s_off[i] : off(k);
+                    const uint64_t e = i < FQ_WIN ? s_off[i + 1] : off(k + 1);
+                    if (e <= pos) { // the record ended (or is empty)
+                        ++k;
+                        continue;
+                    }
+                    const uint64_t pe = min(e, end);
+                    fq_record_bytes(a, j, k, pos - b, (int)(pos - g), (int)(pe - pos), acc);
+                    pos = pe;
+                }
+                fq_store_granule(j.dst, g, acc, (int)(end - g));
+            }
+            // the next chunk starts at or after the record of the last lane's last granule
+            if (t == FQ_THREADS - 1) s_cur = k_last;
+            __syncthreads();
+            cur = s_cur;
+        }
+        __syncthreads(); // s_cur / s_off are reused by the next job
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
+{
+    if (!bytes) return 0;
+    const uint64_t span = (reinterpret_cast<uintptr_t>(text) & 15) + bytes;
+    return (span + SK_FQ_CHUNK_BYTES - 1) / SK_FQ_CHUNK_BYTES;
+}
+
+void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fastq_output *out, void *workspace,
+                  const unsigned long long *errword, fq_args &a)
+{
+    sk_fq_layout L;
+    sk_fq_layout_of(in->bytes[0] + (mode == SK_TRIM_PE_SPLIT ? in->bytes[1] : 0), trunc_n, &L);
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    const int n_in = mode == SK_TRIM_PE_SPLIT ? 2 : 1;
+    for (int i = 0; i < 2; ++i) {
+        a.text[i] = i < n_in ? in->text[i] : nullptr;
+        a.bytes[i] = i < n_in ? in->bytes[i] : 0;
+        a.n_chunks[i] = fq_chunks_of(a.text[i], a.bytes[i]);
+        a.slots[i] = i < n_in ? sk_fq_slots(a.bytes[i]) : 0;
+    }
+    a.mode = mode;
+    a.trunc_n = trunc_n ? 1 : 0;
+    a.n_pack = sk_fq_pack_reads(a.bytes[0], a.bytes[1], mode);
+    a.n_blocks = (a.n_pack + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
+    a.hdr = reinterpret_cast<uint64_t *>(ws);
+    a.chunks = reinterpret_cast<uint64_t *>(ws + L.chunks);
+    a.desc[0] = reinterpret_cast<uint64_t *>(ws + L.desc);
+    a.desc[1] = a.desc[0] + 5 * a.slots[0];
+    a.offsets = reinterpret_cast<uint64_t *>(ws + L.offsets);
+    a.cuts = reinterpret_cast<sk_cut_dev *>(ws + L.cuts);
+    a.blk = reinterpret_cast<uint64_t *>(ws + L.blocks);
+    a.emit = reinterpret_cast<uint64_t *>(ws + L.emit);
+    a.pq = ws + L.qual;
+    a.ps = trunc_n ? ws + L.seq : nullptr;
+    a.errword = errword;
+    for (int o = 0; o < 3; ++o) {
+        const bool used = o == 0 || (mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2);
+        a.out[o] = used && out ? fq_out{out[o].text, out[o].capacity, out[o].record_index, out[o].record_capacity} : fq_out{};
+    }
+}
+
+} // namespace
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                  void *workspace, int cu_count, hipStream_t stream,
+                                                                                  sk_batch *packed, sk_cut_dev **cuts)
+{
+    fq_args a;
+    fq_make_args(in, mode, trunc_n, nullptr, workspace, nullptr, a);
+    const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
+    if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
+    if (nc) hipLaunchKernelGGL(sk_fq_frame_lines_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_pack_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 0);
+    *packed = sk_batch{};
+    packed->qual = a.pq;
+    packed->seq = a.ps;
+    packed->offsets = a.offsets;
+    packed->stride = in->max_read_len;
+    packed->n_reads = a.n_pack;
+    *cuts = a.cuts;
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                 const sk_fastq_output *out, void *workspace,
+                                                                                 const unsigned long long *errword, int cu_count,
+                                                                                 hipStream_t stream)
+{
+    fq_args a;
+    fq_make_args(in, mode, trunc_n, out, workspace, errword, a);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_emit_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
+    return hipGetLastError();
+}
