@@ -399,6 +399,67 @@ void *sk_bgzf_host_alloc(size_t bytes);
 void sk_bgzf_host_free(void *p);
 const char *sk_bgzf_last_error(void);
 
+/*
+ * BGZF on the device: text in device memory -> a complete BGZF byte image in device memory, a valid .gz file as it
+ * stands.  Stream-ordered, so it chains behind sk_trim_fastq_device_async without a host wait in between.
+ *
+ * Blocks: block b is text bytes [65280 b, min(65280 (b + 1), n)), n the text's actual length: in->bytes, or *in->bytes_dev
+ * (read on the stream, must be <= in->bytes; a larger value is taken as in->bytes) when that is given; with valid_dev given
+ * and *valid_dev == 0 the text counts as empty.  The launches are sized by in->bytes; blocks past n produce nothing, and
+ * n == 0 gives no data block.
+ * Each data block becomes one gzip member: the 18-byte BGZF header (1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00, then
+ * BSIZE = member size - 1, 16 bit LE), the body, then CRC-32 and ISIZE of the block's text (LE).  The body is the deflate
+ * stream sk_bgzf_deflate writes for that block, or a stored block (01 LEN NLEN + text) iff that stream does not fit its
+ * 64 KiB slot or has text + 5 bytes or more: the rule of the CLI's -g writer.  Members lie back to back from out[0]; with
+ * SK_BGZF_EOF the standard 28-byte empty member (1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00
+ * 00 00 00) follows.
+ * `out` is 16-byte aligned.  If the image exceeds `capacity`, NOTHING is written to out and finish returns SK_ESPACE with
+ * bytes_out = the need.  sk_bgzf_bound(bytes, flags) = bytes + 31 ceil(bytes / 65280) + (SK_BGZF_EOF ? 28 : 0) always
+ * suffices (a stored member is its text + 5 + 26 bytes).
+ *
+ * sk_bgzf_device_async only enqueues three kernels on hip_stream: no allocation, no copy, no synchronisation, no lock.  All
+ * scratch and the counts live in `workspace` (device, 16-byte aligned).  With NB = ceil(text_bytes / 65280):
+ *   sk_bgzf_workspace_bytes(text_bytes) = 128 + 16 NB + 261152 min(NB, 1280) + 65536 NB
+ * (header; table; one token per text byte for each of at most 1280 blocks in flight -- a fixed grid, not the device's CU
+ * count, so the size needs no device; a 64 KiB deflate slot per block), i.e. about the text's size plus at most 334 MB.
+ * sk_bgzf_device_finish is the only call that waits.  Two calls in flight need two workspaces.  Bad arguments (NULL ctx or
+ * in, unknown flags, text NULL with bytes != 0, out NULL with capacity != 0, out or workspace not 16-byte aligned, bytes_dev
+ * or valid_dev not 8-byte aligned, a short workspace) return SK_EINVAL and enqueue nothing.
+ */
+enum { SK_BGZF_EOF = 1 }; /* flags: close the image with the 28-byte empty end-of-file member */
+
+typedef struct {
+    const uint8_t *text;       /* device, ANY alignment */
+    uint64_t bytes;            /* the text's length, or an upper bound on it when bytes_dev is given */
+    const uint64_t *bytes_dev; /* device, 8-byte aligned, or NULL: the length, read on the stream; must be <= bytes */
+    const uint64_t *valid_dev; /* device, 8-byte aligned, or NULL: if given and *valid_dev == 0 the text counts as empty */
+} sk_bgzf_input;
+
+typedef struct {
+    uint64_t bytes_in, blocks, stored_blocks; /* data blocks; the EOF member is not counted */
+    uint64_t bytes_out;                       /* what the image needs, also when it did not fit */
+} sk_bgzf_counts;
+
+uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags); /* worst-case image size; pure, no device */
+size_t sk_bgzf_workspace_bytes(uint64_t text_bytes);    /* pure, no device */
+int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uint64_t capacity, int flags, void *workspace,
+                         size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts from the workspace: SK_OK, or SK_ESPACE (the image is beyond the capacity). */
+int sk_bgzf_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_counts *counts);
+
+/*
+ * The device words of output `output` (0..2) inside the workspace of a sk_trim_fastq_device_async call, as its kernels write
+ * them on the stream: *bytes_dev = the output's byte count, *written_dev = 1 iff the output's text is in its buffer
+ * (produced, no format or range error, within its capacities), else 0.  Fed to sk_bgzf_input.bytes_dev / valid_dev (with
+ * bytes = the output buffer's capacity) they chain the two calls without a host wait; after an upstream error or an output
+ * that did not fit, the image is empty (the EOF member only): whatever the buffer held is never compressed.
+ * One-pass sizing: a trimmed text holds, per kept record, its name and '+' lines as they were and its seq and qual lines cut
+ * shorter or not at all (sk_fastq.hip's emission: name + 1, plus-line + 1, 2 * (three - five + 1) bytes), so it never
+ * exceeds its inputs by more than the one '\n' synthesized after an unterminated last line of each input text: an output
+ * buffer of bytes[0] + bytes[1] + 2 bytes always fits.
+ */
+int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t **bytes_dev, const uint64_t **written_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,10 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_kernel_for", "sk_kernel_name", "sk_seg_classes", "sk_probe_read_bandwidth",
            "sk_count_pairs_device_async", "sk_count_pairs_device_finish", "sk_bgzf_deflate", "sk_bgzf_host_alloc", "sk_bgzf_host_free",
            "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish",
-           "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish")
+           "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish",
+           "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_device_async",
+           "sk_bgzf_device_finish")
+SK_BGZF_EOF = 1
 
 
 class Params(C.Structure):
@@ -99,6 +102,18 @@ class FastqCounts(C.Structure):
                 "bytes": list(self.bytes), "format_error": int(self.format_error),
                 "format_input": int(self.format_input), "format_record": int(self.format_record),
                 "range": (int(self.range.read), int(self.range.pos), int(self.range.ch))}
+
+
+class BgzfInput(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("bytes", C.c_uint64), ("bytes_dev", C.c_void_p), ("valid_dev", C.c_void_p)]
+
+
+class BgzfCounts(C.Structure):
+    _fields_ = [("bytes_in", C.c_uint64), ("blocks", C.c_uint64), ("stored_blocks", C.c_uint64), ("bytes_out", C.c_uint64)]
+
+    def as_dict(self):
+        return {"bytes_in": int(self.bytes_in), "blocks": int(self.blocks), "stored_blocks": int(self.stored_blocks),
+                "bytes_out": int(self.bytes_out)}
 
 
 class SickleError(RuntimeError):
@@ -204,6 +219,17 @@ def lib():
                                                  C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
         L.sk_trim_fastq_device_finish.restype = C.c_int
         L.sk_trim_fastq_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts)]
+        L.sk_trim_fastq_output_words.restype = C.c_int
+        L.sk_trim_fastq_output_words.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.sk_bgzf_bound.restype = C.c_uint64
+        L.sk_bgzf_bound.argtypes = [C.c_uint64, C.c_int]
+        L.sk_bgzf_workspace_bytes.restype = C.c_size_t
+        L.sk_bgzf_workspace_bytes.argtypes = [C.c_uint64]
+        L.sk_bgzf_device_async.restype = C.c_int
+        L.sk_bgzf_device_async.argtypes = [C.c_void_p, C.POINTER(BgzfInput), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]
+        L.sk_bgzf_device_finish.restype = C.c_int
+        L.sk_bgzf_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BgzfCounts)]
         _lib = L
     return _lib
 
@@ -434,6 +460,77 @@ class Context:
             R, B = counts["records"][o], counts["bytes"][o]
             res[o] = (t[:B], idx[:R]) if record_index else t[:B]
         return tuple(res), counts
+
+    # ---- BGZF on the device -------------------------------------------------------------------
+    def bgzf_device_async(self, text_ptr, text_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, eof=True,
+                          bytes_dev_ptr=None, valid_dev_ptr=None, stream=None):
+        """sk_bgzf_device_async on raw device pointers: text_bytes is the text's length, or with bytes_dev_ptr its bound."""
+        inp = BgzfInput(text_ptr, text_bytes, bytes_dev_ptr, valid_dev_ptr)
+        self._check(lib().sk_bgzf_device_async(self._h, C.byref(inp), out_ptr, capacity, SK_BGZF_EOF if eof else 0,
+                                               workspace_ptr, workspace_bytes, stream))
+
+    def bgzf_device_finish(self, workspace_ptr, stream=None):
+        """sk_bgzf_device_finish -> counts (dict); raises TrimError (with .counts) on SK_ESPACE."""
+        c = BgzfCounts()
+        rc = lib().sk_bgzf_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc == SK_ESPACE:
+            raise TrimError("bgzf failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc)
+        return c.as_dict()
+
+    def bgzf(self, text, eof=True):
+        """Text in device memory (a uint8 torch tensor) -> its BGZF image (a uint8 tensor, a valid .gz file as it stands),
+        on the current stream."""
+        import torch
+        dev, n = text.device, text.numel()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cap = lib().sk_bgzf_bound(n, SK_BGZF_EOF if eof else 0)
+        ws_bytes = lib().sk_bgzf_workspace_bytes(n)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        self.bgzf_device_async(text.data_ptr() if n else None, n, out.data_ptr(), cap, ws.data_ptr(), ws_bytes, eof=eof,
+                               stream=stream)
+        return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
+
+    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0):
+        """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
+        the current stream: the outputs are sized by the inputs (a trimmed text never exceeds them by more than one
+        newline each), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
+        only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises."""
+        import torch
+        dev = text.device
+        texts = [text] if text2 is None else [text, text2]
+        ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        cap = sum(sizes) + 2
+        bound, zws_bytes = lib().sk_bgzf_bound(cap, SK_BGZF_EOF), lib().sk_bgzf_workspace_bytes(cap)
+        outs, trimmed, images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
+        for o in used:
+            trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+            outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
+        self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                     max_read_len=max_read_len, stream=stream)
+        for o in used:
+            images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
+            zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
+            nbytes, written = self.trim_fastq_output_words(ws.data_ptr(), o)
+            self.bgzf_device_async(trimmed[o].data_ptr(), cap, images[o].data_ptr(), bound, zws[o].data_ptr(), zws_bytes,
+                                   eof=True, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream)
+        sizes_out = [None if images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
+                     for o in range(3)]
+        counts = self.trim_fastq_device_finish(ws.data_ptr(), stream)
+        return tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3)), counts
+
+    @staticmethod
+    def trim_fastq_output_words(fastq_workspace_ptr, output):
+        """sk_trim_fastq_output_words -> (bytes_dev, written_dev) device addresses of a trim's output `output`."""
+        b, w = C.c_void_p(), C.c_void_p()
+        if lib().sk_trim_fastq_output_words(fastq_workspace_ptr, output, C.byref(b), C.byref(w)) != SK_OK:
+            raise SickleError("sk_trim_fastq_output_words: bad arguments")
+        return b.value, w.value
 
 
 BGZF_INPUT = 65280   # bytes of text per BGZF block

@@ -850,6 +850,75 @@ int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, 
     return rc;
 }
 
+int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t **bytes_dev, const uint64_t **written_dev)
+{
+    if (!fastq_workspace || output < 0 || output > 2 || !bytes_dev || !written_dev) return SK_EINVAL;
+    const uint64_t *hdr = static_cast<const uint64_t *>(fastq_workspace);
+    *bytes_dev = hdr + SK_FQ_H_OUT_BYTES + output;
+    *written_dev = hdr + SK_FQ_H_FIT + output;
+    return SK_OK;
+}
+
+uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags)
+{
+    sk_bgzf_layout L;
+    sk_bgzf_layout_of(text_bytes, &L);
+    return text_bytes + SK_BGZF_MEMBER_EXTRA * L.n_blocks + ((flags & SK_BGZF_EOF) ? SK_BGZF_EOF_BYTES : 0);
+}
+
+size_t sk_bgzf_workspace_bytes(uint64_t text_bytes)
+{
+    sk_bgzf_layout L;
+    sk_bgzf_layout_of(text_bytes, &L);
+    return (size_t)L.total;
+}
+
+int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uint64_t capacity, int flags, void *workspace,
+                         size_t workspace_bytes, void *hip_stream)
+{
+#define SK_BGZF_BAD(...)              \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!in) SK_BGZF_BAD("sk_bgzf_device_async: in is required");
+    if (flags & ~SK_BGZF_EOF) SK_BGZF_BAD("bgzf: flags %d are unknown", flags);
+    if (!in->text && in->bytes) SK_BGZF_BAD("bgzf: text is NULL with %llu bytes", (unsigned long long)in->bytes);
+    if ((reinterpret_cast<uintptr_t>(in->bytes_dev) | reinterpret_cast<uintptr_t>(in->valid_dev)) & 7)
+        SK_BGZF_BAD("bgzf: bytes_dev and valid_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_BGZF_BAD("bgzf: out must be 16-byte aligned");
+    if (!out && capacity) SK_BGZF_BAD("bgzf: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+    if (in->bytes > (1ull << 60)) SK_BGZF_BAD("bgzf: %llu bytes of text is beyond what one call takes", (unsigned long long)in->bytes);
+    const size_t need = sk_bgzf_workspace_bytes(in->bytes);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
+        SK_BGZF_BAD("bgzf: workspace must be 16-byte aligned and hold sk_bgzf_workspace_bytes(%llu) = %zu bytes",
+                    (unsigned long long)in->bytes, need);
+#undef SK_BGZF_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_bgzf(in, out, capacity, flags, workspace, ctx->cu_count, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_bgzf_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[SK_BGZF_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    counts->bytes_in = h[SK_BGZF_H_BYTES_IN];
+    counts->blocks = h[SK_BGZF_H_BLOCKS];
+    counts->stored_blocks = h[SK_BGZF_H_STORED];
+    counts->bytes_out = h[SK_BGZF_H_BYTES_OUT];
+    if (!h[SK_BGZF_H_FIT]) {
+        set_error(ctx, "bgzf: the image needs %llu bytes, more than the capacity", (unsigned long long)counts->bytes_out);
+        return SK_ESPACE;
+    }
+    return SK_OK;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

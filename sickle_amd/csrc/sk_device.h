@@ -195,6 +195,45 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);
+// BGZF on the device (sk_bgzf.hip).  The caller's workspace (16-byte sections, sizes in bytes, NB = ceil(text bytes /
+// SK_BGZF_BLOCK) blocks, G = min(NB, SK_BGZF_GRID) workgroups of the block kernel):
+//   header    SK_BGZF_HDR_WORDS words
+//   table     16 per block: body bytes (bit 31: stored), CRC-32, the member's offset in the image
+//   tokens    4 * SK_BGZF_TOK_WORDS per workgroup of the block kernel: one token per text byte of the block in flight
+//   slots     65536 per block: its deflate stream
+// The grid is a constant, not the device's CU count: the size must not depend on a device (5 workgroups per CU by LDS on
+// the 256 CUs of an MI355X; on fewer CUs the surplus workgroups wait their turn).
+#define SK_BGZF_BLOCK 65280u
+#define SK_BGZF_SLOT 65536u
+#define SK_BGZF_GRID 1280u
+#define SK_BGZF_TOK_WORDS (SK_BGZF_BLOCK + 8u)
+#define SK_BGZF_MEMBER_EXTRA 31u // a stored member: 18 + 5 + 8 bytes beyond its text
+#define SK_BGZF_EOF_BYTES 28u
+#define SK_BGZF_HDR_WORDS 16u
+#define SK_BGZF_H_BYTES_IN 0
+#define SK_BGZF_H_BLOCKS 1
+#define SK_BGZF_H_STORED 2
+#define SK_BGZF_H_BYTES_OUT 3 // what the image needs
+#define SK_BGZF_H_FIT 4       // the image is within the capacity: the pack kernel writes it
+struct sk_bgzf_entry {
+    uint32_t body, crc;
+    uint64_t off;
+};
+struct sk_bgzf_layout {
+    uint64_t n_blocks, grid, table, tokens, slots, total;
+};
+static inline void sk_bgzf_layout_of(uint64_t text_bytes, sk_bgzf_layout *L)
+{
+    L->n_blocks = text_bytes / SK_BGZF_BLOCK + (text_bytes % SK_BGZF_BLOCK != 0);
+    L->grid = L->n_blocks < SK_BGZF_GRID ? L->n_blocks : SK_BGZF_GRID;
+    L->table = 8 * SK_BGZF_HDR_WORDS;
+    L->tokens = L->table + 16 * L->n_blocks;
+    L->slots = L->tokens + 4ull * SK_BGZF_TOK_WORDS * L->grid;
+    L->total = L->slots + (uint64_t)SK_BGZF_SLOT * L->n_blocks;
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf(const sk_bgzf_input *in, uint8_t *out, uint64_t capacity,
+                                                                           int flags, void *workspace, int cu_count,
+                                                                           hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
