@@ -85,3 +85,39 @@ def test_bound_and_workspace_need_no_device(tools, tmp_path):
     # bad arguments are refused before anything touches a device
     assert L.sk_bgzf_device_async(None, None, None, 0, 0, None, 0, None) == capi.SK_EINVAL
     assert L.sk_trim_fastq_output_words(None, 0, None, None) == capi.SK_EINVAL
+
+
+def test_codes_of_every_dynamic_header(tools, tmp_path):
+    """What inflating cannot show (zlib accepts some incomplete codes): in every deflated member of every encoder input no
+    literal/length or distance code is longer than 15 bits, no code-length code longer than 7, and all three codes are
+    complete (Kraft sum exactly 1).  tests/golden/bgzf_deep_code_length.txt (one block of FASTQ-like text with a third of
+    its bytes random, found by a search over the soak's generator) is an input on which skd_huffman's limiter has to
+    act on the code-length code: a Huffman tree over the header's own code-length symbol counts is 8 deep, the header
+    states 7 bits and a complete code.  And a block whose matches all have one distance: the distance code is the one
+    used symbol plus symbol 0."""
+    import numpy as np
+    import soak_bgzf
+    depth = {}
+    for name, data in _encoder_inputs().items():
+        soak_bgzf.members(sim_image(data, tmp_path, name), data, depth)
+    assert depth["literal/length"] == 15  # "fibonacci"
+    deep = open(os.path.join(cu.ROOT, "tests", "golden", "bgzf_deep_code_length.txt"), "rb").read()
+    assert len(deep) == BLOCK
+    one = {}
+    assert [m[0] for m in soak_bgzf.members(sim_image(deep, tmp_path, "deep"), deep, one)] == [False]
+    assert one["code-length"] == 7 and one["code-length, unlimited"] == 8
+    text = soak_bgzf.one_distance_text(np.random.default_rng(3), BLOCK)
+    image = sim_image(text, tmp_path, "one_distance")
+    assert soak_bgzf.members(image, text, {}) == [(False, len(image), BLOCK)] and len(image) < BLOCK // 20
+    assert soak_bgzf.one_far_distance(soak_bgzf.dynamic_header(image[18:-8])[1])
+
+
+def test_bgzf_host_soak(tools):
+    """tests/soak_bgzf.py run_host: drawn texts through the sim, every member against zlib, every dynamic header checked,
+    bgzf_host's image and CRC-32 against the sim and zlib.  Both verdicts occur, and some deflated block is within 2 % of
+    its text's size (the sweep reaches the threshold from below)."""
+    import soak_bgzf
+    stats = {}
+    assert soak_bgzf.run_host(15, 2028, verbose=False, stats=stats) == 45
+    assert stats["stored"] > 0 and stats["deflated"] > 0 and stats["closest"] > 0.98
+    assert stats["depth"]["literal/length"] <= 15 and stats["depth"]["code-length"] <= 7

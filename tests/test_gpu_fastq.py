@@ -12,102 +12,12 @@ import cli_util as cu
 import fastq_model as fm
 import trim_model as tm
 from sickle_amd import capi, synth
+from fastq_raw import SENTINEL, check, raw, texts_of, torch_mod, untouched, upload
 from test_fastq_api import golden_texts
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xAB
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def torch_mod():
-    import torch
-    return torch
-
-
-def upload(text, shift=0):
-    """text (bytes) on the device at an address that is `shift` bytes past a 16-byte boundary."""
-    torch = torch_mod()
-    buf = torch.zeros(len(text) + shift + 16, dtype=torch.uint8, device="cuda")
-    if len(text):
-        buf[shift:shift + len(text)] = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
-    return buf, buf.data_ptr() + shift
-
-
-def raw(ctx, params, texts, mode, caps=None, rec_caps=None, shift=0, max_read_len=0, index=True, ws=None, stream=None,
-        finish=True):
-    """One async + finish on raw pointers, every output pre-filled with SENTINEL.  caps / rec_caps: per output (None =
-    what the model says plus a little).  -> (rc, counts, [bytes or None], [index arrays or None])."""
-    torch = torch_mod()
-    bufs = [upload(t, shift) for t in texts]
-    T = sum(len(t) for t in texts)
-    ws_bytes = capi.lib().sk_trim_fastq_workspace_bytes(T, params.trunc_n)
-    if ws is None:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-    caps = caps or [T + 64] * 3
-    rec_caps = rec_caps or [T // 4 + 4] * 3
-    outs, keep = [], []
-    for o in range(3):
-        if caps[o] is None:
-            outs.append(capi.FastqOutput())
-            keep.append(None)
-            continue
-        t = torch.full((max(caps[o], 16),), SENTINEL, dtype=torch.uint8, device="cuda")
-        ix = torch.full((max(rec_caps[o], 1),), -7, dtype=torch.int64, device="cuda") if index else None
-        outs.append(capi.FastqOutput(t.data_ptr(), caps[o], ix.data_ptr() if index else None, rec_caps[o]))
-        keep.append((t, ix))
-    inp = capi.FastqInput((C.c_void_p * 2)(*([b[1] for b in bufs] + [None] * (2 - len(bufs)))),
-                          (C.c_uint64 * 2)(*([len(t) for t in texts] + [0] * (2 - len(texts)))), max_read_len)
-    arr = (capi.FastqOutput * 3)(*outs)
-    L = capi.lib()
-    rc = L.sk_trim_fastq_device_async(ctx._h, C.byref(params), C.byref(inp), capi.TRIM_MODES[mode], arr, ws.data_ptr(),
-                                      ws_bytes, stream)
-    assert rc == capi.SK_OK, L.sk_last_error(ctx._h)
-    if not finish:
-        return ws, keep, bufs
-    c = capi.FastqCounts()
-    rc = L.sk_trim_fastq_device_finish(ctx._h, ws.data_ptr(), stream, C.byref(c))
-    return rc, c.as_dict(), keep
-
-
-def texts_of(keep, counts):
-    return [None if k is None else k[0][:counts["bytes"][o]].cpu().numpy().tobytes() for o, k in enumerate(keep)]
-
-
-def untouched(keep):
-    for k in keep:
-        if k is not None:
-            assert bool((k[0] == SENTINEL).all()), "an output was written after an error"
-            if k[1] is not None:
-                assert bool((k[1] == -7).all())
-
-
-def check(ctx, ptuple, texts, mode, **kw):
-    """The device against the model: verdict, range error or every output text, index and count."""
-    want = fm.expected(ptuple, texts, mode)
-    rc, counts, keep = raw(ctx, capi.make_params(*ptuple), texts, mode, **kw)
-    assert counts["records_in"] == want["records_in"] and counts["tail_lines"] == want["tail_lines"]
-    assert counts["dropped_unpaired"] == want["dropped_unpaired"]
-    if want["verdict"] is not None:
-        assert rc == capi.SK_EFORMAT
-        assert (counts["format_error"], counts["format_input"], counts["format_record"]) == want["verdict"]
-        untouched(keep)
-        return rc, counts, None
-    if want["range"] is not None:
-        assert rc == capi.SK_ERANGE
-        assert counts["range"] == tuple(want["range"])
-        untouched(keep)
-        return rc, counts, None
-    assert rc == capi.SK_OK, capi.lib().sk_last_error(ctx._h)
-    got = texts_of(keep, counts)
-    for o in range(3):
-        if o not in fm.USED[mode]:
-            continue
-        assert got[o] == want["texts"][o], "output %d" % o
-        assert counts["records"][o] == len(want["index"][o]) and counts["bytes"][o] == len(want["texts"][o])
-        if keep[o][1] is not None:
-            assert np.array_equal(keep[o][1][:counts["records"][o]].cpu().numpy(), want["index"][o])
-    return rc, counts, got
 
 
 # ---- 1 the reference runs ----------------------------------------------------------------------------------------
@@ -313,6 +223,58 @@ def test_at_size(sk_ctx, kind):
               index=False)
 
 
+def _tile_10kb(seed, n=3000, L=10_000):
+    """n records of L bases whose quality stays above -q 20, one read in ten with a bad tail from a drawn position on (so it
+    is cut there) and one in fifty bad throughout (dropped): most of the text is kept."""
+    rng = np.random.default_rng(seed)
+    qual = rng.integers(55, 75, (n, L), dtype=np.uint8)
+    tail = np.where(rng.random(n) < 0.1, rng.integers(100, L, n), L)
+    tail[rng.random(n) < 0.02] = 0
+    qual[np.arange(L)[None, :] >= tail[:, None]] = 35
+    seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (n, L))]
+    name = np.empty((n, 12), np.uint8)
+    name[:, 0], name[:, 1], name[:, 11] = ord("@"), ord("t"), 10
+    for p in range(9):
+        name[:, 10 - p] = 48 + (np.arange(n) * 7 + seed) // 10 ** p % 10
+    nl = np.full((n, 1), 10, np.uint8)
+    return np.concatenate([name, seq, nl, np.tile(np.frombuffer(b"+\n", np.uint8), (n, 1)), qual, nl], 1).tobytes()
+
+
+def test_text_beyond_4_gib(sk_ctx):
+    """A text of more than 2^32 bytes of 10 kb reads, SK_TRIM_SE, built on the device from three different tiles of 3 000
+    records in a fixed pattern.  Records are independent and stay in order, so the model's output is the tiles' outputs in
+    that pattern: its MD5 is computed tile by tile (a slice of records each) and compared with the MD5 of the device's
+    output read back in pieces, plus the counts.  Text, framing tables and output offsets all pass 2^32."""
+    torch = torch_mod()
+    pt = ("sanger", 20, 20, False, False)
+    tiles = [_tile_10kb(60 + k) for k in range(3)]
+    wants = [fm.expected(pt, [t], "se") for t in tiles]
+    assert all(w["verdict"] is None and w["range"] is None and 2500 < len(w["index"][0]) < 3000 for w in wants)
+    reps = (1 << 32) // min(len(w["texts"][0]) for w in wants) + 2  # the output, too, passes 2^32 bytes
+    pattern = [(7 * k) % 3 for k in range(reps)]
+    dt = [torch.from_numpy(np.frombuffer(t, dtype=np.uint8).copy()).cuda() for t in tiles]
+    text = torch.cat([dt[k] for k in pattern])
+    del dt
+    total = sum(len(tiles[k]) for k in pattern)
+    assert text.numel() == total > 1 << 32
+    outs, counts = sk_ctx.trim_fastq(capi.make_params(*pt), text, mode="se")
+    del text
+    want_md5, want_bytes, want_records = hashlib.md5(), 0, 0
+    for k in pattern:
+        want_md5.update(wants[k]["texts"][0])
+        want_bytes += len(wants[k]["texts"][0])
+        want_records += len(wants[k]["index"][0])
+    assert counts["records_in"] == [3000 * reps, 0] and counts["tail_lines"] == [0, 0]
+    assert counts["records"][0] == want_records and counts["bytes"][0] == want_bytes == outs[0].numel()
+    assert want_bytes > 1 << 32
+    got_md5 = hashlib.md5()
+    for a in range(0, want_bytes, 1 << 28):
+        got_md5.update(outs[0][a:a + (1 << 28)].cpu().numpy().tobytes())
+    assert got_md5.hexdigest() == want_md5.hexdigest()
+    del outs
+    torch.cuda.empty_cache()
+
+
 # ---- 6 capacity --------------------------------------------------------------------------------------------------
 def test_capacity(sk_ctx):
     pt = ("sanger", 20, 20, False, False)
@@ -384,3 +346,85 @@ def test_trim_fastq_raises(sk_ctx):
     t = torch.from_numpy(np.frombuffer(b"".join(many_good(10)), np.uint8).copy()).cuda()
     outs, counts = sk_ctx.trim_fastq(capi.make_params(), t, mode="pe_interleaved", record_index=True)
     assert outs[1] is None and outs[0][1].numel() == counts["records"][0]
+
+
+# ---- 8 lines over several framing chunks, newlines on chunk boundaries, degenerate texts ----------------------------
+def _record(rng, k, L, name=b""):
+    q = bytes(rng.integers(35, 75, size=L, dtype=np.uint8))
+    s = bytearray(rng.choice(np.frombuffer(b"ACGT", np.uint8), size=L))
+    if k % 10 == 3 and L < 1000:
+        s[int(rng.integers(0, L))] = ord("N")
+    return [b"@r%d%s" % (k, name), bytes(s), b"+", q]
+
+
+def _join(recs):
+    return b"".join(x + b"\n" for r in recs for x in r)
+
+
+def test_lines_over_several_chunks(sk_ctx):
+    """A valid text whose reads of 70 000, 131 072 and 200 000 bases each cover 64 KiB framing chunks without any '\\n',
+    among short reads, with -n, at text addresses 0, 1 and 15 past a 16-byte boundary."""
+    rng = np.random.default_rng(81)
+    lens = [int(x) for x in rng.integers(30, 152, 400)]
+    for at, L in ((7, 70_000), (120, 131_072), (121, 200_000), (399, 131_072)):
+        lens[at] = L
+    text = _join([_record(rng, k, L) for k, L in enumerate(lens)])
+    for shift in (0, 1, 15):
+        for mode in ("se", "pe_interleaved"):
+            rc, counts, _ = check(sk_ctx, ("sanger", 20, 20, False, True), [text], mode, shift=shift)
+            assert rc == capi.SK_OK and counts["records_in"][0] == 400 and sum(counts["bytes"]) > 400_000
+
+
+@pytest.mark.parametrize("item", ["name_nl", "seq_nl", "plus_nl", "qual_nl", "first_byte"])
+@pytest.mark.parametrize("byte", [65535, 65536])
+@pytest.mark.parametrize("shift", [0, 9])
+def test_newline_on_a_chunk_boundary(sk_ctx, item, byte, shift):
+    """Each of the four '\\n' of a record, and the record's first byte, on the last byte of the second 64 KiB framing chunk
+    and on the first byte of the third (a name line padded to put it there).  The kernel's chunks start at the 16-byte
+    boundary below the text: at shift 9 the byte lies on the kernel's chunk edge and not on the text's."""
+    rng = np.random.default_rng(82)
+    recs = [_record(rng, k, 100) for k in range(1200)]
+    i = ["name_nl", "seq_nl", "plus_nl", "qual_nl", "first_byte"].index(item)
+    target, at, k = 65536 + byte - shift, 0, 0
+    while True:  # the last record whose item lies at or before the target
+        size = sum(len(x) + 1 for x in recs[k])
+        if at + size + (0 if i == 4 else sum(len(x) + 1 for x in recs[k + 1][:i + 1]) - 1) > target:
+            break
+        at += size
+        k += 1
+    pos = at if i == 4 else at + sum(len(x) + 1 for x in recs[k][:i + 1]) - 1
+    recs[k - 1 if i == 4 else k][0] += b"p" * (target - pos)
+    text = _join(recs)
+    assert (text[target] == 10) if i < 4 else (text[target] == ord("@") and text[target - 1] == 10)
+    for mode in ("se", "pe_interleaved"):
+        rc, counts, _ = check(sk_ctx, ("sanger", 20, 20, False, False), [text], mode, shift=shift)
+        assert rc == capi.SK_OK and counts["records_in"][0] == 1200
+
+
+@pytest.mark.parametrize("name", ["empty", "one_byte", "nl_1", "nl_7", "nl_8", "nl_9", "nl_70000", "leading_nl", "no_nl"])
+def test_degenerate_texts(sk_ctx, name):
+    """Texts without a record, of newlines only, with a leading newline, and one line longer than a chunk without any
+    newline: the counts and the verdict of the model, nothing written."""
+    good = b"".join(many_good(50, L=60))
+    text = {"empty": b"", "one_byte": b"A", "nl_1": b"\n", "nl_7": b"\n" * 7, "nl_8": b"\n" * 8, "nl_9": b"\n" * 9,
+            "nl_70000": b"\n" * 70_000, "leading_nl": b"\n" + good, "no_nl": b"A" * 70_001}[name]
+    pt = ("sanger", 20, 20, False, False)
+    want = fm.expected(pt, [text], "se")
+    if name in ("empty", "one_byte", "nl_1", "no_nl"):  # fewer than four lines: no record, so nothing to judge
+        assert want["verdict"] is None and want["records_in"][0] == 0
+    else:
+        assert want["verdict"] == (capi.SK_FQ_ID_SHORT, 0, 0)
+    for mode in ("se", "pe_interleaved"):
+        for shift in (0, 9):
+            check(sk_ctx, pt, [text], mode, shift=shift)
+
+
+FASTQ_SOAK = (120, 316)  # iterations, comparisons
+
+
+def test_fastq_soak(sk_ctx):
+    """tests/soak_fastq.py: random FASTQ texts (placed newlines, lines over chunks, endings, malformed records, every mode
+    and encoding, capacities) against tests/fastq_model.py (the same draws without a device give the same number of
+    comparisons: soak_fastq.py --dry)."""
+    import soak_fastq
+    assert soak_fastq.run(FASTQ_SOAK[0], 2028, verbose=False) == FASTQ_SOAK[1]

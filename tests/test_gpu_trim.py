@@ -10,28 +10,9 @@ import cli_util as cu
 import oracle_bind as ob
 import trim_model as tm
 from sickle_amd import capi, synth
+from trim_raw import Raw, dev, host, raw_call, torch_mod
 
 pytestmark = pytest.mark.gpu
-
-def torch_mod():
-    import torch
-    return torch
-
-
-def dev(a):
-    torch = torch_mod()
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint64:
-        a = a.view(np.int64)
-    elif a.dtype == np.uint32:
-        a = a.view(np.int32)
-    return torch.from_numpy(a).cuda()
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def check_outputs(got, want, mode):
@@ -225,40 +206,41 @@ def test_at_size_se_and_pe_split(sk_ctx):
     torch.cuda.empty_cache()
 
 
-# ---- 4 capacity, 5 bad cuts: the raw C ABI ------------------------------------------------------------------------
-class Raw:
-    """Device buffers for the three outputs of a raw sk_trim_device_async call, filled with a canary."""
-    CANARY = 0xA5
-
-    def __init__(self, recs, nbytes, seq=True):
-        torch = torch_mod()
-        self.t = []
-        self.outs = []
-        for o in range(3):
-            q = torch.full((nbytes[o] + 16,), self.CANARY, dtype=torch.uint8, device="cuda")
-            s = torch.full((nbytes[o] + 16,), self.CANARY, dtype=torch.uint8, device="cuda") if seq else None
-            off = torch.full((recs[o] + 2,), -0x5a5a5a5a, dtype=torch.int64, device="cuda")
-            idx = torch.full((recs[o] + 1,), -0x5a5a5a5a, dtype=torch.int64, device="cuda")
-            self.t.append((q, s, off, idx))
-            self.outs.append(capi.TrimOutput(q.data_ptr(), None if s is None else s.data_ptr(), off.data_ptr(),
-                                             idx.data_ptr(), nbytes[o], recs[o]))
-
-    def untouched(self, o):
-        q, s, off, idx = self.t[o]
-        ok = bool((q == self.CANARY).all()) and bool((off == -0x5a5a5a5a).all()) and bool((idx == -0x5a5a5a5a).all())
-        return ok and (s is None or bool((s == self.CANARY).all()))
-
-
-def raw_call(ctx, qual_t, seq_t, off_t, cuts_t, n, outs, mode, ws=None, stream=None):
+def test_offsets_beyond_4_gib(sk_ctx):
+    """An `offsets` batch of 45 000 reads of 100 kb, 4.5e9 bytes of qual built on the device from one tile of 500 reads, no
+    seq, hand-made cuts that keep most of every read (2 % of the reads dropped), SK_TRIM_SE: input and output offsets
+    beyond 2^32.  Compared tile by tile, so the host never holds an index per byte of the batch."""
     torch = torch_mod()
-    nb = capi.lib().sk_trim_workspace_bytes(n)
-    if ws is None:
-        ws = torch.empty(nb + 16, dtype=torch.uint8, device="cuda")
-    return ctx.trim_device(cuts_t.data_ptr(), n, outs, ws.data_ptr(), nb, mode=mode, stream=stream,
-                           qual_ptr=qual_t.data_ptr(), seq_ptr=None if seq_t is None else seq_t.data_ptr(),
-                           offsets_ptr=off_t.data_ptr())
+    L, tile, reps = 100_000, 500, 90
+    n = tile * reps
+    rng = np.random.default_rng(51)
+    base = rng.integers(33, 75, tile * L, dtype=np.uint8)
+    dq = dev(base).repeat(reps)
+    assert dq.numel() > 1 << 32
+    off = np.arange(n + 1, dtype=np.uint64) * np.uint64(L)
+    cuts = np.stack([rng.integers(0, 500, n), L - rng.integers(0, 500, n)], axis=1).astype(np.int32)
+    cuts[rng.random(n) < 0.02] = (-1, -1)
+    got = sk_ctx.trim_reads_device(None, dq, None, offsets=dev(off), mode="se", cuts=dev(cuts))
+    assert got[1] is None and got[2] is None
+    q, s, o, idx = got[0]
+    assert s is None
+    o_h, idx_h = host(o), host(idx)
+    q2d = base.reshape(tile, L)
+    r0 = b0 = 0
+    for t in range(reps):
+        want = _fixed_expected(q2d, q2d, cuts[t * tile:(t + 1) * tile], "se", t * tile)[0]
+        R, B = len(want["read_index"]), int(want["offsets"][-1])
+        assert np.array_equal(o_h[r0:r0 + R + 1] - b0, want["offsets"]), t
+        assert np.array_equal(idx_h[r0:r0 + R], want["read_index"]), t
+        assert np.array_equal(host(q[b0:b0 + B]), want["qual"]), t
+        r0 += R
+        b0 += B
+    assert r0 == len(idx_h) and b0 == q.numel() and b0 > 1 << 32 and 0 < r0 < n
+    del dq, q, o, idx, got
+    torch.cuda.empty_cache()
 
 
+# ---- 4 capacity, 5 bad cuts: the raw C ABI ------------------------------------------------------------------------
 def test_capacity_one_short_and_count_only(sk_ctx):
     qual, seq, starts, kw, lens = LAYOUTS["ragged1_2500"]
     off = kw["offsets"]
@@ -398,3 +380,37 @@ def test_trim_output_is_a_valid_offsets_batch(sk_ctx):
     want, err = ob.oracle_trim_batch(ob.make_params(*p2), host(q), host(s), offsets=host(off).astype(np.uint64))
     assert err is None
     assert np.array_equal(host(out), want)
+
+
+# ---- 7 block boundaries and tiny outputs -------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 4097])
+@pytest.mark.parametrize("total", [1, 15, 16, 17, 47])
+def test_only_the_last_read_or_pair_kept(sk_ctx, n, total):
+    """Reads are counted in blocks of 2 048: n reads (SK_TRIM_SE) or n pairs (the PE modes) of which only the last one is
+    kept, `total` bytes of it -- a count block whose only kept record is its last, an output smaller than one 16-byte
+    granule, one granule, and a few."""
+    rng = np.random.default_rng(n * 100 + total)
+    for mode in tm.MODES:
+        reads = n if mode == "se" else 2 * n
+        lens = rng.integers(47, 120, reads)
+        off = np.zeros(reads + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(lens)
+        qual = rng.integers(33, 75, int(off[-1])).astype(np.uint8)
+        seq = rng.choice(np.frombuffer(b"ACGTN", dtype=np.uint8), int(off[-1]))
+        cuts = np.full((reads, 2), -1, np.int32)
+        for r in range(reads - (1 if mode == "se" else 2), reads):
+            five = int(rng.integers(0, lens[r] - total + 1))
+            cuts[r] = (five, five + total)
+        want = tm.expected(qual, seq, off[:-1].astype(np.int64), cuts, mode)
+        assert tm.counts_of(want)["bytes"][0] == (total if mode != "pe_interleaved" else 2 * total)
+        check_outputs(trim(sk_ctx, qual, seq, cuts, mode, offsets=off), want, mode)
+
+
+TRIM_SOAK = (100, 290)  # iterations, comparisons
+
+
+def test_trim_soak(sk_ctx):
+    """tests/soak_trim.py: random batches, layouts, alignments, cuts, modes and capacities through the raw C ABI against
+    tests/trim_model.py (the same draws without a device give the same number of comparisons: soak_trim.py --dry)."""
+    import soak_trim
+    assert soak_trim.run(TRIM_SOAK[0], 2028, verbose=False) == TRIM_SOAK[1]
