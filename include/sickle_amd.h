@@ -460,6 +460,67 @@ int sk_bgzf_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgz
  */
 int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t **bytes_dev, const uint64_t **written_dev);
 
+/*
+ * BGZF read on the device: a BGZF byte image in device memory -> the concatenated text of its members in device memory,
+ * with every member's CRC-32 and ISIZE checked.  The inverse of sk_bgzf_device_async, and it reads what bgzip and htslib
+ * write.  Plain (non-BGZF) gzip is NOT decoded: it is reported as SK_GZ_HEADER at member 0, and the caller falls back to a
+ * host decoder.
+ *
+ * Framing.  Members lie back to back from image[0].  A member begins 1f 8b 08, FLG exactly 04, six bytes that are not
+ * looked at (MTIME, XFL, OS), XLEN; the extra field is walked subfield by subfield (SI1 SI2 SLEN data) for the first
+ * 'B' 'C' 02 00 BSIZE, which need not come first.  The member is BSIZE + 1 bytes, its body lies between the extra field and
+ * the 8-byte trailer (CRC-32, ISIZE).  Where a member must begin, in this order: bytes that are not 1f 8b 08 04 (as many
+ * of the four as the image still holds) are SK_GZ_HEADER, so trailing garbage is; fewer than 26 bytes left (12 + the
+ * 6-byte subfield + an empty body + 8: the shortest member), or an extra field that ends beyond the image, is
+ * SK_GZ_TRUNCATED; a subfield that overruns XLEN, no BC subfield, or BSIZE + 1 < 12 + XLEN + 8 is SK_GZ_HEADER; a member that
+ * ends beyond the image is SK_GZ_TRUNCATED.  Framing stops there: `members` counts those framed before it, and the error
+ * is that of member `members`.  ISIZE above 65 536 is SK_GZ_LENGTH (the member is framed, not decoded, and adds nothing to
+ * bytes_out).  An empty image is valid: 0 members.
+ *
+ * Decoding.  All of RFC 1951: stored, fixed and dynamic blocks, any number per member, empty ones included.  SK_GZ_DEFLATE:
+ * block type 3; stored LEN != ~NLEN; HLIT > 29 or HDIST > 29; an over-subscribed code; an incomplete code, except (as in
+ * zlib) one whose longest code has one bit; no end-of-block code; a repeat with nothing before it or past HLIT + HDIST; a
+ * bit pattern without a symbol; length symbols 286 / 287, distance symbols 30 / 31; a distance reaching before the member's
+ * first byte; bits or stored bytes beyond the body.  Body bytes behind the final block are ignored.  Text beyond ISIZE is
+ * SK_GZ_LENGTH at the token that would cross it, text short of ISIZE at the end of the stream; then the CRC-32 of the text
+ * against the trailer, SK_GZ_CRC.  The first check to fail is the member's reason; across members the lowest index wins.
+ *
+ * out == NULL with capacity == 0 only counts (framing and sums, no decode, so only framing errors and ISIZE > 65 536 are
+ * seen): this is how a caller sizes `out`.  If bytes_out > capacity NOTHING is written to out, nothing is decoded, and
+ * finish returns SK_ESPACE with bytes_out = the need.  finish returns, in this order of precedence, SK_EDATA (counts say
+ * where and why), SK_ESPACE, SK_OK.  After SK_EDATA out[0, min(bytes_out, capacity)) is undefined; no byte at or beyond
+ * capacity is ever written, and a member writes inside its own ISIZE span only.  A corrupt image is never read outside
+ * [image, image + image_bytes).  `image` has any alignment, `out` and `workspace` are 16-byte aligned.
+ *
+ * sk_bgzf_inflate_device_async only enqueues kernels on hip_stream (7 + ceil(log2(n / 26 + 1)) + 1 of them): no allocation,
+ * no copy, no synchronisation.  All scratch and the counts live in `workspace`.  With n = image_bytes and
+ * A(x) = 16 ceil(x / 16):
+ *   sk_bgzf_inflate_workspace_bytes(n) = 128 + A(4 (floor(n / 4096) + 1)) + A(8 C) + 3 A(4 C) + A(40 (floor(n / 26) + 1)),
+ *                                        C = floor(n / 4) + 1
+ * (header; a count per 4096 positions; position, two successor words and a rank for each of the at most n / 4
+ * non-overlapping matches of 1f 8b 08 04; a table entry per member), about 6.6 bytes per image byte.  It holds for any image,
+ * adversarial ones included, and needs no device: the grids are constants.  An image above 8 GiB is SK_EINVAL.
+ * sk_bgzf_inflate_device_finish is the only call that waits.  Two calls in flight need two workspaces.  Bad arguments (NULL
+ * ctx, image NULL with bytes != 0, out NULL with capacity != 0, out or workspace not 16-byte aligned, a short workspace, an
+ * image above 8 GiB) return SK_EINVAL and enqueue nothing.
+ */
+enum { SK_EDATA = -7 }; /* sk_bgzf_inflate_device_finish: the image is not valid BGZF (counts say where and why) */
+enum { SK_GZ_OK = 0, SK_GZ_HEADER = 1, SK_GZ_TRUNCATED = 2, SK_GZ_DEFLATE = 3, SK_GZ_LENGTH = 4, SK_GZ_CRC = 5 };
+
+typedef struct {
+    uint64_t bytes_in, members;  /* members framed, empty ones (the EOF marker) included */
+    uint64_t bytes_out;          /* sum of ISIZE: what `out` needs, also when it did not fit or was NULL */
+    int32_t  error;              /* SK_GZ_* of the LOWEST bad member, SK_GZ_OK if none */
+    uint32_t reserved;
+    uint64_t error_member, error_offset; /* its index, and its byte offset in the image */
+} sk_bgzf_inflate_counts;
+
+size_t sk_bgzf_inflate_workspace_bytes(uint64_t image_bytes);   /* pure, no device */
+int sk_bgzf_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
+                                 void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts from the workspace: SK_EDATA, SK_ESPACE or SK_OK (in this order of precedence). */
+int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_inflate_counts *counts);
+
 #ifdef __cplusplus
 }
 #endif

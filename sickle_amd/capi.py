@@ -9,7 +9,9 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsickle_amd.so")
 
-SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE, SK_EFORMAT = 0, 1, -1, -2, -3, -4, -5, -6
+SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE, SK_EFORMAT, SK_EDATA = 0, 1, -1, -2, -3, -4, -5, -6, -7
+# why a BGZF image is not valid (sk_bgzf_inflate_device_finish)
+SK_GZ_OK, SK_GZ_HEADER, SK_GZ_TRUNCATED, SK_GZ_DEFLATE, SK_GZ_LENGTH, SK_GZ_CRC = range(6)
 # why a FASTQ record is malformed (sk_trim_fastq_device_finish), in the order the reference checks
 (SK_FQ_OK, SK_FQ_ID_SHORT, SK_FQ_ID_NO_AT, SK_FQ_SEQ_EMPTY, SK_FQ_QUAL_EMPTY, SK_FQ_LENGTHS, SK_FQ_TOO_LONG,
  SK_FQ_PAIR_COUNT) = range(8)
@@ -26,7 +28,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish",
            "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish",
            "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_device_async",
-           "sk_bgzf_device_finish")
+           "sk_bgzf_device_finish", "sk_bgzf_inflate_workspace_bytes", "sk_bgzf_inflate_device_async",
+           "sk_bgzf_inflate_device_finish")
 SK_BGZF_EOF = 1
 
 
@@ -116,8 +119,26 @@ class BgzfCounts(C.Structure):
                 "bytes_out": int(self.bytes_out)}
 
 
+class BgzfInflateCounts(C.Structure):
+    _fields_ = [("bytes_in", C.c_uint64), ("members", C.c_uint64), ("bytes_out", C.c_uint64), ("error", C.c_int32),
+                ("reserved", C.c_uint32), ("error_member", C.c_uint64), ("error_offset", C.c_uint64)]
+
+    def as_dict(self):
+        return {"bytes_in": int(self.bytes_in), "members": int(self.members), "bytes_out": int(self.bytes_out),
+                "error": int(self.error), "error_member": int(self.error_member), "error_offset": int(self.error_offset)}
+
+
 class SickleError(RuntimeError):
     pass
+
+
+class GzDataError(SickleError):
+    """sk_bgzf_inflate_device_finish returned SK_EDATA: member `member` at byte `offset` of the image is bad, `reason`
+    (SK_GZ_*) says why.  SK_GZ_HEADER at member 0 is what a plain, non-BGZF gzip file gives: decode it on the host."""
+
+    def __init__(self, reason, member, offset, counts=None):
+        super().__init__("not valid BGZF: member %d at byte %d (reason %d)" % (member, offset, reason))
+        self.reason, self.member, self.offset, self.counts = reason, member, offset, counts
 
 
 class TrimError(SickleError):
@@ -230,6 +251,13 @@ def lib():
                                            C.c_size_t, C.c_void_p]
         L.sk_bgzf_device_finish.restype = C.c_int
         L.sk_bgzf_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BgzfCounts)]
+        L.sk_bgzf_inflate_workspace_bytes.restype = C.c_size_t
+        L.sk_bgzf_inflate_workspace_bytes.argtypes = [C.c_uint64]
+        L.sk_bgzf_inflate_device_async.restype = C.c_int
+        L.sk_bgzf_inflate_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]
+        L.sk_bgzf_inflate_device_finish.restype = C.c_int
+        L.sk_bgzf_inflate_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateCounts)]
         _lib = L
     return _lib
 
@@ -523,6 +551,47 @@ class Context:
                      for o in range(3)]
         counts = self.trim_fastq_device_finish(ws.data_ptr(), stream)
         return tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3)), counts
+
+    # ---- BGZF read on the device --------------------------------------------------------------
+    def bgzf_inflate_device_async(self, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, stream=None):
+        """sk_bgzf_inflate_device_async on raw device pointers; out_ptr None with capacity 0 only counts."""
+        self._check(lib().sk_bgzf_inflate_device_async(self._h, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr,
+                                                       workspace_bytes, stream))
+
+    def bgzf_inflate_device_finish(self, workspace_ptr, stream=None):
+        """sk_bgzf_inflate_device_finish -> counts (dict); raises GzDataError, or TrimError (with .counts) on SK_ESPACE."""
+        c = BgzfInflateCounts()
+        rc = lib().sk_bgzf_inflate_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc == SK_EDATA:
+            raise GzDataError(int(c.error), int(c.error_member), int(c.error_offset), c.as_dict())
+        if rc == SK_ESPACE:
+            raise TrimError("bgzf inflate failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc)
+        return c.as_dict()
+
+    def bgunzip(self, image):
+        """A BGZF image in device memory (a uint8 torch tensor) -> its text (a uint8 tensor), on the current stream: a
+        count-only pass sizes the text, a second one writes it.  Raises GzDataError."""
+        import torch
+        dev, n = image.device, image.numel()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws_bytes = lib().sk_bgzf_inflate_workspace_bytes(n)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ptr = image.data_ptr() if n else None
+        self.bgzf_inflate_device_async(ptr, n, None, 0, ws.data_ptr(), ws_bytes, stream=stream)
+        need = self.bgzf_inflate_device_finish(ws.data_ptr(), stream)["bytes_out"]
+        out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        self.bgzf_inflate_device_async(ptr, n, out.data_ptr(), need, ws.data_ptr(), ws_bytes, stream=stream)
+        self.bgzf_inflate_device_finish(ws.data_ptr(), stream)
+        return out[:need]
+
+    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0):
+        """.fastq.gz (BGZF) image(s) in device memory -> the trimmed texts as BGZF images, every byte of work on the
+        device: bgunzip, then trim_fastq_gz.  The one host wait in between is the text's length, which sk_fastq_input
+        takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises."""
+        text = self.bgunzip(image)
+        text2 = None if image2 is None else self.bgunzip(image2)
+        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):

@@ -919,6 +919,73 @@ int sk_bgzf_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgz
     return SK_OK;
 }
 
+size_t sk_bgzf_inflate_workspace_bytes(uint64_t image_bytes)
+{
+    sk_inflate_layout L;
+    sk_inflate_layout_of(image_bytes, &L);
+    return (size_t)L.total;
+}
+
+int sk_bgzf_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
+                                 void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+#define SK_GZ_BAD(...)               \
+    do {                             \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;            \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!image && image_bytes) SK_GZ_BAD("bgzf inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (image_bytes > SK_INFLATE_MAX_IMAGE)
+        SK_GZ_BAD("bgzf inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_GZ_BAD("bgzf inflate: out must be 16-byte aligned");
+    if (!out && capacity) SK_GZ_BAD("bgzf inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+    const size_t need = sk_bgzf_inflate_workspace_bytes(image_bytes);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
+        SK_GZ_BAD("bgzf inflate: workspace must be 16-byte aligned and hold sk_bgzf_inflate_workspace_bytes(%llu) = %zu bytes",
+                  (unsigned long long)image_bytes, need);
+#undef SK_GZ_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_bgzf_inflate(image, image_bytes, out, capacity, workspace, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_inflate_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[SK_INFLATE_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    memset(counts, 0, sizeof *counts);
+    counts->bytes_in = h[SK_INFLATE_H_BYTES_IN];
+    counts->members = h[SK_INFLATE_H_MEMBERS];
+    counts->bytes_out = h[SK_INFLATE_H_BYTES_OUT];
+    const uint64_t key = h[SK_INFLATE_H_ERROR_KEY];
+    if (key != ~0ull) {
+        counts->error = (int32_t)(key & 7);
+        counts->error_member = key >> 3;
+        if (key == h[SK_INFLATE_H_FRAME_KEY]) {
+            counts->error_offset = h[SK_INFLATE_H_FRAME_OFFSET];
+        } else { // a member that framed: its offset is in the table
+            sk_inflate_layout L;
+            sk_inflate_layout_of(counts->bytes_in, &L);
+            const uint8_t *entry = static_cast<const uint8_t *>(workspace) + L.table + sizeof(sk_inflate_entry) * counts->error_member;
+            SK_HIP(ctx, hipMemcpyAsync(&counts->error_offset, entry, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            SK_HIP(ctx, hipStreamSynchronize(stream));
+        }
+        set_error(ctx, "bgzf inflate: member %llu at byte %llu is not valid BGZF (reason %d)",
+                  (unsigned long long)counts->error_member, (unsigned long long)counts->error_offset, counts->error);
+        return SK_EDATA;
+    }
+    if (!h[SK_INFLATE_H_FIT]) {
+        set_error(ctx, "bgzf inflate: the text needs %llu bytes, more than the capacity", (unsigned long long)counts->bytes_out);
+        return SK_ESPACE;
+    }
+    return SK_OK;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

@@ -234,6 +234,57 @@ static inline void sk_bgzf_layout_of(uint64_t text_bytes, sk_bgzf_layout *L)
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf(const sk_bgzf_input *in, uint8_t *out, uint64_t capacity,
                                                                            int flags, void *workspace, int cu_count,
                                                                            hipStream_t stream);
+// BGZF read on the device (sk_inflate.hip).  The caller's workspace (16-byte sections, sizes in bytes, n = image bytes):
+//   header    SK_INFLATE_HDR_WORDS words
+//   tiles     4 per tile of SK_INFLATE_TILE byte positions (n / 4096 + 1 tiles): candidates in the tile, then their base
+//   cand      8 per candidate: its position.  A candidate is a match of 1f 8b 08 04, and matches cannot overlap, so an
+//             image holds n / 4 at most, whatever its bytes; + 1
+//   next a/b  4 per candidate each: the successor's index, ping-pong for the pointer doubling
+//   rank      4 per candidate: its member number if the chain from position 0 reaches it
+//   table     40 per member: n / 26 + 1 members at most (SK_INFLATE_MIN_MEMBER bytes each)
+// The grids are constants, not the device's CU count: 16 single-wave workgroups per CU on the 256 CUs of an MI355X.
+#define SK_INFLATE_TILE 4096u
+#define SK_INFLATE_MIN_MEMBER 26u
+#define SK_INFLATE_GRID 4096u
+#define SK_INFLATE_FRAME_GRID 2048u
+#define SK_INFLATE_MAX_IMAGE (1ull << 33) // the candidates' indices are 32-bit
+#define SK_INFLATE_HDR_WORDS 16u
+#define SK_INFLATE_H_BYTES_IN 0
+#define SK_INFLATE_H_MEMBERS 1
+#define SK_INFLATE_H_BYTES_OUT 2
+#define SK_INFLATE_H_FIT 3          // count-only, or the text is within the capacity: the inflate kernel writes it
+#define SK_INFLATE_H_ERROR_KEY 4    // (member << 3) | SK_GZ_* of the lowest bad member, or ~0
+#define SK_INFLATE_H_FRAME_KEY 5    // the same for the framing error alone
+#define SK_INFLATE_H_FRAME_OFFSET 6 // its byte offset (a member that framed has its offset in the table)
+#define SK_INFLATE_H_CANDIDATES 7
+struct sk_inflate_entry {
+    uint64_t image_off, out_off;
+    uint32_t body_off, body_len; // the deflate stream, relative to image_off
+    uint32_t isize, crc;
+    uint32_t verdict, reserved;  // SK_GZ_*
+};
+struct sk_inflate_layout {
+    uint64_t n_tiles, n_cand, n_table, rounds, tiles, cand, next_a, next_b, rank, table, total;
+};
+static inline uint64_t sk_inflate_a16(uint64_t x) { return (x + 15) & ~15ull; }
+static inline void sk_inflate_layout_of(uint64_t image_bytes, sk_inflate_layout *L)
+{
+    L->n_tiles = image_bytes / SK_INFLATE_TILE + 1;
+    L->n_cand = image_bytes / 4 + 1;
+    L->n_table = image_bytes / SK_INFLATE_MIN_MEMBER + 1;
+    L->rounds = 0;
+    while ((1ull << L->rounds) < L->n_table) ++L->rounds; // ranks are below n_table
+    L->tiles = 8 * SK_INFLATE_HDR_WORDS;
+    L->cand = L->tiles + sk_inflate_a16(4 * L->n_tiles);
+    L->next_a = L->cand + sk_inflate_a16(8 * L->n_cand);
+    L->next_b = L->next_a + sk_inflate_a16(4 * L->n_cand);
+    L->rank = L->next_b + sk_inflate_a16(4 * L->n_cand);
+    L->table = L->rank + sk_inflate_a16(4 * L->n_cand);
+    L->total = L->table + sk_inflate_a16(sizeof(sk_inflate_entry) * L->n_table);
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf_inflate(const uint8_t *image, uint64_t image_bytes,
+                                                                                   uint8_t *out, uint64_t capacity,
+                                                                                   void *workspace, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
