@@ -463,8 +463,8 @@ int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t
 /*
  * BGZF read on the device: a BGZF byte image in device memory -> the concatenated text of its members in device memory,
  * with every member's CRC-32 and ISIZE checked.  The inverse of sk_bgzf_device_async, and it reads what bgzip and htslib
- * write.  Plain (non-BGZF) gzip is NOT decoded: it is reported as SK_GZ_HEADER at member 0, and the caller falls back to a
- * host decoder.
+ * write.  Plain (non-BGZF) gzip is NOT decoded: it is reported as SK_GZ_HEADER at member 0, and the caller goes on to
+ * sk_gzip_inflate_device_async (below), which reads any gzip.
  *
  * Framing.  Members lie back to back from image[0].  A member begins 1f 8b 08, FLG exactly 04, six bytes that are not
  * looked at (MTIME, XFL, OS), XLEN; the extra field is walked subfield by subfield (SI1 SI2 SLEN data) for the first
@@ -520,6 +520,62 @@ int sk_bgzf_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t ima
                                  void *workspace, size_t workspace_bytes, void *hip_stream);
 /* Waits for hip_stream and fills *counts from the workspace: SK_EDATA, SK_ESPACE or SK_OK (in this order of precedence). */
 int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_inflate_counts *counts);
+
+/*
+ * Plain gzip read on the device: any gzip byte image in device memory (what gzip, pigz and zlib write: one long member or a
+ * few, no BC subfield) -> the concatenated text of its members in device memory, every member's CRC-32 and ISIZE checked.
+ * One deflate stream is decoded in parallel: the image is cut into chunks, a block start is guessed per chunk, every
+ * guessed start is decoded as a STRETCH until it arrives exactly on a later guess, and the chain of stretches from the
+ * first block is what counts; matches into the unknown 32 KiB before a stretch are filled in afterwards.  No result rests
+ * on a guess.  A BGZF image is valid input here, only slow: parallelism comes from non-final dynamic block headers, and
+ * an image of stored or fixed blocks alone, or of many one-block members, is decoded by few wavefronts
+ * (`stretches_used` tells).
+ *
+ * Format.  RFC 1952 members lie back to back from image[0].  Where a member must begin, in this order: bytes that are not
+ * 1f 8b 08 (as many of the three as the image still holds) are SK_GZ_HEADER, so trailing bytes are; fewer than 10 bytes
+ * left is SK_GZ_TRUNCATED; a reserved FLG bit (0xe0) is SK_GZ_HEADER; FEXTRA, FNAME, FCOMMENT and FHCRC are stepped over
+ * (the header CRC is not checked), and one that runs past the image is SK_GZ_TRUNCATED.  The deflate stream follows:
+ * all of RFC 1951 with the SK_GZ_DEFLATE list of the BGZF reader; bits that run out are SK_GZ_DEFLATE too.  A distance
+ * reaching before its member's first byte is SK_GZ_DEFLATE.  The final block ends on a byte boundary with the 8-byte
+ * trailer; fewer than 8 bytes left is SK_GZ_TRUNCATED.  A text length that differs from ISIZE mod 2^32 is SK_GZ_LENGTH;
+ * then the CRC-32: SK_GZ_CRC.  Within a member the reasons come in the order of their numbers, across members the lowest
+ * index wins.  error_offset is the member's first byte for header, truncation, length and CRC errors and the byte that
+ * holds the first bit of the failing block for SK_GZ_DEFLATE (image_bytes when the stream ends where a block must begin).
+ * A header, truncation or Huffman-level error stops the chain: `members` and `bytes_out` are then those up to it.  An empty
+ * image is valid: 0 members.
+ *
+ * out == NULL with capacity == 0 only counts: the lengths alone are decoded, so header, truncation and Huffman-level
+ * errors are seen, distance, length and CRC errors are not.  This is how a caller sizes `out`.  If bytes_out > capacity
+ * NOTHING is written to out and finish returns SK_ESPACE with bytes_out = the need.  finish returns, in this order of
+ * precedence, SK_EDATA, SK_ESPACE, SK_OK.  After SK_EDATA out[0, min(bytes_out, capacity)) is undefined.  No byte at or
+ * beyond capacity is ever written, none outside [image, image + image_bytes) is ever read.  `image` has any alignment,
+ * `out` and `workspace` are 16-byte aligned.
+ *
+ * sk_gzip_inflate_device_async only enqueues kernels on hip_stream (3 when counting, 9 otherwise): no allocation, no copy,
+ * no synchronisation.  All scratch and the counts live in `workspace`.  With n = image_bytes, A(x) = 16 ceil(x / 16),
+ * chunk = 32768 doubled until 4096 chunks hold n, and S = ceil(n / chunk):
+ *   sk_gzip_inflate_workspace_bytes(n, capacity) = 256 + 128 (S + 1) + A(8 (S + 1)) + A(4 (S + 1))
+ *                                                  + 32 (floor(n / 18) + 1) + A(2 capacity)
+ * (header; a record per stretch; the chain; an entry per member, whose trailers lie 18 bytes apart at least; the text as
+ * 16-bit symbols).  It needs no device.  The environment variable SK_GZIP_CHUNK, a power of two of 256 or more, replaces
+ * `chunk` in both calls (read at call time; anything else is ignored); it exists for tests.  Bad arguments (NULL ctx,
+ * image NULL with bytes != 0, out NULL with capacity != 0, out or workspace not 16-byte aligned, a short workspace, an
+ * image above 8 GiB) return SK_EINVAL and enqueue nothing.  Two calls in flight need two workspaces.
+ */
+typedef struct {
+    uint64_t bytes_in, members;       /* members completed (trailer reached) */
+    uint64_t bytes_out;               /* text bytes of the chain: what `out` needs */
+    uint64_t stretches, stretches_used; /* chunks the image was cut into; those the chain from bit 0 went through */
+    int32_t  error;                   /* SK_GZ_* of the lowest failure on the chain, SK_GZ_OK if none */
+    uint32_t reserved;
+    uint64_t error_member, error_offset;
+} sk_gzip_inflate_counts;
+
+size_t sk_gzip_inflate_workspace_bytes(uint64_t image_bytes, uint64_t capacity);   /* pure, no device */
+int sk_gzip_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
+                                 void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts from the workspace: SK_EDATA, SK_ESPACE or SK_OK (in this order of precedence). */
+int sk_gzip_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts);
 
 #ifdef __cplusplus
 }

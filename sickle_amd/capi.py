@@ -29,7 +29,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish",
            "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_device_async",
            "sk_bgzf_device_finish", "sk_bgzf_inflate_workspace_bytes", "sk_bgzf_inflate_device_async",
-           "sk_bgzf_inflate_device_finish")
+           "sk_bgzf_inflate_device_finish", "sk_gzip_inflate_workspace_bytes", "sk_gzip_inflate_device_async",
+           "sk_gzip_inflate_device_finish")
 SK_BGZF_EOF = 1
 
 
@@ -126,6 +127,17 @@ class BgzfInflateCounts(C.Structure):
     def as_dict(self):
         return {"bytes_in": int(self.bytes_in), "members": int(self.members), "bytes_out": int(self.bytes_out),
                 "error": int(self.error), "error_member": int(self.error_member), "error_offset": int(self.error_offset)}
+
+
+class GzipInflateCounts(C.Structure):
+    _fields_ = [("bytes_in", C.c_uint64), ("members", C.c_uint64), ("bytes_out", C.c_uint64), ("stretches", C.c_uint64),
+                ("stretches_used", C.c_uint64), ("error", C.c_int32), ("reserved", C.c_uint32), ("error_member", C.c_uint64),
+                ("error_offset", C.c_uint64)]
+
+    def as_dict(self):
+        return {"bytes_in": int(self.bytes_in), "members": int(self.members), "bytes_out": int(self.bytes_out),
+                "stretches": int(self.stretches), "stretches_used": int(self.stretches_used), "error": int(self.error),
+                "error_member": int(self.error_member), "error_offset": int(self.error_offset)}
 
 
 class SickleError(RuntimeError):
@@ -258,6 +270,13 @@ def lib():
                                                    C.c_size_t, C.c_void_p]
         L.sk_bgzf_inflate_device_finish.restype = C.c_int
         L.sk_bgzf_inflate_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BgzfInflateCounts)]
+        L.sk_gzip_inflate_workspace_bytes.restype = C.c_size_t
+        L.sk_gzip_inflate_workspace_bytes.argtypes = [C.c_uint64, C.c_uint64]
+        L.sk_gzip_inflate_device_async.restype = C.c_int
+        L.sk_gzip_inflate_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]
+        L.sk_gzip_inflate_device_finish.restype = C.c_int
+        L.sk_gzip_inflate_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GzipInflateCounts)]
         _lib = L
     return _lib
 
@@ -585,12 +604,58 @@ class Context:
         self.bgzf_inflate_device_finish(ws.data_ptr(), stream)
         return out[:need]
 
+    # ---- plain gzip read on the device -------------------------------------------------------
+    def gzip_inflate_device_async(self, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, stream=None):
+        """sk_gzip_inflate_device_async on raw device pointers; out_ptr None with capacity 0 only counts."""
+        self._check(lib().sk_gzip_inflate_device_async(self._h, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr,
+                                                       workspace_bytes, stream))
+
+    def gzip_inflate_device_finish(self, workspace_ptr, stream=None):
+        """sk_gzip_inflate_device_finish -> counts (dict); raises GzDataError, or TrimError (with .counts) on SK_ESPACE."""
+        c = GzipInflateCounts()
+        rc = lib().sk_gzip_inflate_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc == SK_EDATA:
+            raise GzDataError(int(c.error), int(c.error_member), int(c.error_offset), c.as_dict())
+        if rc == SK_ESPACE:
+            raise TrimError("gzip inflate failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc)
+        return c.as_dict()
+
+    def gunzip(self, image):
+        """Any gzip image in device memory (a uint8 torch tensor) -> its text (a uint8 tensor), on the current stream: a
+        count-only pass sizes the text, a second one writes it.  Raises GzDataError."""
+        import torch
+        dev, n = image.device, image.numel()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = image.data_ptr() if n else None
+        ws_bytes = lib().sk_gzip_inflate_workspace_bytes(n, 0)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        self.gzip_inflate_device_async(ptr, n, None, 0, ws.data_ptr(), ws_bytes, stream=stream)
+        need = self.gzip_inflate_device_finish(ws.data_ptr(), stream)["bytes_out"]
+        del ws
+        ws_bytes = lib().sk_gzip_inflate_workspace_bytes(n, need)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        self.gzip_inflate_device_async(ptr, n, out.data_ptr(), need, ws.data_ptr(), ws_bytes, stream=stream)
+        self.gzip_inflate_device_finish(ws.data_ptr(), stream)
+        return out[:need]
+
+    def _gunzip_any(self, image):
+        """bgunzip, and for an image the BGZF reader refuses at member 0 although it begins as gzip does, gunzip"""
+        try:
+            return self.bgunzip(image)
+        except GzDataError as e:
+            if (e.reason, e.member) != (SK_GZ_HEADER, 0) or image[:3].cpu().tolist() != [0x1f, 0x8b, 8]:
+                raise
+        return self.gunzip(image)
+
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0):
-        """.fastq.gz (BGZF) image(s) in device memory -> the trimmed texts as BGZF images, every byte of work on the
-        device: bgunzip, then trim_fastq_gz.  The one host wait in between is the text's length, which sk_fastq_input
-        takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises."""
-        text = self.bgunzip(image)
-        text2 = None if image2 is None else self.bgunzip(image2)
+        """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
+        on the device: bgunzip (gunzip for plain gzip), then trim_fastq_gz.  The one host wait in between is the text's
+        length, which sk_fastq_input takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what
+        it raises."""
+        text = self._gunzip_any(image)
+        text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len)
 
     @staticmethod

@@ -986,6 +986,81 @@ int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream
     return SK_OK;
 }
 
+// SK_GZIP_CHUNK: a power of two of 256 or more, else 0 (the chunk follows the image's size)
+static uint64_t gzip_forced_chunk()
+{
+    const char *e = getenv("SK_GZIP_CHUNK");
+    if (!e || !*e) return 0;
+    char *end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (*end || v < 256 || v > (1ull << 40) || (v & (v - 1))) return 0;
+    return v;
+}
+
+size_t sk_gzip_inflate_workspace_bytes(uint64_t image_bytes, uint64_t capacity)
+{
+    sk_gunzip_layout L;
+    sk_gunzip_layout_of(image_bytes, capacity, gzip_forced_chunk(), &L);
+    return (size_t)L.total;
+}
+
+int sk_gzip_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
+                                 void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+#define SK_GZ_BAD(...)               \
+    do {                             \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;            \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!image && image_bytes) SK_GZ_BAD("gzip inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (image_bytes > SK_GUNZIP_MAX_IMAGE)
+        SK_GZ_BAD("gzip inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_GZ_BAD("gzip inflate: out must be 16-byte aligned");
+    if (!out && capacity) SK_GZ_BAD("gzip inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+    if (capacity > (1ull << 60)) SK_GZ_BAD("gzip inflate: a capacity of %llu bytes", (unsigned long long)capacity);
+    const uint64_t forced = gzip_forced_chunk();
+    sk_gunzip_layout L;
+    sk_gunzip_layout_of(image_bytes, capacity, forced, &L);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < L.total)
+        SK_GZ_BAD("gzip inflate: workspace must be 16-byte aligned and hold sk_gzip_inflate_workspace_bytes(%llu, %llu) = %llu bytes",
+                  (unsigned long long)image_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
+#undef SK_GZ_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_gunzip(image, image_bytes, out, capacity, forced, workspace, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_gzip_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[SK_GUNZIP_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    memset(counts, 0, sizeof *counts);
+    counts->bytes_in = h[0];
+    counts->members = h[1];
+    counts->bytes_out = h[2];
+    counts->stretches = h[3];
+    counts->stretches_used = h[4];
+    const uint64_t key = h[6];
+    if (key != ~0ull) {
+        counts->error = (int32_t)(key & 7);
+        counts->error_member = key >> 3;
+        counts->error_offset = h[7];
+        set_error(ctx, "gzip inflate: member %llu is not valid gzip at byte %llu (reason %d)",
+                  (unsigned long long)counts->error_member, (unsigned long long)counts->error_offset, counts->error);
+        return SK_EDATA;
+    }
+    if (!h[5]) {
+        set_error(ctx, "gzip inflate: the text needs %llu bytes, more than the capacity", (unsigned long long)counts->bytes_out);
+        return SK_ESPACE;
+    }
+    return SK_OK;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

@@ -285,6 +285,46 @@ static inline void sk_inflate_layout_of(uint64_t image_bytes, sk_inflate_layout 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf_inflate(const uint8_t *image, uint64_t image_bytes,
                                                                                    uint8_t *out, uint64_t capacity,
                                                                                    void *workspace, hipStream_t stream);
+// Plain gzip read on the device (sk_gunzip.hip, sk_gunzip_block.h).  The caller's workspace (16-byte sections, sizes in
+// bytes, n = image bytes, S = ceil(n / chunk) stretches, chunk = sk_gunzip_chunk_of(n)):
+//   header    SK_GUNZIP_HDR_WORDS words
+//   stretches 128 per stretch, S + 1
+//   used      8 * (S + 1) text offsets and 4 * (S + 1) stretch numbers of the chain from bit 0
+//   members   32 per member end: n / 18 + 1 (two trailers lie 18 bytes apart at least)
+//   symbols   2 * capacity: the text as 16-bit symbols
+// The chunk: 32 KiB, doubled until 4096 chunks cover the image (the decode kernels' grids are 4096 single-wave
+// workgroups); SK_GZIP_CHUNK (a power of two of 256 or more) replaces it.
+#define SK_GUNZIP_HDR_WORDS 32u
+#define SK_GUNZIP_STRETCH_BYTES 128u
+#define SK_GUNZIP_MEMBER_BYTES 32u
+#define SK_GUNZIP_MIN_CHUNK 32768u
+#define SK_GUNZIP_GRID 4096u
+#define SK_GUNZIP_MAX_IMAGE (1ull << 33)
+struct sk_gunzip_layout {
+    uint64_t chunk, S, n_members, stretches, u_off, u_id, members, sym, total;
+};
+static inline uint64_t sk_gunzip_chunk_of(uint64_t image_bytes, uint64_t forced)
+{
+    if (forced) return forced;
+    uint64_t c = SK_GUNZIP_MIN_CHUNK;
+    while (c * SK_GUNZIP_GRID < image_bytes) c <<= 1;
+    return c;
+}
+static inline void sk_gunzip_layout_of(uint64_t image_bytes, uint64_t capacity, uint64_t forced_chunk, sk_gunzip_layout *L)
+{
+    L->chunk = sk_gunzip_chunk_of(image_bytes, forced_chunk);
+    L->S = image_bytes / L->chunk + (image_bytes % L->chunk != 0);
+    L->n_members = image_bytes / 18 + 1;
+    L->stretches = 8 * SK_GUNZIP_HDR_WORDS;
+    L->u_off = L->stretches + SK_GUNZIP_STRETCH_BYTES * (L->S + 1);
+    L->u_id = L->u_off + sk_inflate_a16(8 * (L->S + 1));
+    L->members = L->u_id + sk_inflate_a16(4 * (L->S + 1));
+    L->sym = L->members + (uint64_t)SK_GUNZIP_MEMBER_BYTES * L->n_members;
+    L->total = L->sym + sk_inflate_a16(2 * capacity);
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_gunzip(const uint8_t *image, uint64_t image_bytes, uint8_t *out,
+                                                                             uint64_t capacity, uint64_t forced_chunk,
+                                                                             void *workspace, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
