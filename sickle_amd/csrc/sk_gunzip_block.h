@@ -22,6 +22,9 @@
 #define SKG_PIECE 32768u             /* text bytes per CRC piece */
 #define SKG_MIN_GAP 18u              /* two members' trailers lie this far apart at least */
 #define SKG_TRY_CAP (4u << 20)       /* a guessed block that decodes more text than this is taken for nonsense */
+#ifndef SKG_REBASE_AT
+#define SKG_REBASE_AT (1u << 24)     /* skg_rebase moves the reader's base once s.in reaches this (a test harness lowers it) */
+#endif
 #define SKG_HDR_WORDS 32u
 #define SKG_H_BYTES_IN 0
 #define SKG_H_MEMBERS 1
@@ -145,7 +148,7 @@ SKD_FN uint64_t skg_bitpos(const skg_reader *r, const uint8_t *image) { return (
 // keeps s.in small; 8 bytes stay below it: the buffer's bytes, which a stored block's start is counted back over
 SKD_FN void skg_rebase(skg_reader *r, const uint8_t *image, uint64_t n)
 {
-    if (r->s.in < (1u << 24)) return;
+    if (r->s.in < SKG_REBASE_AT) return;
     const uint32_t in = r->s.in;
     skg_window_of(r, image, n, (uint64_t)(r->s.body - image) + in - 8);
     r->s.in = 8;

@@ -6,6 +6,7 @@ import json
 import os
 import shutil
 import subprocess
+import sys
 
 from fastq_util import parse_fastq
 from sickle_amd import synth
@@ -172,3 +173,12 @@ def check_embedded(binary, tmp, gpu):
         assert free[3] >= free[0] - (8 << 20), free  # the same run again: no growth
     assert rss[3] <= rss[0] + 96 * 1024, rss  # the same run again: the resident set does not creep (kB)
     return marks
+
+
+def soak_child(script, iterations, seed):
+    """A soak's slice in a process of its own (it sets SK_GZIP_CHUNK in its environment) -> its stats"""
+    env = {k: v for k, v in os.environ.items() if k != "SK_GZIP_CHUNK"}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", script), "--iterations", str(iterations), "--seed", str(seed)],
+                       capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0 and "soak ok: " in r.stdout, "%s: exit status %d\n%s%s" % (script, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return json.loads(r.stdout[r.stdout.rindex("soak ok: ") + 9:])

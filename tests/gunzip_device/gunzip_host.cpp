@@ -1,12 +1,18 @@
 // TEST INFRASTRUCTURE ONLY: sk_gunzip_block.h on the host.  Usage: gunzip_host <batch> <results> <texts>
+//                                                                 gunzip_host --shift <numbers> <results>
+//                                                                 gunzip_host --crc <buffer> <cut> <results>
 //   batch    records of: uint32 LE chunk bytes, uint32 LE length, then that many bytes of a gzip image
 //   results  one line per image: error member offset members bytes_out stretches stretches_used   (error: SK_GZ_*)
 //   texts    the texts of the images without an error, back to back
 // The stages run in the order of sk_gunzip.hip's launches, every unit of work in turn, lanes one after the other.  Every
 // image, `out` and every section of the workspace is an allocation of exactly its size, so a read or a write outside
 // them is a sanitizer report.  The capacity is what a counting pass reports, as Context.gunzip does it.
+// --shift: one decimal k per line of <numbers> -> one line each: skg_shift_of(power, k) after skg_crc_tables.
+// --crc: the CRC-32 of <buffer> as skg_crc_piece and skg_check_member assemble it from the spans [0, cut) and [cut, end).
+// The same source with -DSKG_REBASE_AT=64u is gunzip_host_rebase: the bit reader re-bases at every block and batch.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <vector>
 
@@ -16,12 +22,49 @@ static ski_shared sh;
 static skg_crc_shared cs;
 static skg_walk walk;
 
+static int shift_mode(const char *numbers, const char *results)
+{
+    FILE *in = fopen(numbers, "r"), *res = fopen(results, "w");
+    if (!in || !res) return 2;
+    unsigned long long k;
+    while (fscanf(in, "%llu", &k) == 1) fprintf(res, "%u\n", skg_shift_of(cs.power, k));
+    fclose(in);
+    fclose(res);
+    return 0;
+}
+
+static int crc_mode(const char *buffer, const char *cut_text, const char *results)
+{
+    FILE *in = fopen(buffer, "rb"), *res = fopen(results, "w");
+    if (!in || !res) return 2;
+    std::vector<uint8_t> data;
+    uint8_t block[65536];
+    for (size_t got; (got = fread(block, 1, sizeof block, in)) > 0;) data.insert(data.end(), block, block + got);
+    const uint64_t len = data.size(), cut = strtoull(cut_text, nullptr, 10);
+    if (cut > len || len > 0xffffffffull) return 2;
+    uint32_t acc = 0;
+    if (cut) {
+        SKI_ALL(skg_crc_span_lane(&cs, data.data(), (uint32_t)cut, len - cut, lane));
+        skg_crc_span_close(&cs, &acc);
+    }
+    if (len > cut) {
+        SKI_ALL(skg_crc_span_lane(&cs, data.data() + cut, (uint32_t)(len - cut), 0, lane));
+        skg_crc_span_close(&cs, &acc);
+    }
+    fprintf(res, "%u\n", ~(skb_mul(0xffffffffu, skg_shift_of(cs.power, len)) ^ acc));
+    fclose(in);
+    fclose(res);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    SKI_ALL(skg_crc_tables(&cs, lane));
+    if (argc == 4 && !strcmp(argv[1], "--shift")) return shift_mode(argv[2], argv[3]);
+    if (argc == 5 && !strcmp(argv[1], "--crc")) return crc_mode(argv[2], argv[3], argv[4]);
     if (argc != 4) return 2;
     FILE *in = fopen(argv[1], "rb"), *res = fopen(argv[2], "w"), *txt = fopen(argv[3], "wb");
     if (!in || !res || !txt) return 2;
-    SKI_ALL(skg_crc_tables(&cs, lane));
     SKI_ALL(ski_fixed_lengths(&sh, lane));
     const ski_build lit = ski_build_lit(&sh.fixed, 288), dist = ski_build_dist(&sh.fixed, 288, 32);
     SKI_BUILD(&sh, lit);

@@ -2,7 +2,9 @@
 walks the stream block by block (so it knows every block's first bit, which zlib does not tell), the reason codes and
 their order.  zlib is the decoder every valid text is held against (gunzip() asserts it).  And the test images: small_blocks()
 draws gzip whose blocks hold a few hundred symbols, images() the valid ones the CPU harness and the GPU tests share,
-bad_images() the damaged ones."""
+bad_images() the damaged ones, long_images() and long_bad_images() those beyond 16 MiB of image, beyond the guess's text
+cap and with thousands of members.  crc_shift() and crc_combine() are the CRC-32 algebra of the device's member check on
+Python integers."""
 import functools
 import gzip
 import struct
@@ -181,16 +183,16 @@ def block(r, out, floor, far):
             out += bytes(n)
         elif d >= n:
             out += out[len(out) - d:len(out) - d + n]
-        else:
-            for _ in range(n):
-                out.append(out[-d])
+        else:  # the copy overlaps itself: its d bytes repeat
+            out += (bytes(out[len(out) - d:]) * (n // d + 1))[:n]
 
 
-def walk(image):
+def walk(image, lengths=None):
     """The whole image -> (result dict, blocks): blocks is the list of (first bit, type, final, member) of every block that
-    decoded.  The failures: a header or truncation error or a block that does not decode stops the walk; a distance
-    before the member's first byte, a length unlike ISIZE and a CRC-32 unlike the trailer's are noted and the walk goes on.
-    The lowest (member, reason number) wins, for two of one member and reason the lower offset."""
+    decoded; a list given as `lengths` gets the text bytes of each of them.  The failures: a header or truncation error or
+    a block that does not decode stops the walk; a distance before the member's first byte, a length unlike ISIZE and a
+    CRC-32 unlike the trailer's are noted and the walk goes on.  The lowest (member, reason number) wins, for two of one
+    member and reason the lower offset."""
     n, pos, member = len(image), 0, 0
     out, blocks, errors = bytearray(), [], []
     while pos < n:
@@ -200,7 +202,7 @@ def walk(image):
             break
         r, floor, far_seen, stop = Reader(image, 8 * h[1]), len(out), False, False
         while True:
-            b, far = r.bit, [False]
+            b, far, before = r.bit, [False], len(out)
             try:
                 kind, final = block(r, out, floor, far)
             except Bad:
@@ -212,6 +214,8 @@ def walk(image):
                     far_seen = True
                     errors.append((member, DEFLATE, b >> 3))
             blocks.append((b, kind, final, member))
+            if lengths is not None:
+                lengths.append(len(out) - before)
             if final:
                 break
         if stop:
@@ -436,3 +440,151 @@ def big_images():
     small = small_blocks(mib)
     return {"fq1m_c4096": (small, mib, 4096), "fq1m_c1024": (small, mib, 1024), "fq1m_c256": (small, mib, 256),
             "fq5m_gzip1": (gzip.compress(five, 1), five, 0)}
+
+
+# ---- CRC-32 algebra: polynomials over GF(2) modulo the CRC-32 polynomial, reflected (bit 31 is x^0) --------------------
+POLY = 0xedb88320
+
+
+def _mul(a, b):
+    """a * b modulo the polynomial"""
+    p = 0
+    for i in range(31, -1, -1):  # a's coefficient of x^(31 - i)
+        if (a >> i) & 1:
+            p ^= b
+        b = (b >> 1) ^ POLY if b & 1 else b >> 1  # b * x
+    return p
+
+
+def crc_shift(k):
+    """x^(8 k) modulo the polynomial (1 is 0x80000000): what appending k bytes multiplies a CRC register by"""
+    r, p = 0x80000000, 0x00800000
+    while k:
+        if k & 1:
+            r = _mul(r, p)
+        p = _mul(p, p)
+        k >>= 1
+    return r
+
+
+def crc_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(a + b) from zlib.crc32(a), zlib.crc32(b) and len(b)"""
+    return _mul(crc_shift(len_b), crc_a) ^ crc_b
+
+
+# ---- the long images -----------------------------------------------------------------------------------------------
+def spliced_member(parts, head=None):
+    """One member of parts (text, level, strategy, mem_level): each its own raw deflate stream, all but the last ended by a
+    full flush (an empty stored block, behind which the next starts on a byte and with an empty window)"""
+    body = []
+    for i, (t, level, strategy, mem_level) in enumerate(parts):
+        c = zlib.compressobj(level, zlib.DEFLATED, -15, mem_level, strategy)
+        body.append(c.compress(t) + (c.flush(zlib.Z_FULL_FLUSH) if i + 1 < len(parts) else c.flush()))
+    text = b"".join(p[0] for p in parts)
+    image = (header() if head is None else head) + b"".join(body) + struct.pack("<II", zlib.crc32(text), len(text) & 0xffffffff)
+    assert gzip.decompress(image) == text
+    return image
+
+
+PAST16M_D = dict(zip("abcdefgh", (0, 1, 2, 3, 5, 8, 11, 15)))  # the stored run's length is (1 << 24) - 70000 + d
+LONG_RUN = 13 << 20
+
+
+@functools.lru_cache(maxsize=None)
+def long_images():
+    """name -> (image, text, chunk); chunk 0 is the default.  The texts are zlib's (asserted here)."""
+    rng = np.random.default_rng(16)
+    rnd = rng.integers(0, 256, 17 << 20, dtype=np.uint8).tobytes()
+    out = {}
+    tail = [(fastq_text(300000, 41), 6, 0, 1), (fastq_text(50000, 42), 6, zlib.Z_FIXED, 8), (rnd[-200000:], 0, 0, 8),
+            (fastq_text(300000, 43), 9, 0, 1)]
+    for letter, d in PAST16M_D.items():  # the bit reader's base moves inside the small dynamic blocks, at 8 alignments
+        parts = [(rnd[d:d + (1 << 24) - 70000 + d], 0, 0, 8)] + tail
+        out["past16m_" + letter] = (spliced_member(parts), b"".join(p[0] for p in parts), 1 << 25)
+    out["past16m_d_default"] = out["past16m_d"][:2] + (0,)
+    out["past16m_stored"] = (member(rnd, 0), rnd, 0)
+    fq = fastq_text(26 << 20, 44)
+    out["past16m_fixed"] = (member(fq, 6, zlib.Z_FIXED), fq, 0)
+    assert len(out["past16m_fixed"][0]) > 17 << 20
+    for mem_level in (8, 7):  # blocks of 16 383 and of 8 191 copies of 258 bytes: beyond the guess's text cap, and within
+        text = fastq_text(5000, 45) + b"A" * LONG_RUN + fastq_text(5000, 46)
+        image = member(text, 9, mem_level=mem_level)
+        over = long_blocks(image)
+        assert bool(over) == (mem_level == 8), (mem_level, over)
+        out["long_run_m%d" % mem_level] = (image, text, 256)
+    parts, texts, i = [member(b"")], [b""], 0
+    while len(parts) < 5900:  # runs of 1, 2, 63, 64 and 65 empty members between members of one byte and of 200
+        run = (1, 2, 63, 64, 65)[i % 5]
+        t = bytes([65 + i % 26]) if i % 2 else fastq_text(200, 300 + i)
+        parts += [member(b"")] * run + [member(t, mem_level=1)]
+        texts.append(t)
+        i += 1
+    parts += [member(b"")] * (6000 - len(parts))
+    image, text = b"".join(parts), b"".join(texts)
+    assert gzip.decompress(image) == text
+    out["empty_members_c256"] = (image, text, 256)
+    out["empty_members"] = (image, text, 0)
+    for name, (image, text, chunk) in out.items():
+        assert name.startswith("past16m") == (len(image) > 1 << 24), name
+    return out
+
+
+def long_blocks(image):
+    """The (first bit, text bytes) of the non-final dynamic blocks that hold more than 4 MiB of text"""
+    lengths = []
+    blocks = walk(image, lengths)[1]
+    return [(b[0], n) for b, n in zip(blocks, lengths) if b[1] == 2 and not b[2] and n > 4 << 20]
+
+
+LONG_MEMBERS = {"empty_members": 6000, "empty_members_c256": 6000}
+
+
+def long_want(name):
+    """What gunzip() says of long_images()[name], without the walk: its text is zlib's and its members are counted"""
+    image, text, _ = long_images()[name]
+    return dict(error=0, error_member=0, error_offset=0, members=LONG_MEMBERS.get(name, 1), bytes_out=len(text), text=text)
+
+
+@functools.lru_cache(maxsize=None)
+def long_bad_images():
+    """name -> (image, chunk, gunzip(image)): past16m_a with a bit flipped in a dynamic block beyond byte 2^24, with a
+    damaged CRC-32 and cut short"""
+    image = long_images()["past16m_a"][0]
+    at = next(b[0] for b in walk(image)[1] if b[0] > 8 * ((1 << 24) + 4096) and b[1] == 2) // 8 + 40
+    assert 1 << 24 < at < len(image) - 400000  # in the level 6 part
+    out = {"past16m_a_bit": image[:at] + bytes([image[at] ^ 4]) + image[at + 1:],
+           "past16m_a_crc": image[:-8] + bytes([image[-8] ^ 1]) + image[-7:],
+           "past16m_a_cut": image[:-100000]}
+    out = {name: (bad, 1 << 25, gunzip(bad)) for name, bad in out.items()}
+    assert [v[2]["error"] for v in out.values()] == [out["past16m_a_bit"][2]["error"], CRC, DEFLATE]
+    assert out["past16m_a_bit"][2]["error"] in (DEFLATE, CRC) and out["past16m_a_bit"][2]["error_offset"] in (0, at - 40)
+    return out
+
+
+SEGMENT = 4 << 20
+
+
+@functools.lru_cache(maxsize=None)
+def repeated_member(repeats, tail_bytes=70000):
+    """-> (image, segment text, tail text): one member whose text is the segment text `repeats` times, then the tail, built
+    without compressing more than one segment: a raw deflate stream ended by a full flush leaves the compressor as it
+    began, so the same text gives the same bytes again (asserted), and the image repeats them.  The segment is a random
+    period of 32 500 bytes behind a little FASTQ: copies of 258 bytes from 32 500 back, about 2 MiB of text a block.  The
+    trailer's CRC-32 is crc_combine's; ISIZE is the length modulo 2^32."""
+    rng = np.random.default_rng(77)
+    period = rng.integers(0, 256, 32500, dtype=np.uint8).tobytes()
+    seg_text = (fastq_text(300, 47) + period * (SEGMENT // 32500 + 1))[:SEGMENT]
+    tail_text = fastq_text(tail_bytes, 48)
+    c = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
+    seg = c.compress(seg_text) + c.flush(zlib.Z_FULL_FLUSH)
+    again = c.compress(seg_text) + c.flush(zlib.Z_FULL_FLUSH)
+    assert seg == again
+    tail = c.compress(tail_text) + c.flush()
+    c = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
+    assert tail == c.compress(tail_text) + c.flush()
+    crc, shift, seg_crc = 0, crc_shift(SEGMENT), zlib.crc32(seg_text)
+    for _ in range(repeats):
+        crc = _mul(shift, crc) ^ seg_crc
+    crc = crc_combine(crc, zlib.crc32(tail_text), tail_bytes)
+    image = header() + seg * repeats + tail + struct.pack("<II", crc, (repeats * SEGMENT + tail_bytes) & 0xffffffff)
+    return image, seg_text, tail_text

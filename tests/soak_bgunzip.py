@@ -8,6 +8,7 @@ text where the damage hit bytes nothing looks at.
 --dry runs the generator and the model only (no GPU): every valid image must also satisfy gzip.decompress."""
 import argparse
 import gzip
+import json
 import os
 import sys
 import zlib
@@ -18,6 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bgunzip_model as bm  # noqa: E402
 
+SLICE = (150, 1)  # (iterations, seed) of the slice the suite runs: tests/test_gpu_bgunzip.py, and dry in tests/test_bgunzip_model.py
+SLICE_STATS = dict(text=66, reasons={"1": 25, "2": 22, "3": 2, "4": 3, "5": 32})  # what the model says of it
 STRATEGIES = (zlib.Z_DEFAULT_STRATEGY, zlib.Z_FILTERED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE, zlib.Z_FIXED)
 
 
@@ -72,8 +75,20 @@ def damage(rng, image):
     return bytes(image)
 
 
-def run(iterations, seed, dry=False, verbose=True):
+def check_slice(stats, iterations):
+    """What a soak slice of the suite must draw: a third at least read to their text, a third at least end in an error,
+    and every reason code occurs"""
+    assert stats["text"] + sum(stats["reasons"].values()) == iterations
+    assert 3 * stats["text"] >= iterations and 3 * sum(stats["reasons"].values()) >= iterations, stats
+    assert sorted(stats["reasons"]) == ["1", "2", "3", "4", "5"], stats
+
+
+def run(iterations, seed, dry=False, verbose=True, stats=None):
+    """stats (a dict) gets: text, the iterations the model reads to their text; reasons, those it ends in each reason code;
+    stretches_used, the device's sum (0 in a dry run and for BGZF, which has none)"""
     rng = np.random.default_rng(seed)
+    stats = {} if stats is None else stats
+    stats.update(text=0, reasons={}, stretches_used=0)
     ctx = inflate = None
     if not dry:
         import torch
@@ -88,10 +103,15 @@ def run(iterations, seed, dry=False, verbose=True):
         if rng.integers(0, 2):
             image = damage(rng, image)
         want = bm.bgunzip(image)
+        shift = int(rng.integers(0, 16))  # drawn in a dry run too: the same images
+        if want["error"] == 0:
+            stats["text"] += 1
+        else:
+            stats["reasons"][str(want["error"])] = stats["reasons"].get(str(want["error"]), 0) + 1
         if dry:
             assert want["error"] != 0 or want["text"] is not None
         else:
-            rc, c, out = inflate(ctx, image, shift=int(rng.integers(0, 16)))
+            rc, c, out = inflate(ctx, image, shift=shift)
             if want["error"] == 0:
                 assert rc == 0 and text_of(out, c) == want["text"], (seed, it)
             else:
@@ -111,4 +131,6 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dry", action="store_true")
     a = ap.parse_args()
-    print("%d iterations passed" % run(a.iterations, a.seed, dry=a.dry))
+    st = {}
+    print("%d iterations passed" % run(a.iterations, a.seed, dry=a.dry, stats=st))
+    print("soak ok: " + json.dumps(st, sort_keys=True))

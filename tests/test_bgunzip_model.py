@@ -6,6 +6,7 @@ import zlib
 import pytest
 
 import bgunzip_model as bm
+import soak_bgunzip
 
 
 @pytest.fixture(scope="module")
@@ -71,3 +72,10 @@ def test_framing_damage_and_precedence():
             want = bm.bad_members()[name.split("@")[0]][1]
             at = {"0": 0, "1": 1, "last": 2}[name.split("@")[1]]
             assert (r["error"], r["error_member"]) == (want, at), name
+
+
+def test_soak_bgunzip_dry():
+    stats = {}
+    assert soak_bgunzip.run(*soak_bgunzip.SLICE, dry=True, verbose=False, stats=stats) == soak_bgunzip.SLICE[0]
+    soak_bgunzip.check_slice(stats, soak_bgunzip.SLICE[0])
+    assert {k: stats[k] for k in soak_bgunzip.SLICE_STATS} == soak_bgunzip.SLICE_STATS  # what the device run of the slice is held to

@@ -1,6 +1,6 @@
 """GPU: BGZF read on the device (sk_bgzf_inflate_device_async / finish, Context.bgunzip, Context.trim_gz) against zlib and
 tests/bgunzip_model.py: the project's own writer round trip, every kind of member zlib writes, many members, capacity, bad
-arguments, every reason code, and .gz in -> .gz out against the plain-text trim."""
+arguments, every reason code, .gz in -> .gz out against the plain-text trim, and a slice of tests/soak_bgunzip.py."""
 import ctypes as C
 import gzip
 
@@ -222,3 +222,12 @@ def test_trim_gz_single_end(sk_ctx, workdir):
     got, counts2 = sk_ctx.trim_gz(params, to_device(bm.bgzip(text, block=30000)), mode="se")
     assert counts2 == counts and got[1] is None and got[2] is None
     assert gzip.decompress(got[0].cpu().numpy().tobytes()) == want[0].cpu().numpy().tobytes()
+
+
+def test_bgunzip_soak():
+    """tests/soak_bgunzip.py's slice: what tests/test_bgunzip_model.py's dry run of it draws, on the device"""
+    import soak_bgunzip
+    stats = cu.soak_child("soak_bgunzip.py", *soak_bgunzip.SLICE)
+    print("soak_bgunzip slice:", stats)
+    soak_bgunzip.check_slice(stats, soak_bgunzip.SLICE[0])
+    assert {k: stats[k] for k in soak_bgunzip.SLICE_STATS} == soak_bgunzip.SLICE_STATS

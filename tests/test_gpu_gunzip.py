@@ -1,9 +1,12 @@
 """GPU: plain gzip read on the device (sk_gzip_inflate_device_async / finish, Context.gunzip, Context.trim_gz) against zlib,
 tests/gunzip_model.py and the host run of the same stages (tests/test_gunzip_host.py): every kind of member and header,
 images cut into one, a few and hundreds of stretches, the placeholder cases, many members, capacity, every reason code at
-member 0 and in a later stretch, bad arguments, and plain .gz in -> .gz out against the BGZF path."""
+member 0 and in a later stretch, bad arguments, and plain .gz in -> .gz out against the BGZF path.  Beyond the fixtures'
+sizes: images of more than 16 MiB read by one stretch, a guessed block beyond the text cap, 6 000 members, one member of
+more than 4 GiB of text, and a slice of tests/soak_gunzip.py."""
 import ctypes as C
 import gzip
+import struct
 
 import pytest
 
@@ -14,7 +17,7 @@ import trim_model as tm
 from bgzf_raw import SENTINEL, to_device, torch_mod, upload
 from sickle_amd import capi
 from test_fastq_api import golden_texts
-from test_gunzip_host import run_host, tool  # noqa: F401 (the fixture that builds the host harness)
+from test_gunzip_host import long_runs, run_host, tool  # noqa: F401 (the fixtures that build and run the host harness)
 
 pytestmark = pytest.mark.gpu
 GUARD = 64
@@ -213,3 +216,62 @@ def test_trim_gz_takes_plain_gzip(sk_ctx, tmp_path, monkeypatch):
             assert gzip.decompress(got[o].cpu().numpy().tobytes()) == gzip.decompress(want[o].cpu().numpy().tobytes()), (name, o)
     with pytest.raises(capi.GzDataError):
         sk_ctx.trim_gz(params, to_device(b"not gzip at all, not at all"), mode="se")
+
+
+# ---- 7 beyond the fixtures' sizes ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(gm.long_images()) + list(gm.long_bad_images()))
+def test_long_images(sk_ctx, monkeypatch, long_runs, name):  # noqa: F811
+    """The device against the host run of the same stages and against the model: one wavefront that reads 17 MiB and
+    re-bases its bit reader on the way (past16m_*, three walks each: search or count, decode), guesses beyond the cap
+    (long_run_*), 6 000 members with runs of empty ones, and the damaged past16m_a"""
+    host = long_runs[name]
+    if name in gm.long_images():
+        image, text, chunk = gm.long_images()[name]
+        rc, c, out = inflate(sk_ctx, image, shift=len(name) % 16, capacity=len(text), chunk=chunk, monkeypatch=monkeypatch)
+        assert rc == capi.SK_OK, (name, c)
+        assert {k: c[k] for k in ("stretches", "stretches_used", "members", "bytes_out")} == \
+            {k: host[k] for k in ("stretches", "stretches_used", "members", "bytes_out")}, name
+        assert c["members"] == gm.long_want(name)["members"] and text_of(out, c) == text, name
+    else:
+        image, chunk, want = gm.long_bad_images()[name]
+        rc, c, out = inflate(sk_ctx, image, shift=len(name) % 16, capacity=want["bytes_out"] + (1 << 20), chunk=chunk,
+                             monkeypatch=monkeypatch)
+        assert rc == capi.SK_EDATA, (name, c)
+        assert tuple(c[x] for x in KEYS) == tuple(want[x] for x in KEYS) == tuple(host[x] for x in KEYS), (name, c)
+        assert (c["stretches"], c["stretches_used"]) == (host["stretches"], host["stretches_used"]), name
+
+
+def test_text_beyond_4_gib_in_one_member(sk_ctx, monkeypatch, tool, tmp_path):  # noqa: F811
+    """(1 << 32) + 70 000 bytes of text in one member: 64-bit text offsets in the chain, the symbols, the resolve granules and
+    the CRC pieces; a shift of more than 2^32 bytes in the member's CRC-32; ISIZE modulo 2^32.  The text stays on the device."""
+    torch = torch_mod()
+    image3, seg, tail = gm.repeated_member(3)
+    host = run_host(tool, [(image3, 32768)], tmp_path)[0]  # the guesses hold: not one wavefront for the whole text
+    assert host["error"] == 0 and host["text"] == seg * 3 + tail and host["stretches_used"] > 3
+    image, seg, tail = gm.repeated_member(1024)
+    total = 1024 * gm.SEGMENT + len(tail)
+    assert total == (1 << 32) + 70000 and struct.unpack("<I", image[-4:])[0] == 70000
+    rc, c, out = inflate(sk_ctx, image, capacity=total, monkeypatch=monkeypatch)
+    assert rc == capi.SK_OK, c
+    assert (c["members"], c["bytes_out"], c["error"]) == (1, total, 0) and c["stretches_used"] > 1024
+    want = to_device(seg).repeat(64)  # 256 MiB
+    for k in range(16):
+        assert torch.equal(out[k * want.numel():(k + 1) * want.numel()], want), k
+    assert out[1 << 32:].cpu().numpy().tobytes() == tail
+    del out, want
+    torch.cuda.empty_cache()
+    for bad, reason in ((image[:-8] + bytes([image[-8] ^ 1]) + image[-7:], capi.SK_GZ_CRC),
+                        (image[:-4] + struct.pack("<I", 70001), capi.SK_GZ_LENGTH)):
+        rc, c, out = inflate(sk_ctx, bad, capacity=total, monkeypatch=monkeypatch)
+        assert rc == capi.SK_EDATA and (c["error"], c["error_member"], c["error_offset"]) == (reason, 0, 0), c
+        del out
+        torch.cuda.empty_cache()
+
+
+def test_gunzip_soak():
+    """tests/soak_gunzip.py's slice: what tests/test_gunzip_model.py's dry run of it draws, on the device"""
+    import soak_gunzip
+    stats = cu.soak_child("soak_gunzip.py", *soak_gunzip.SLICE)
+    print("soak_gunzip slice:", stats)
+    soak_gunzip.check_slice(stats, soak_gunzip.SLICE[0])
+    assert {k: stats[k] for k in soak_gunzip.SLICE_STATS} == soak_gunzip.SLICE_STATS
