@@ -381,6 +381,87 @@ int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fa
 /* Waits for hip_stream and fills *counts: SK_OK, SK_EFORMAT, SK_ERANGE or SK_ESPACE (in this order of precedence). */
 int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts);
 
+/*
+ * The same trim with the records in the order the reference writes them at -a T (its default T is the machine's hardware
+ * concurrency), so the outputs are byte-identical to its files for any T, not only -a 1.  Everything said above holds
+ * (framing, checks, read numbers, the pair rule, the record format, capacities, "nothing is written on an error"), except
+ * for what follows.  This comment is the normative text of the rule.
+ *
+ * Lines and units.  A line ends at '\n'; len(line) does not count it.  m = 4 lines (SK_TRIM_SE, SK_TRIM_PE_SPLIT) or 8
+ * (SK_TRIM_PE_INTERLEAVED), L = order->batch_len.  The unit of ordering is a read (SE) or a pair (both PE modes).
+ * Batches (the reference's reader, src/GZReader.cpp:59-132), per input text, on line numbers.  Start with a = c = 0, then:
+ *   1. if c is already the number of lines the input has ended, and the current set is the carried lines [a, c);
+ *   2. else e = the smallest line number > c with sum(len(lines[a:e])) >= L; without one e = the number of lines and the
+ *      input has ended;
+ *   3. the batch is lines [a, e - (e - a) % m);
+ *   4. an empty batch ends the run;
+ *   5. else a = the batch's end, c = e; go on unless the input has ended.
+ * Lines left over at the end are dropped.  SK_TRIM_PE_SPLIT cuts both texts with the same L and stops before the first
+ * batch index at which one text has no batch or the two batches differ in their line count (stopped_on_mismatch; the
+ * reference's "Batch2 and Batch1 have different lengths", which exits 0 after writing what came before).  With
+ * batch_limit != 0 only the first batch_limit batches exist.  Records behind the last batch do not exist for the call:
+ * they are not checked, not scanned, so no format or range error comes from them, and not emitted; they are counted in
+ * records_unbatched (the odd record of an interleaved text is one of them: dropped_unpaired is 0 in ordered calls, and
+ * SK_FQ_PAIR_COUNT never occurs).
+ * Order.  Batches go in input order.  Inside a batch of n units, with T = order->threads and k the unit's number in the
+ * batch: SE writes the units with k % T == T - 1 first, then residues 0, 1, .., T - 2 (src/trim_single.cpp:263-298); PE
+ * writes residues 0, 1, .., T - 1 (src/trim_paired.cpp:388-403,530-567); k ascends inside a residue.  The pair rule routes
+ * the kept reads as above; each output is that order filtered by its destination.  record_index gets the read numbers
+ * (as above) in emission order.  T = 1 is read order.
+ * Lines gzgets would split.  The reference reads with gzgets(file, buf, L), which splits a line of L - 1 bytes or more;
+ * that is not reproduced.  If ANY line of an input is that long -- the lines of records behind the last batch and the
+ * lines after the last complete record included, so the rare text whose only such line lies behind the point where the
+ * reference stops is refused too -- finish returns SK_ELONGLINE with long_line_input = the lowest input that has one
+ * and long_line = its lowest such line (0-based); nothing is written, the order counts are filled, records[] and bytes[]
+ * are 0.
+ * Unterminated last line.  Parity with the reference is claimed for texts that end in '\n'.  A last line without one
+ * ends at the end of the text, as above (the reference's reader drops its last character).
+ *
+ * The workspace: sk_trim_fastq_ordered_workspace_bytes(text_bytes, trunc_n, batch_capacity), with text_bytes = bytes[0] +
+ * bytes[1], is sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + 8 (batch_capacity + 1) rounded up to 16.  The number
+ * of batches depends on the text: a batch usually holds about batch_len bytes, fewer when long carried lines use the
+ * budget up.  A caller starts at, say, batch_capacity = text_bytes / batch_len + 16 and calls again with a larger table
+ * when it was too small: finish then returns SK_ESPACE with batches = batch_capacity + 1 ("more than") and nothing
+ * written.  max(bytes[0], bytes[1]) / 4 + 2 always suffices (a batch holds four lines at least).  The walk stops at a full
+ * table, so the one serial loop of the call is bounded by batch_capacity + 1 steps of about 32 dependent loads per input.
+ * Same discipline as sk_trim_fastq_device_async: only kernels are enqueued, all state lives in the workspace, finish is
+ * the only call that waits, nothing is written on any error, and sk_trim_fastq_output_words works on this workspace.
+ * finish returns, in this order of precedence: SK_ELONGLINE, SK_ESPACE for the batch table, SK_EFORMAT, SK_ERANGE,
+ * SK_ESPACE for the outputs, SK_OK.  Bad arguments (those of sk_trim_fastq_device_async; order NULL, threads 0, reserved
+ * != 0, batch_len < 20, batch_capacity 0 or beyond 2^40) return SK_EINVAL and enqueue nothing.
+ */
+enum { SK_ELONGLINE = -8 }; /* sk_trim_fastq_ordered_device_finish: a line of batch_len - 1 bytes or more (counts say where) */
+
+typedef struct {
+    uint32_t threads;        /* -a T, >= 1 */
+    uint32_t reserved;       /* 0 */
+    uint64_t batch_len;      /* GZReader's byte budget, >= 20 (the caller computes it from the file size) */
+    uint64_t batch_capacity; /* entries of the batch table in the workspace, >= 1 */
+    uint64_t batch_limit;    /* 0 = none; else only the first batch_limit batches exist for the call */
+} sk_fastq_order;
+
+typedef struct {
+    uint64_t batches;             /* batches trimmed (after the PE stop and batch_limit) */
+    uint64_t units;               /* reads (SE) or pairs in them */
+    uint64_t last_batch_units;    /* what the PE summary's "Total input FastQ records" is made from */
+    uint64_t records_unbatched[2];/* complete records of each input behind the last batch */
+    uint32_t stopped_on_mismatch; /* PE split: the two inputs' batches differed in line count */
+    uint32_t long_line_input;     /* with SK_ELONGLINE: which input, and */
+    uint64_t long_line;           /*   its lowest line of batch_len - 1 bytes or more */
+    uint64_t error_batch;         /* batch of the record behind SK_EFORMAT / SK_ERANGE, else UINT64_MAX */
+} sk_fastq_order_counts;
+
+size_t sk_trim_fastq_ordered_workspace_bytes(uint64_t text_bytes, int32_t trunc_n, uint64_t batch_capacity); /* pure */
+int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                                       const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace,
+                                       size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills both counts (order_counts may be NULL). */
+int sk_trim_fastq_ordered_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                        sk_fastq_order_counts *order_counts);
+/* *first_unit_dev = the device table of the call that used `workspace`: batches + 1 entries, batch b holds units
+ * [t[b], t[b + 1]), valid once the call's kernels have run.  No device access, no wait. */
+int sk_trim_fastq_ordered_batches(void *workspace, const uint64_t **first_unit_dev);
+
 /* Measurement aid (bench.py's second roofline denominator): streams `bytes` of device memory at
  * dev_buf through a read-only kernel (16-byte nt loads, nothing written) `launches` times on
  * hip_stream and returns the average rate in GB/s, timed with HIP events on that stream. */

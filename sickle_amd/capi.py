@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsickle_amd.so")
 
 SK_OK, SK_ERANGE, SK_EINVAL, SK_ENODEV, SK_EHIP, SK_EBUSY, SK_ESPACE, SK_EFORMAT, SK_EDATA = 0, 1, -1, -2, -3, -4, -5, -6, -7
+SK_ELONGLINE = -8  # sk_trim_fastq_ordered_device_finish: a line the reference's reader would split
 # why a BGZF image is not valid (sk_bgzf_inflate_device_finish)
 SK_GZ_OK, SK_GZ_HEADER, SK_GZ_TRUNCATED, SK_GZ_DEFLATE, SK_GZ_LENGTH, SK_GZ_CRC = range(6)
 # why a FASTQ record is malformed (sk_trim_fastq_device_finish), in the order the reference checks
@@ -30,7 +31,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_device_async",
            "sk_bgzf_device_finish", "sk_bgzf_inflate_workspace_bytes", "sk_bgzf_inflate_device_async",
            "sk_bgzf_inflate_device_finish", "sk_gzip_inflate_workspace_bytes", "sk_gzip_inflate_device_async",
-           "sk_gzip_inflate_device_finish")
+           "sk_gzip_inflate_device_finish", "sk_trim_fastq_ordered_workspace_bytes", "sk_trim_fastq_ordered_device_async",
+           "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches")
 SK_BGZF_EOF = 1
 
 
@@ -108,6 +110,23 @@ class FastqCounts(C.Structure):
                 "range": (int(self.range.read), int(self.range.pos), int(self.range.ch))}
 
 
+class FastqOrder(C.Structure):
+    _fields_ = [("threads", C.c_uint32), ("reserved", C.c_uint32), ("batch_len", C.c_uint64),
+                ("batch_capacity", C.c_uint64), ("batch_limit", C.c_uint64)]
+
+
+class FastqOrderCounts(C.Structure):
+    _fields_ = [("batches", C.c_uint64), ("units", C.c_uint64), ("last_batch_units", C.c_uint64),
+                ("records_unbatched", C.c_uint64 * 2), ("stopped_on_mismatch", C.c_uint32), ("long_line_input", C.c_uint32),
+                ("long_line", C.c_uint64), ("error_batch", C.c_uint64)]
+
+    def as_dict(self):
+        return {"batches": int(self.batches), "units": int(self.units), "last_batch_units": int(self.last_batch_units),
+                "records_unbatched": list(self.records_unbatched), "stopped_on_mismatch": int(self.stopped_on_mismatch),
+                "long_line_input": int(self.long_line_input), "long_line": int(self.long_line),
+                "error_batch": int(self.error_batch)}
+
+
 class BgzfInput(C.Structure):
     _fields_ = [("text", C.c_void_p), ("bytes", C.c_uint64), ("bytes_dev", C.c_void_p), ("valid_dev", C.c_void_p)]
 
@@ -167,6 +186,15 @@ class FormatError(SickleError):
     def __init__(self, reason, input, record, counts=None):
         super().__init__("malformed FASTQ record %d of input %d (reason %d)" % (record, input, reason))
         self.reason, self.input, self.record, self.counts = reason, input, record, counts
+
+
+class LongLineError(SickleError):
+    """sk_trim_fastq_ordered_device_finish returned SK_ELONGLINE: line `line` of input `input` has batch_len - 1 bytes or
+    more, which the reference's reader would split."""
+
+    def __init__(self, input, line, counts=None):
+        super().__init__("line %d of input %d is as long as the batch budget" % (line, input))
+        self.input, self.line, self.counts = input, line, counts
 
 
 class RangeError(SickleError):
@@ -252,6 +280,17 @@ def lib():
                                                  C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
         L.sk_trim_fastq_device_finish.restype = C.c_int
         L.sk_trim_fastq_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts)]
+        L.sk_trim_fastq_ordered_workspace_bytes.restype = C.c_size_t
+        L.sk_trim_fastq_ordered_workspace_bytes.argtypes = [C.c_uint64, C.c_int32, C.c_uint64]
+        L.sk_trim_fastq_ordered_device_async.restype = C.c_int
+        L.sk_trim_fastq_ordered_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput), C.c_int,
+                                                         C.POINTER(FastqOrder), C.POINTER(FastqOutput), C.c_void_p,
+                                                         C.c_size_t, C.c_void_p]
+        L.sk_trim_fastq_ordered_device_finish.restype = C.c_int
+        L.sk_trim_fastq_ordered_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts),
+                                                          C.POINTER(FastqOrderCounts)]
+        L.sk_trim_fastq_ordered_batches.restype = C.c_int
+        L.sk_trim_fastq_ordered_batches.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.sk_trim_fastq_output_words.restype = C.c_int
         L.sk_trim_fastq_output_words.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sk_bgzf_bound.restype = C.c_uint64
@@ -475,22 +514,96 @@ class Context:
         self._check(rc, c.range)
         return c.as_dict()
 
-    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False):
+    def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
+                                        mode="se", max_read_len=0, stream=None):
+        """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
+        trim_fastq_device_async."""
+        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bytes) + [0] * (2 - len(text_bytes))
+        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
+        arr = (FastqOutput * 3)(*list(outs)[:3])
+        self._check(lib().sk_trim_fastq_ordered_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
+                                                             C.byref(order), arr, workspace_ptr, workspace_bytes, stream))
+
+    def trim_fastq_ordered_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_fastq_ordered_device_finish -> counts (dict, with the order counts under "order"); raises
+        LongLineError, FormatError, RangeError or TrimError (SK_ESPACE: the batch table when counts["order"]["batches"]
+        is batch_capacity + 1, else an output)."""
+        c, oc = FastqCounts(), FastqOrderCounts()
+        rc = lib().sk_trim_fastq_ordered_device_finish(self._h, workspace_ptr, stream, C.byref(c), C.byref(oc))
+        counts = dict(c.as_dict(), order=oc.as_dict())
+        if rc == SK_ELONGLINE:
+            raise LongLineError(int(oc.long_line_input), int(oc.long_line), counts)
+        if rc == SK_EFORMAT:
+            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
+        self._check(rc, c.range)
+        return counts
+
+    @staticmethod
+    def trim_fastq_ordered_batches(workspace_ptr):
+        """sk_trim_fastq_ordered_batches -> the device address of the table of first units (batches + 1 entries)."""
+        t = C.c_void_p()
+        if lib().sk_trim_fastq_ordered_batches(workspace_ptr, C.byref(t)) != SK_OK:
+            raise SickleError("sk_trim_fastq_ordered_batches: bad arguments")
+        return t.value
+
+    @staticmethod
+    def _order_tables(order, sizes):
+        """order = (threads, batch_len) -> the FastqOrder of the first call, and of the second one if the first one's
+        table was too small: a batch holds four lines at least, so an input of b bytes has b / 4 + 1 batches at most."""
+        threads, batch_len = order
+        return [FastqOrder(threads, 0, batch_len, cap, 0) for cap in (sum(sizes) // batch_len + 16, max(sizes) // 4 + 2)]
+
+    def _with_batch_table(self, order, sizes, call):
+        """call(FastqOrder or None); once more with the larger table if the first one was too small"""
+        if order is None:
+            return call(None)
+        first, second = self._order_tables(order, sizes)
+        try:
+            return call(first)
+        except TrimError as e:
+            if e.rc != SK_ESPACE or e.counts["order"]["batches"] != first.batch_capacity + 1 or \
+                    second.batch_capacity <= first.batch_capacity:
+                raise
+        return call(second)
+
+    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
         record_index=True a pair (text, index) with the read number of each record (int64).  Raises FormatError,
-        RangeError or TrimError."""
+        RangeError or TrimError.
+        order=(threads, batch_len): the records in the order the reference writes them at -a threads with its reader's
+        byte budget batch_len (sk_trim_fastq_ordered_device_async); counts then has the order counts under "order", and
+        LongLineError may be raised.  A batch table that was too small shows in the count-only pass, which is then
+        repeated once with the larger table; the writing pass runs once, with the table that fitted, so nothing is
+        written twice.  order=None: read order, the -a 1 order."""
+        if order is not None:
+            sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
+            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
+                                                                                  record_index, o))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None)
+
+    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        if order is None:
+            ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        else:
+            ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        run = lambda outs: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                         max_read_len=max_read_len, stream=stream),
-                            self.trim_fastq_device_finish(ws.data_ptr(), stream))[1]
+        if order is None:
+            run = lambda outs: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                                             max_read_len=max_read_len, stream=stream),
+                                self.trim_fastq_device_finish(ws.data_ptr(), stream))[1]
+        else:
+            run = lambda outs: (self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes,
+                                                                     mode=mode, max_read_len=max_read_len, stream=stream),
+                                self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[1]
         counts = run([FastqOutput() for _ in range(3)])
         used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
         bufs, outs = [None] * 3, [FastqOutput() for _ in range(3)]
@@ -539,17 +652,27 @@ class Context:
                                stream=stream)
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
-    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0):
+    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (a trimmed text never exceeds them by more than one
         newline each), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
-        only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises."""
+        only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
+        trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more)."""
+        if order is not None:
+            sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
+            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None)
+
+    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        if order is None:
+            ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
+        else:
+            ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
         cap = sum(sizes) + 2
@@ -558,8 +681,12 @@ class Context:
         for o in used:
             trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
             outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
-        self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                     max_read_len=max_read_len, stream=stream)
+        if order is None:
+            self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                         max_read_len=max_read_len, stream=stream)
+        else:
+            self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                                 max_read_len=max_read_len, stream=stream)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -568,7 +695,7 @@ class Context:
                                    eof=True, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream)
         sizes_out = [None if images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
                      for o in range(3)]
-        counts = self.trim_fastq_device_finish(ws.data_ptr(), stream)
+        counts = (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
         return tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3)), counts
 
     # ---- BGZF read on the device --------------------------------------------------------------
@@ -649,14 +776,14 @@ class Context:
                 raise
         return self.gunzip(image)
 
-    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0):
+    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device: bgunzip (gunzip for plain gzip), then trim_fastq_gz.  The one host wait in between is the text's
         length, which sk_fastq_input takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what
-        it raises."""
+        it raises.  order: as trim_fastq's (the reference takes batch_len from the compressed file's size)."""
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
-        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len)
+        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):

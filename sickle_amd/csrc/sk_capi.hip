@@ -14,6 +14,7 @@
 
 #include "sickle_amd.h"
 #include "sk_device.h"
+#include "sk_fastq_order.h"
 
 static_assert(sizeof(sk_tile) == sizeof(sk_tile_dev) && sizeof(sk_tile) == 24, "sk_tile layout");
 
@@ -756,8 +757,10 @@ size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n)
     return (size_t)L.total;
 }
 
-int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
-                               const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
+namespace {
+// the argument checks of both FASTQ calls; extra = what an ordered call's batch table adds to the workspace
+int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in, int mode,
+                     const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, size_t extra)
 {
 #define SK_FQ_BAD(...)                \
     do {                              \
@@ -765,7 +768,7 @@ int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fa
         return SK_EINVAL;             \
     } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!params || !in || !out) SK_FQ_BAD("sk_trim_fastq_device_async: params, in and out are required");
+    if (!params || !in || !out) SK_FQ_BAD("%s: params, in and out are required", who);
     if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_FQ_BAD("trim mode %d is unknown", mode);
     const bool split = mode == SK_TRIM_PE_SPLIT;
     if (split && !in->text[1]) SK_FQ_BAD("fastq: SK_TRIM_PE_SPLIT needs text[1]");
@@ -779,16 +782,29 @@ int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fa
     const uint64_t T = in->bytes[0] + (split ? in->bytes[1] : 0);
     if (sk_fq_pack_reads(in->bytes[0], split ? in->bytes[1] : 0, mode) >= (1ull << 32))
         SK_FQ_BAD("fastq: %llu bytes of text is beyond what one call takes", (unsigned long long)T);
-    const size_t need = sk_trim_fastq_workspace_bytes(T, params->trunc_n);
+    const size_t need = sk_trim_fastq_workspace_bytes(T, params->trunc_n) + extra;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_FQ_BAD("fastq: workspace must be 16-byte aligned and hold sk_trim_fastq_workspace_bytes(%llu, %d) = %zu bytes",
-                  (unsigned long long)T, params->trunc_n, need);
+        SK_FQ_BAD("fastq: workspace must be 16-byte aligned and hold sk_trim_fastq%s_workspace_bytes(%llu, %d%s) = %zu bytes",
+                  extra ? "_ordered" : "", (unsigned long long)T, params->trunc_n, extra ? ", batch_capacity" : "", need);
 #undef SK_FQ_BAD
+    return SK_OK;
+}
+} // namespace
+
+namespace {
+// both FASTQ calls; order: NULL = read order
+int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in, int mode,
+                const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                void *hip_stream)
+{
+    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
+                              order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
+    if (rc != SK_OK) return rc;
     sk_scan_args chk;
     const uint64_t no_reads = 0;
     sk_batch probe = {};
     probe.offsets = &no_reads; // an empty `offsets` batch: only params is checked
-    int rc = make_args(ctx, params, &probe, &chk); // the parameter checks of the scan, before anything is enqueued
+    rc = make_args(ctx, params, &probe, &chk); // the parameter checks of the scan, before anything is enqueued
     if (rc != SK_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     unsigned long long *d_err, *h_err;
@@ -797,14 +813,23 @@ int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fa
     SK_HIP(ctx, hipSetDevice(ctx->device));
     sk_batch packed;
     sk_cut_dev *cuts;
-    SK_HIP(ctx, sk_launch_fastq_front(in, mode, params->trunc_n, workspace, ctx->cu_count, stream, &packed, &cuts));
+    SK_HIP(ctx, sk_launch_fastq_front(in, mode, params->trunc_n, order, workspace, ctx->cu_count, stream, &packed, &cuts));
     rc = sk_scan_device_async(ctx, params, &packed, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, out, workspace, d_err, ctx->cu_count, stream));
+    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, order, out, workspace, d_err, ctx->cu_count, stream));
     return SK_OK;
 }
+} // namespace
 
-int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts)
+int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                               const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return fastq_async(ctx, "sk_trim_fastq_device_async", params, in, mode, nullptr, out, workspace, workspace_bytes, hip_stream);
+}
+
+namespace {
+// finish of both FASTQ calls
+int fastq_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts, sk_fastq_order_counts *oc, bool ordered)
 {
     if (!ctx || !workspace || !counts) return SK_EINVAL;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -824,11 +849,37 @@ int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, 
         counts->tail_lines[i] = h[SK_FQ_H_LINES + i] & 3;
     }
     const uint64_t fmt = h[SK_FQ_H_FMT];
-    const bool bad = fmt != ~0ull, split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
-    counts->dropped_unpaired = h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
+    const bool split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
+    const bool refused = ordered && (h[SK_FQO_H_LONG] != ~0ull || h[SK_FQO_H_OVERFLOW]);
+    const bool bad = fmt != ~0ull || refused;
+    counts->dropped_unpaired = !ordered && h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
     for (int o = 0; o < 3; ++o) {
         counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
         counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
+    }
+    if (oc) {
+        *oc = sk_fastq_order_counts{};
+        oc->batches = h[SK_FQO_H_BATCHES];
+        oc->units = h[SK_FQO_H_UNITS];
+        oc->last_batch_units = h[SK_FQO_H_LAST_UNITS];
+        oc->records_unbatched[0] = h[SK_FQO_H_UNBATCHED];
+        oc->records_unbatched[1] = h[SK_FQO_H_UNBATCHED + 1];
+        oc->stopped_on_mismatch = (uint32_t)h[SK_FQO_H_MISMATCH];
+        oc->error_batch = refused ? UINT64_MAX : h[SK_FQO_H_ERROR_BATCH];
+    }
+    if (ordered && h[SK_FQO_H_LONG] != ~0ull) {
+        const uint64_t key = h[SK_FQO_H_LONG];
+        if (oc) {
+            oc->long_line_input = (uint32_t)(key >> 63);
+            oc->long_line = key & ~(1ull << 63);
+        }
+        set_error(ctx, "fastq: input %u, line %llu has batch_len - 1 bytes or more", (unsigned)(key >> 63),
+                  (unsigned long long)(key & ~(1ull << 63)));
+        return SK_ELONGLINE;
+    }
+    if (ordered && h[SK_FQO_H_OVERFLOW]) {
+        set_error(ctx, "fastq: the text has more batches than batch_capacity");
+        return SK_ESPACE;
     }
     if (bad) {
         const uint64_t read = fmt >> 3;
@@ -848,6 +899,44 @@ int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, 
         if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
     if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
     return rc;
+}
+} // namespace
+
+int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts)
+{
+    return fastq_finish(ctx, workspace, hip_stream, counts, nullptr, false);
+}
+
+size_t sk_trim_fastq_ordered_workspace_bytes(uint64_t text_bytes, int32_t trunc_n, uint64_t batch_capacity)
+{
+    return sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + (size_t)sk_fq_order_shift(batch_capacity);
+}
+
+int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                                       const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace,
+                                       size_t workspace_bytes, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+    if (!order || order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN ||
+        order->batch_capacity == 0 || order->batch_capacity > (1ull << 40)) {
+        set_error(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
+        return SK_EINVAL;
+    }
+    return fastq_async(ctx, "sk_trim_fastq_ordered_device_async", params, in, mode, order, out, workspace, workspace_bytes,
+                       hip_stream);
+}
+
+int sk_trim_fastq_ordered_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                        sk_fastq_order_counts *order_counts)
+{
+    return fastq_finish(ctx, workspace, hip_stream, counts, order_counts, true);
+}
+
+int sk_trim_fastq_ordered_batches(void *workspace, const uint64_t **first_unit_dev)
+{
+    if (!workspace || !first_unit_dev) return SK_EINVAL;
+    *first_unit_dev = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(workspace) + SK_FQO_TABLE_BYTES_AT);
+    return SK_OK;
 }
 
 int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t **bytes_dev, const uint64_t **written_dev)

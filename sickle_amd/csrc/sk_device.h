@@ -188,10 +188,16 @@ static inline void sk_fq_layout_of(uint64_t text_bytes, int trunc_n, sk_fq_layou
     L->seq = L->qual + Q;
     L->total = L->seq + (trunc_n ? Q : 0);
 }
+// Ordered calls (sk_trim_fastq_ordered_device_async, sk_fastq_order.h): the same header (its words 21.. are theirs), then
+// the table of first units (8 * (batch_capacity + 1), rounded up to 16), then the sections above, shifted by the table.
+static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * (batch_capacity + 1) + 15) & ~15ull; }
+// order: NULL = read order (sk_trim_fastq_device_async)
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                  void *workspace, int cu_count, hipStream_t stream,
+                                                                                  const sk_fastq_order *order, void *workspace,
+                                                                                  int cu_count, hipStream_t stream,
                                                                                   sk_batch *packed, sk_cut_dev **cuts);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                 const sk_fastq_order *order,
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
+#include "sk_fastq_order.h"
 
 namespace {
 
@@ -743,6 +744,233 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int
 }
 
 // ------------------------------------------------------------------------------------------
+// ordered calls (sk_trim_fastq_ordered_device_async): the reference's batches and -a T order, sk_fastq_order.h
+//   frame 1-3 as above, then  O1 chain  one lane walks the batches: the table of first units, the counts, NREAL
+//                             O2 check  the records inside the batches; every line of every text against batch_len - 1
+//   pack 5-8 and the scan as above (reads stay in read order), then
+//   emit  O3 count / O4 scan / O5 place  as 9-11, but over emission ranks: a lane owns FQ_PER_THREAD consecutive ranks
+//         and maps each to its read; 12 gather as above (a.emit holds (output offset, read) in rank order)
+// ------------------------------------------------------------------------------------------
+struct fq_order {
+    uint64_t *tab; // capacity + 1 first units
+    uint64_t capacity, batch_len, limit;
+    uint32_t threads;
+};
+
+// lines of text i the descriptor table holds (all of them, but for a text with a malformed record among its first
+// slots[i] records: sk_device.h)
+__device__ __forceinline__ uint64_t fq_order_lines(const fq_args &a, int i)
+{
+    return min(a.hdr[SK_FQ_H_LINES + i], 4 * a.slots[i]);
+}
+
+__global__ void __launch_bounds__(64) sk_fq_order_chain_kernel(fq_args a, fq_order o)
+{
+    if (threadIdx.x != 0) return;
+    uint64_t *h = a.hdr;
+    const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
+    const uint64_t *const desc[2] = {a.desc[0], a.desc[1]};
+    const uint64_t nl[2] = {fq_order_lines(a, 0), n_in == 2 ? fq_order_lines(a, 1) : 0};
+    fqo_chain_result r;
+    fqo_chain(desc, nl, n_in, a.mode == SK_TRIM_PE_INTERLEAVED ? 8u : 4u, o.batch_len, o.capacity, o.limit, o.tab, &r);
+    h[SK_FQO_H_BATCHES] = r.overflow ? o.capacity + 1 : r.batches;
+    h[SK_FQO_H_UNITS] = r.units;
+    h[SK_FQO_H_LAST_UNITS] = r.last_units;
+    h[SK_FQO_H_UNBATCHED] = h[SK_FQ_H_RECORDS] - r.batched_lines[0] / 4;
+    h[SK_FQO_H_UNBATCHED + 1] = n_in == 2 ? h[SK_FQ_H_RECORDS + 1] - r.batched_lines[1] / 4 : 0;
+    h[SK_FQO_H_MISMATCH] = r.mismatch;
+    h[SK_FQO_H_OVERFLOW] = r.overflow;
+    h[SK_FQO_H_LONG] = ~0ull;
+    h[SK_FQO_H_ERROR_BATCH] = ~0ull;
+    h[SK_FQ_H_FMT] = ~0ull; // records without a mate are behind the last batch: no verdict
+    // a table that was too small trims nothing; more reads than the packed batch holds only with a malformed record
+    // inside the batches (sk_device.h)
+    h[SK_FQ_H_NREAL] = r.overflow ? 0 : min(r.units * (a.mode == SK_TRIM_SE ? 1u : 2u), a.n_pack);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_check_kernel(fq_args a, fq_order o)
+{
+    const uint64_t *h = a.hdr;
+    const uint64_t nl[2] = {fq_order_lines(a, 0), a.mode == SK_TRIM_PE_SPLIT ? fq_order_lines(a, 1) : 0};
+    const uint64_t n0 = (nl[0] + 3) / 4, n1 = (nl[1] + 3) / 4; // records with a line, the last one maybe incomplete
+    const uint64_t inside = h[SK_FQO_H_UNITS] * (a.mode == SK_TRIM_PE_INTERLEAVED ? 2u : 1u); // records per input
+    uint64_t best = ~0ull, longest = ~0ull;
+    for (uint64_t g = (uint64_t)blockIdx.x * FQ_THREADS + threadIdx.x; g < n0 + n1; g += (uint64_t)gridDim.x * FQ_THREADS) {
+        const int i = g < n0 ? 0 : 1;
+        const uint64_t r = g - (i ? n0 : 0);
+        const uint64_t *d = a.desc[i] + 5 * r;
+        const uint64_t have = min(nl[i] - 4 * r, (uint64_t)4);
+        uint64_t start = d[0], e[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((uint64_t)k < have) {
+                e[k] = d[1 + k];
+                if (e[k] - start + 1 >= o.batch_len) longest = min(longest, ((uint64_t)i << 63) | (4 * r + k));
+                start = e[k] + 1;
+            }
+        if (r >= inside) continue;
+        const uint64_t s0 = d[0], name = e[0] - s0, seq = e[1] - e[0] - 1, qual = e[3] - e[2] - 1;
+        uint64_t why = SK_FQ_OK;
+        if (name <= 1) why = SK_FQ_ID_SHORT;
+        else if (a.text[i][s0] != '@') why = SK_FQ_ID_NO_AT;
+        else if (seq == 0) why = SK_FQ_SEQ_EMPTY;
+        else if (qual == 0) why = SK_FQ_QUAL_EMPTY;
+        else if (qual != seq) why = SK_FQ_LENGTHS;
+        else if (qual > SK_MAX_READ_LEN_DEV) why = SK_FQ_TOO_LONG;
+        if (why != SK_FQ_OK) {
+            const uint64_t read = a.mode == SK_TRIM_PE_SPLIT ? 2 * r + i : r;
+            best = min(best, (read << 3) | why);
+        }
+    }
+    if (best != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.hdr + SK_FQ_H_FMT), (unsigned long long)best);
+    if (longest != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.hdr + SK_FQO_H_LONG), (unsigned long long)longest);
+}
+
+// the reads at the lane's FQ_PER_THREAD consecutive ranks from `first` (even): mates share a pair rank, so they stay
+// neighbours.  Ranks at or beyond n_real get ~0.
+__device__ __forceinline__ void fq_order_reads(const fq_args &a, const fq_order &o, uint64_t first, uint64_t n_real,
+                                               uint64_t (&reads)[FQ_PER_THREAD])
+{
+    const uint64_t batches = a.hdr[SK_FQO_H_BATCHES];
+    if (a.mode == SK_TRIM_SE) {
+        fqo_lane_units<FQ_PER_THREAD>(o.tab, batches, o.threads, true, first, n_real, reads);
+    } else {
+        uint64_t pairs[FQ_PER_THREAD / 2];
+        fqo_lane_units<FQ_PER_THREAD / 2>(o.tab, batches, o.threads, false, first >> 1, n_real >> 1, pairs);
+#pragma unroll
+        for (int j = 0; j < FQ_PER_THREAD; ++j) reads[j] = pairs[j >> 1] == ~0ull ? ~0ull : 2 * pairs[j >> 1] + (j & 1);
+    }
+}
+
+// fq_emit_load at the mapped reads
+__device__ __forceinline__ void fq_order_emit_load(const fq_args &a, const uint64_t (&reads)[FQ_PER_THREAD], bool bad,
+                                                   fq_emit_read (&rd)[FQ_PER_THREAD])
+{
+    bool kept[FQ_PER_THREAD];
+    sk_cut_dev c[FQ_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        c[j] = {-1, -1};
+        if (!bad && reads[j] < a.n_pack) c[j] = a.cuts[reads[j]];
+        kept[j] = c[j].three >= 0;
+    }
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        rd[j].dest = fq_dest(a.mode, kept[j], kept[j ^ 1], j & 1);
+        rd[j].bytes = 0;
+        if (rd[j].dest >= 0) {
+            const fq_rec x = fq_record(a, reads[j]);
+            rd[j].bytes = (x.e0 - x.s0 + 1) + (x.e2 - x.e1) + 2 * (uint64_t)(c[j].three - c[j].five + 1);
+        }
+    }
+}
+
+// nothing is trimmed after a format error, a line gzgets would split or a table that was too small
+__device__ __forceinline__ bool fq_order_bad(const uint64_t *h)
+{
+    return h[SK_FQ_H_FMT] != ~0ull || h[SK_FQO_H_LONG] != ~0ull || h[SK_FQO_H_OVERFLOW] != 0;
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_args a, fq_order o)
+{
+    __shared__ uint64_t lds[4 * 6];
+    const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    const bool bad = fq_order_bad(a.hdr);
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    uint64_t reads[FQ_PER_THREAD];
+    fq_emit_read rd[FQ_PER_THREAD];
+    fq_order_reads(a, o, first, bad ? 0 : n_real, reads);
+    fq_order_emit_load(a, reads, bad, rd);
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (rd[j].dest == k) {
+                v[k] += 1;
+                v[3 + k] += rd[j].bytes;
+            }
+    fq_block_scan<6>(v, tot, lds);
+    if (threadIdx.x < 6) {
+        uint64_t x = 0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x = threadIdx.x == k ? tot[k] : x; // no runtime index into tot[]
+        a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS + threadIdx.x] = x;
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_scan_kernel(fq_args a, fq_order o)
+{
+    __shared__ uint64_t lds[4 * 6];
+    uint64_t run[6];
+    fq_scan_blocks<6>(a, run, lds);
+    const unsigned long long range = *a.errword;
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        const fq_out &out = a.out[k];
+        const bool ok = !fq_order_bad(a.hdr) && range == ~0ull;
+        const uint64_t recs = k == 0 ? run[0] : k == 1 ? run[1] : run[2], bytes = k == 0 ? run[3] : k == 1 ? run[4] : run[5];
+        const bool produced = out.text != nullptr;
+        const bool fit = produced && ok && bytes <= out.cap && (!out.index || recs <= out.rec_cap);
+        a.hdr[SK_FQ_H_OUT_RECORDS + k] = recs;
+        a.hdr[SK_FQ_H_OUT_BYTES + k] = bytes;
+        a.hdr[SK_FQ_H_PRODUCED + k] = produced;
+        a.hdr[SK_FQ_H_FIT + k] = fit;
+        if (k == 0) a.hdr[SK_FQ_H_RANGE] = range;
+    }
+    if (threadIdx.x == 3) { // the batch of the record behind the error finish will report
+        const uint64_t fmt = a.hdr[SK_FQ_H_FMT], units = a.hdr[SK_FQO_H_UNITS];
+        uint64_t read = ~0ull;
+        if (fmt != ~0ull) read = fmt >> 3;
+        else if (range != ~0ull) read = range >> 32;
+        const uint64_t unit = a.mode == SK_TRIM_SE ? read : read >> 1;
+        if (read != ~0ull && unit < units && !a.hdr[SK_FQO_H_OVERFLOW])
+            a.hdr[SK_FQO_H_ERROR_BATCH] = fqo_batch_of(o.tab, a.hdr[SK_FQO_H_BATCHES], unit);
+    }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_args a, fq_order o)
+{
+    __shared__ uint64_t lds[4 * 6];
+    const uint64_t *h = a.hdr;
+    const bool fit[3] = {h[SK_FQ_H_FIT] != 0, h[SK_FQ_H_FIT + 1] != 0, h[SK_FQ_H_FIT + 2] != 0};
+    if (!fit[0] && !fit[1] && !fit[2]) return; // uniform
+    const uint64_t n_real = h[SK_FQ_H_NREAL];
+    const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
+    uint64_t reads[FQ_PER_THREAD];
+    fq_emit_read rd[FQ_PER_THREAD];
+    fq_order_reads(a, o, first, n_real, reads);
+    fq_order_emit_load(a, reads, false, rd);
+    uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (rd[j].dest == k) {
+                v[k] += 1;
+                v[3 + k] += rd[j].bytes;
+            }
+    fq_block_scan<6>(v, tot, lds);
+    const uint64_t *blk = a.blk + blockIdx.x * SK_FQ_BLOCK_WORDS;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] += blk[k];
+    const uint64_t dbase[3] = {0, h[SK_FQ_H_OUT_RECORDS], h[SK_FQ_H_OUT_RECORDS] + h[SK_FQ_H_OUT_RECORDS + 1]};
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (rd[j].dest == k) {
+                const uint64_t at = v[k], b = v[3 + k];
+                v[k] += 1;
+                v[3 + k] += rd[j].bytes;
+                if (!fit[k]) continue;
+                a.emit[2 * (dbase[k] + at)] = b;
+                a.emit[2 * (dbase[k] + at) + 1] = reads[j];
+                if (a.out[k].index) a.out[k].index[at] = reads[j];
+            }
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
@@ -752,12 +980,13 @@ uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
     return (span + SK_FQ_CHUNK_BYTES - 1) / SK_FQ_CHUNK_BYTES;
 }
 
+// shift: bytes between the header and the sections (an ordered call's batch table lies there)
 void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fastq_output *out, void *workspace,
-                  const unsigned long long *errword, fq_args &a)
+                  const unsigned long long *errword, fq_args &a, uint64_t shift = 0)
 {
     sk_fq_layout L;
     sk_fq_layout_of(in->bytes[0] + (mode == SK_TRIM_PE_SPLIT ? in->bytes[1] : 0), trunc_n, &L);
-    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    uint8_t *ws = static_cast<uint8_t *>(workspace) + shift;
     const int n_in = mode == SK_TRIM_PE_SPLIT ? 2 : 1;
     for (int i = 0; i < 2; ++i) {
         a.text[i] = i < n_in ? in->text[i] : nullptr;
@@ -769,7 +998,7 @@ void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fast
     a.trunc_n = trunc_n ? 1 : 0;
     a.n_pack = sk_fq_pack_reads(a.bytes[0], a.bytes[1], mode);
     a.n_blocks = (a.n_pack + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
-    a.hdr = reinterpret_cast<uint64_t *>(ws);
+    a.hdr = static_cast<uint64_t *>(workspace);
     a.chunks = reinterpret_cast<uint64_t *>(ws + L.chunks);
     a.desc[0] = reinterpret_cast<uint64_t *>(ws + L.desc);
     a.desc[1] = a.desc[0] + 5 * a.slots[0];
@@ -788,17 +1017,33 @@ void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fast
 
 } // namespace
 
+namespace {
+fq_order fq_make_order(const sk_fastq_order *order, void *workspace)
+{
+    return {reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(workspace) + SK_FQO_TABLE_BYTES_AT), order->batch_capacity,
+            order->batch_len, order->batch_limit, order->threads};
+}
+} // namespace
+
+// order: NULL = read order; else the batch chain and its check take the place of the check of every record
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                  void *workspace, int cu_count, hipStream_t stream,
+                                                                                  const sk_fastq_order *order, void *workspace,
+                                                                                  int cu_count, hipStream_t stream,
                                                                                   sk_batch *packed, sk_cut_dev **cuts)
 {
     fq_args a;
-    fq_make_args(in, mode, trunc_n, nullptr, workspace, nullptr, a);
+    fq_make_args(in, mode, trunc_n, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
     const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
     if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
     if (nc) hipLaunchKernelGGL(sk_fq_frame_lines_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(sk_fq_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a);
+    if (order) {
+        const fq_order o = fq_make_order(order, workspace);
+        hipLaunchKernelGGL(sk_fq_order_chain_kernel, dim3(1), dim3(64), 0, stream, a, o);
+        hipLaunchKernelGGL(sk_fq_order_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a, o);
+    } else {
+        hipLaunchKernelGGL(sk_fq_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a);
+    }
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_pack_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
@@ -814,15 +1059,24 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
 }
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
+                                                                                 const sk_fastq_order *order,
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream)
 {
     fq_args a;
-    fq_make_args(in, mode, trunc_n, out, workspace, errword, a);
-    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(sk_fq_emit_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
-    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    fq_make_args(in, mode, trunc_n, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
+    if (order) {
+        const fq_order o = fq_make_order(order, workspace);
+        if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_emit_count_kernel, blocks, threads, 0, stream, a, o);
+        hipLaunchKernelGGL(sk_fq_order_emit_scan_kernel, dim3(1), threads, 0, stream, a, o);
+        if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_emit_place_kernel, blocks, threads, 0, stream, a, o);
+    } else {
+        if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_count_kernel, blocks, threads, 0, stream, a);
+        hipLaunchKernelGGL(sk_fq_emit_scan_kernel, dim3(1), threads, 0, stream, a);
+        if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_place_kernel, blocks, threads, 0, stream, a);
+    }
     hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
     return hipGetLastError();
 }
