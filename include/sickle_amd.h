@@ -506,8 +506,22 @@ const char *sk_bgzf_last_error(void);
  * sk_bgzf_device_finish is the only call that waits.  Two calls in flight need two workspaces.  Bad arguments (NULL ctx or
  * in, unknown flags, text NULL with bytes != 0, out NULL with capacity != 0, out or workspace not 16-byte aligned, bytes_dev
  * or valid_dev not 8-byte aligned, a short workspace) return SK_EINVAL and enqueue nothing.
+ *
+ * SK_BGZF_SEARCH: a data block's body is the deflate stream of the SEARCHING encoder instead: next to the copies from the
+ * line four lines up and the runs it takes matches of 5 bytes or more that a hash table over the block finds (4-byte
+ * hashes, 2048 buckets of 4 ways, at most 32 768 back, never across a line's end), so the image of real reads is smaller
+ * and the call slower.  The image is a function of the text alone, as without the flag.  Everything else above holds as
+ * it stands: the stored-block rule, the framing, CRC-32 and ISIZE, sk_bgzf_bound, the counts, bytes_dev / valid_dev, the
+ * SK_ESPACE rule.  The workspace is larger by one candidate word per text byte of each block in flight:
+ *   sk_bgzf_workspace_bytes_flags(text_bytes, flags) = sk_bgzf_workspace_bytes(text_bytes)
+ *                                                      + (flags & SK_BGZF_SEARCH ? 261152 min(NB, 1280) : 0)
+ * and a workspace shorter than that, passed with the flag, is SK_EINVAL.  A workspace may serve calls with and without
+ * the flag in turn.
  */
-enum { SK_BGZF_EOF = 1 }; /* flags: close the image with the 28-byte empty end-of-file member */
+enum {
+    SK_BGZF_EOF = 1,   /* flags: close the image with the 28-byte empty end-of-file member */
+    SK_BGZF_SEARCH = 2 /* encode the data blocks with the match search */
+};
 
 typedef struct {
     const uint8_t *text;       /* device, ANY alignment */
@@ -523,6 +537,7 @@ typedef struct {
 
 uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags); /* worst-case image size; pure, no device */
 size_t sk_bgzf_workspace_bytes(uint64_t text_bytes);    /* pure, no device */
+size_t sk_bgzf_workspace_bytes_flags(uint64_t text_bytes, int flags); /* pure, no device; what a call with `flags` needs */
 int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uint64_t capacity, int flags, void *workspace,
                          size_t workspace_bytes, void *hip_stream);
 /* Waits for hip_stream and fills *counts from the workspace: SK_OK, or SK_ESPACE (the image is beyond the capacity). */

@@ -28,12 +28,13 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_count_pairs_device_async", "sk_count_pairs_device_finish", "sk_bgzf_deflate", "sk_bgzf_host_alloc", "sk_bgzf_host_free",
            "sk_bgzf_last_error", "sk_trim_workspace_bytes", "sk_trim_device_async", "sk_trim_device_finish",
            "sk_trim_fastq_workspace_bytes", "sk_trim_fastq_device_async", "sk_trim_fastq_device_finish",
-           "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_device_async",
+           "sk_trim_fastq_output_words", "sk_bgzf_bound", "sk_bgzf_workspace_bytes", "sk_bgzf_workspace_bytes_flags", "sk_bgzf_device_async",
            "sk_bgzf_device_finish", "sk_bgzf_inflate_workspace_bytes", "sk_bgzf_inflate_device_async",
            "sk_bgzf_inflate_device_finish", "sk_gzip_inflate_workspace_bytes", "sk_gzip_inflate_device_async",
            "sk_gzip_inflate_device_finish", "sk_trim_fastq_ordered_workspace_bytes", "sk_trim_fastq_ordered_device_async",
            "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches")
 SK_BGZF_EOF = 1
+SK_BGZF_SEARCH = 2
 
 
 class Params(C.Structure):
@@ -297,6 +298,8 @@ def lib():
         L.sk_bgzf_bound.argtypes = [C.c_uint64, C.c_int]
         L.sk_bgzf_workspace_bytes.restype = C.c_size_t
         L.sk_bgzf_workspace_bytes.argtypes = [C.c_uint64]
+        L.sk_bgzf_workspace_bytes_flags.restype = C.c_size_t
+        L.sk_bgzf_workspace_bytes_flags.argtypes = [C.c_uint64, C.c_int]
         L.sk_bgzf_device_async.restype = C.c_int
         L.sk_bgzf_device_async.argtypes = [C.c_void_p, C.POINTER(BgzfInput), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                            C.c_size_t, C.c_void_p]
@@ -623,11 +626,13 @@ class Context:
 
     # ---- BGZF on the device -------------------------------------------------------------------
     def bgzf_device_async(self, text_ptr, text_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, eof=True,
-                          bytes_dev_ptr=None, valid_dev_ptr=None, stream=None):
-        """sk_bgzf_device_async on raw device pointers: text_bytes is the text's length, or with bytes_dev_ptr its bound."""
+                          bytes_dev_ptr=None, valid_dev_ptr=None, stream=None, search=False):
+        """sk_bgzf_device_async on raw device pointers: text_bytes is the text's length, or with bytes_dev_ptr its bound.
+        search: SK_BGZF_SEARCH (the workspace then holds sk_bgzf_workspace_bytes_flags bytes)."""
         inp = BgzfInput(text_ptr, text_bytes, bytes_dev_ptr, valid_dev_ptr)
-        self._check(lib().sk_bgzf_device_async(self._h, C.byref(inp), out_ptr, capacity, SK_BGZF_EOF if eof else 0,
-                                               workspace_ptr, workspace_bytes, stream))
+        flags = (SK_BGZF_EOF if eof else 0) | (SK_BGZF_SEARCH if search else 0)
+        self._check(lib().sk_bgzf_device_async(self._h, C.byref(inp), out_ptr, capacity, flags, workspace_ptr, workspace_bytes,
+                                               stream))
 
     def bgzf_device_finish(self, workspace_ptr, stream=None):
         """sk_bgzf_device_finish -> counts (dict); raises TrimError (with .counts) on SK_ESPACE."""
@@ -638,32 +643,34 @@ class Context:
         self._check(rc)
         return c.as_dict()
 
-    def bgzf(self, text, eof=True):
+    def bgzf(self, text, eof=True, search=False):
         """Text in device memory (a uint8 torch tensor) -> its BGZF image (a uint8 tensor, a valid .gz file as it stands),
-        on the current stream."""
+        on the current stream.  search: encode with the match search (SK_BGZF_SEARCH): a smaller image, a slower call."""
         import torch
         dev, n = text.device, text.numel()
         stream = torch.cuda.current_stream(dev).cuda_stream
         cap = lib().sk_bgzf_bound(n, SK_BGZF_EOF if eof else 0)
-        ws_bytes = lib().sk_bgzf_workspace_bytes(n)
+        ws_bytes = lib().sk_bgzf_workspace_bytes_flags(n, SK_BGZF_SEARCH if search else 0)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
         self.bgzf_device_async(text.data_ptr() if n else None, n, out.data_ptr(), cap, ws.data_ptr(), ws_bytes, eof=eof,
-                               stream=stream)
+                               stream=stream, search=search)
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
-    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None):
+    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (a trimmed text never exceeds them by more than one
         newline each), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
-        trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more)."""
+        trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
+        as bgzf's."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
-            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None)
+            return self._with_batch_table(order, sizes,
+                                          lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o, search))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search)
 
-    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order):
+    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -676,7 +683,8 @@ class Context:
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
         cap = sum(sizes) + 2
-        bound, zws_bytes = lib().sk_bgzf_bound(cap, SK_BGZF_EOF), lib().sk_bgzf_workspace_bytes(cap)
+        bound = lib().sk_bgzf_bound(cap, SK_BGZF_EOF)
+        zws_bytes = lib().sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
         outs, trimmed, images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
         for o in used:
             trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
@@ -692,7 +700,7 @@ class Context:
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
             nbytes, written = self.trim_fastq_output_words(ws.data_ptr(), o)
             self.bgzf_device_async(trimmed[o].data_ptr(), cap, images[o].data_ptr(), bound, zws[o].data_ptr(), zws_bytes,
-                                   eof=True, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream)
+                                   eof=True, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream, search=search)
         sizes_out = [None if images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
                      for o in range(3)]
         counts = (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
@@ -776,14 +784,15 @@ class Context:
                 raise
         return self.gunzip(image)
 
-    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None):
+    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device: bgunzip (gunzip for plain gzip), then trim_fastq_gz.  The one host wait in between is the text's
         length, which sk_fastq_input takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what
-        it raises.  order: as trim_fastq's (the reference takes batch_len from the compressed file's size)."""
+        it raises.  order: as trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as
+        bgzf's."""
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
-        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order)
+        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):

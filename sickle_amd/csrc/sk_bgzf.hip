@@ -10,10 +10,15 @@
 //             trailer to the member's offset.  The offsets have any byte alignment, so the body goes out as aligned 16-byte
 //             stores built from aligned 16-byte loads funnel-shifted by v_alignbyte; the few granules at a member's ends,
 //             which it shares with its neighbours, are written byte by byte.
-// The workspace (caller's, device) holds the header, the table, the token scratch and the slots: sk_device.h.
+// With SK_BGZF_SEARCH launch 1 is sk_bgzf_search_block_kernel instead (sk_bgzf_search.hip: a file of its own, so that the
+// code of the kernel here does not depend on it): the same phases around the tokenizer of sk_bgzf_search.h, which also
+// takes matches that a hash table in LDS finds.
+// The workspace (caller's, device) holds the header, the table, the token scratch and the slots, and behind them the
+// search's candidate scratch: sk_device.h.
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
+#include "sk_bgzf_args.h"
 #include "sk_bgzf_block.h"
 
 typedef unsigned bz_u4 __attribute__((ext_vector_type(4)));
@@ -25,29 +30,6 @@ static_assert(SK_BGZF_BLOCK == SKD_BLOCK_MAX && SK_BGZF_SLOT == 4 * SKD_OUT_WORD
               "the workspace layout follows sk_deflate_block.h");
 static_assert(SK_BGZF_MEMBER_EXTRA == SKB_HEADER_BYTES + SKB_STORED_BYTES + SKB_TRAILER_BYTES && SK_BGZF_EOF_BYTES == SKB_EOF_BYTES,
               "sk_bgzf_bound follows sk_bgzf_block.h");
-
-struct bz_args {
-    const uint8_t *text;
-    uint64_t bytes; // the length, or its bound
-    const uint64_t *bytes_dev, *valid_dev;
-    uint8_t *out;
-    uint64_t capacity;
-    int32_t flags;
-    uint64_t *hdr;
-    sk_bgzf_entry *table;
-    uint32_t *tokens, *slots;
-};
-
-// the text's length: never beyond the bound the launches and the workspace were sized by
-__device__ __forceinline__ uint64_t bz_length(const bz_args &a)
-{
-    uint64_t n = a.bytes;
-    if (a.bytes_dev) n = min(n, *a.bytes_dev);
-    if (a.valid_dev && *a.valid_dev == 0) n = 0;
-    return n;
-}
-
-__device__ __forceinline__ uint64_t bz_blocks(uint64_t n) { return (n + SK_BGZF_BLOCK - 1) / SK_BGZF_BLOCK; }
 
 // ------------------------------------------------------------------------------------------
 // 1 block: deflate, CRC-32, verdict
@@ -238,7 +220,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf(const
     a.table = reinterpret_cast<sk_bgzf_entry *>(ws + L.table);
     a.tokens = reinterpret_cast<uint32_t *>(ws + L.tokens);
     a.slots = reinterpret_cast<uint32_t *>(ws + L.slots);
-    if (L.grid) hipLaunchKernelGGL(sk_bgzf_block_kernel, dim3((unsigned)L.grid), dim3(SKD_LANES), 0, stream, a);
+    if (L.grid && (flags & SK_BGZF_SEARCH))
+        sk_launch_bgzf_search_block(&a, reinterpret_cast<uint32_t *>(ws + L.total), (unsigned)L.grid, stream);
+    else if (L.grid)
+        hipLaunchKernelGGL(sk_bgzf_block_kernel, dim3((unsigned)L.grid), dim3(SKD_LANES), 0, stream, a);
     hipLaunchKernelGGL(sk_bgzf_scan_kernel, dim3(1), dim3(BZ_THREADS), 0, stream, a);
     const uint64_t pack_grid = L.n_blocks < (uint64_t)cu_count * BZ_PACK_WG_PER_CU ? L.n_blocks : (uint64_t)cu_count * BZ_PACK_WG_PER_CU;
     hipLaunchKernelGGL(sk_bgzf_pack_kernel, dim3((unsigned)(pack_grid ? pack_grid : 1)), dim3(BZ_THREADS), 0, stream, a);

@@ -962,6 +962,13 @@ size_t sk_bgzf_workspace_bytes(uint64_t text_bytes)
     return (size_t)L.total;
 }
 
+size_t sk_bgzf_workspace_bytes_flags(uint64_t text_bytes, int flags)
+{
+    sk_bgzf_layout L;
+    sk_bgzf_layout_of(text_bytes, &L);
+    return (size_t)(L.total + ((flags & SK_BGZF_SEARCH) ? sk_bgzf_search_bytes(&L) : 0));
+}
+
 int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uint64_t capacity, int flags, void *workspace,
                          size_t workspace_bytes, void *hip_stream)
 {
@@ -972,17 +979,17 @@ int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uin
     } while (0)
     if (!ctx) return SK_EINVAL;
     if (!in) SK_BGZF_BAD("sk_bgzf_device_async: in is required");
-    if (flags & ~SK_BGZF_EOF) SK_BGZF_BAD("bgzf: flags %d are unknown", flags);
+    if (flags & ~(SK_BGZF_EOF | SK_BGZF_SEARCH)) SK_BGZF_BAD("bgzf: flags %d are unknown", flags);
     if (!in->text && in->bytes) SK_BGZF_BAD("bgzf: text is NULL with %llu bytes", (unsigned long long)in->bytes);
     if ((reinterpret_cast<uintptr_t>(in->bytes_dev) | reinterpret_cast<uintptr_t>(in->valid_dev)) & 7)
         SK_BGZF_BAD("bgzf: bytes_dev and valid_dev must be 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(out) & 15) SK_BGZF_BAD("bgzf: out must be 16-byte aligned");
     if (!out && capacity) SK_BGZF_BAD("bgzf: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
     if (in->bytes > (1ull << 60)) SK_BGZF_BAD("bgzf: %llu bytes of text is beyond what one call takes", (unsigned long long)in->bytes);
-    const size_t need = sk_bgzf_workspace_bytes(in->bytes);
+    const size_t need = sk_bgzf_workspace_bytes_flags(in->bytes, flags);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_BGZF_BAD("bgzf: workspace must be 16-byte aligned and hold sk_bgzf_workspace_bytes(%llu) = %zu bytes",
-                    (unsigned long long)in->bytes, need);
+        SK_BGZF_BAD("bgzf: workspace must be 16-byte aligned and hold sk_bgzf_workspace_bytes_flags(%llu, %d) = %zu bytes",
+                    (unsigned long long)in->bytes, flags, need);
 #undef SK_BGZF_BAD
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_bgzf(in, out, capacity, flags, workspace, ctx->cu_count, static_cast<hipStream_t>(hip_stream)));

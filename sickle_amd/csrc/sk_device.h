@@ -207,6 +207,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
 //   table     16 per block: body bytes (bit 31: stored), CRC-32, the member's offset in the image
 //   tokens    4 * SK_BGZF_TOK_WORDS per workgroup of the block kernel: one token per text byte of the block in flight
 //   slots     65536 per block: its deflate stream
+//   cand      with SK_BGZF_SEARCH only, behind everything else (at sk_bgzf_layout.total): 4 * SK_BGZF_TOK_WORDS per
+//             workgroup of the block kernel, the search's candidate match for each text byte of the block in flight
 // The grid is a constant, not the device's CU count: the size must not depend on a device (5 workgroups per CU by LDS on
 // the 256 CUs of an MI355X; on fewer CUs the surplus workgroups wait their turn).
 #define SK_BGZF_BLOCK 65280u
@@ -237,6 +239,7 @@ static inline void sk_bgzf_layout_of(uint64_t text_bytes, sk_bgzf_layout *L)
     L->slots = L->tokens + 4ull * SK_BGZF_TOK_WORDS * L->grid;
     L->total = L->slots + (uint64_t)SK_BGZF_SLOT * L->n_blocks;
 }
+static inline uint64_t sk_bgzf_search_bytes(const sk_bgzf_layout *L) { return 4ull * SK_BGZF_TOK_WORDS * L->grid; }
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf(const sk_bgzf_input *in, uint8_t *out, uint64_t capacity,
                                                                            int flags, void *workspace, int cu_count,
                                                                            hipStream_t stream);

@@ -7,6 +7,10 @@ On the FASTQ texts of tools/fastq_trim_rates.py (made on the device), per config
             (what Context.trim_fastq_gz does): GB/s of input text
   host      with --baseline: sk_bgzf_deflate (host pointers, pinned; copies both ways and waits) on the first
             --baseline-mb MB of the same text, wall clock, run between the two above on the same box
+  --search  instead of all the above: the call without a flag and the call with SK_BGZF_SEARCH in turn on the same text,
+            workspace and stream, one of each per iteration, so that both see the same state of the machine: their times,
+            the spread of the no-flag call (it is the yardstick: the same kernel as before the search existed), the ratio
+            of the medians and the image / text ratio of each
 Per-kernel times come from a separate run under `rocprofv3 --kernel-trace --stats`.  One JSON line per configuration."""
 import argparse
 import json
@@ -47,6 +51,37 @@ def run_bgzf(ctx, capi, torch, text, iters):
     return {"bgzf_median_ms": round(med, 3), "bgzf_min_ms": round(lo, 3), "bgzf_GBps": round(n / med / 1e6, 2),
             "bgzf_blocks": counts["blocks"], "bgzf_stored": counts["stored_blocks"], "bgzf_ratio": round(counts["bytes_out"] / n, 4),
             "bgzf_workspace_bytes": wsb}
+
+
+def run_search(ctx, capi, torch, text, iters):
+    L = capi.lib()
+    n = text.numel()
+    cap, wsb = L.sk_bgzf_bound(n, capi.SK_BGZF_EOF), L.sk_bgzf_workspace_bytes_flags(n, capi.SK_BGZF_SEARCH)
+    out = torch.empty(cap, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms, counts = {False: [], True: []}, {}
+
+    def once(search, keep):
+        e0.record()
+        ctx.bgzf_device_async(text.data_ptr(), n, out.data_ptr(), cap, ws.data_ptr(), wsb, search=search)
+        e1.record()
+        counts[search] = ctx.bgzf_device_finish(ws.data_ptr())
+        if keep:
+            ms[search].append(e0.elapsed_time(e1))
+
+    for i in range(3 + iters):
+        once(False, i >= 3)
+        once(True, i >= 3)
+    res = {"search_workspace_bytes": wsb}
+    for search, key in ((False, "noflag"), (True, "search")):
+        t = sorted(ms[search])
+        med = t[len(t) // 2]
+        res.update({key + "_median_ms": round(med, 3), key + "_min_ms": round(t[0], 3), key + "_max_ms": round(t[-1], 3),
+                    key + "_GBps": round(n / med / 1e6, 2), key + "_ratio": round(counts[search]["bytes_out"] / n, 4),
+                    key + "_stored": counts[search]["stored_blocks"]})
+    res["search_over_noflag"] = round(res["search_median_ms"] / res["noflag_median_ms"], 3)
+    return res
 
 
 def run_chain(ctx, capi, torch, texts, mode, trunc_n, iters):
@@ -112,6 +147,7 @@ def main():
     ap.add_argument("--baseline", action="store_true", help="also time the host-pointer sk_bgzf_deflate on the same text")
     ap.add_argument("--baseline-mb", type=int, default=480)
     ap.add_argument("--no-chain", action="store_true")
+    ap.add_argument("--search", action="store_true", help="the no-flag call and the SK_BGZF_SEARCH call in turn, nothing else")
     args = ap.parse_args()
     import torch
     torch.cuda.is_available()
@@ -129,6 +165,13 @@ def main():
         texts = [make_text(torch, n, lo, hi, seed) for n, lo, hi, seed in specs]
         whole = texts[0] if len(texts) == 1 else torch.cat(texts)
         res = {"config": name, "mode": mode, "trunc_n": bool(trunc_n), "text_bytes": whole.numel()}
+        if args.search:
+            res.update(run_search(ctx, capi, torch, whole, args.iters))
+            print(json.dumps(res), flush=True)
+            lines.append(res)
+            del whole, texts
+            torch.cuda.empty_cache()
+            continue
         res.update(run_bgzf(ctx, capi, torch, whole, args.iters))
         if args.baseline:
             res.update(run_host(capi, torch, whole, args.baseline_mb))
