@@ -588,7 +588,8 @@ int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t
  * capacity is ever written, and a member writes inside its own ISIZE span only.  A corrupt image is never read outside
  * [image, image + image_bytes).  `image` has any alignment, `out` and `workspace` are 16-byte aligned.
  *
- * sk_bgzf_inflate_device_async only enqueues kernels on hip_stream (7 + ceil(log2(n / 26 + 1)) + 1 of them): no allocation,
+ * sk_bgzf_inflate_device_async only enqueues kernels on hip_stream (with R = ceil(log2(floor(n / 26) + 1)): 6 + R when
+ * counting, 8 + R otherwise, the last one a single lane that writes the word of sk_bgzf_inflate_output_words): no allocation,
  * no copy, no synchronisation.  All scratch and the counts live in `workspace`.  With n = image_bytes and
  * A(x) = 16 ceil(x / 16):
  *   sk_bgzf_inflate_workspace_bytes(n) = 128 + A(4 (floor(n / 4096) + 1)) + A(8 C) + 3 A(4 C) + A(40 (floor(n / 26) + 1)),
@@ -672,6 +673,44 @@ int sk_gzip_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t ima
                                  void *workspace, size_t workspace_bytes, void *hip_stream);
 /* Waits for hip_stream and fills *counts from the workspace: SK_EDATA, SK_ESPACE or SK_OK (in this order of precedence). */
 int sk_gzip_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts);
+
+/*
+ * The device words of a reader's call inside its workspace, as its kernels write them on the stream: *bytes_dev = the
+ * call's bytes_out (what the text needs, also when it did not fit), *written_dev = 1 iff the text is in `out`: the call
+ * decoded (out != NULL), ended without an error, and its text fitted the capacity; else 0, so a count-only call gives 0.
+ * The written word is the last thing a call writes: behind the last kernel that can still lower the error.  Like
+ * sk_trim_fastq_output_words: no device access, no wait; SK_EINVAL for a NULL argument.  Fed to sk_fastq_lengths (below)
+ * with sk_fastq_input.bytes = the capacity of `out`, they chain a reader and the trim without a host wait in between.
+ */
+int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev);
+int sk_gzip_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev);
+
+/*
+ * The FASTQ trim with the texts' lengths taken from the device: sk_trim_fastq_device_async (order == NULL, a workspace of
+ * sk_trim_fastq_workspace_bytes, finished by sk_trim_fastq_device_finish) or sk_trim_fastq_ordered_device_async (order !=
+ * NULL, sk_trim_fastq_ordered_workspace_bytes, sk_trim_fastq_ordered_device_finish), and everything said there holds, with
+ * in->bytes[i] an upper bound on text i's length instead of the length.
+ * The length n_i of text i is in->bytes[i], or *lengths->bytes_dev[i] (read on the stream, must be <= in->bytes[i]; a
+ * larger value is taken as in->bytes[i]) when that is given; with valid_dev[i] given and *valid_dev[i] == 0 the text counts
+ * as empty.  The workspace, the launches and every per-read step are sized by in->bytes (a tight bound is a fast call);
+ * chunks past n_i count no line and load nothing.  No 16-byte block of text[i] without a byte of [0, n_i) is loaded, and
+ * no byte at or beyond n_i bears on anything: the buffer behind n_i may be uninitialised.  It must be READABLE, though, as
+ * for the call without `lengths`: text[i] up to the end of the aligned 16-byte block that holds byte n_i - 1, so at most 15
+ * bytes beyond in->bytes[i].  A last line without '\n' ends at n_i.  Every count, verdict and output is what the call without `lengths` gives on the text text[i][0, n_i).
+ * lengths == NULL, or all four pointers NULL, is that call bit for bit.  Words that are not 8-byte aligned, or a word for
+ * text[1] outside SK_TRIM_PE_SPLIT, are SK_EINVAL and enqueue nothing (as are the bad arguments of the two calls above).
+ * Same discipline: only kernels are enqueued (the same ones, no more), finish is the only call that waits, and
+ * sk_trim_fastq_output_words works on this workspace: reader -> trim -> BGZF writer chain on one stream with one wait.
+ */
+typedef struct {
+    const uint64_t *bytes_dev[2]; /* device, 8-byte aligned, or NULL: text i's length, read on the stream; must be <= bytes[i] */
+    const uint64_t *valid_dev[2]; /* device, 8-byte aligned, or NULL: if given and *valid_dev[i] == 0 text i counts as empty */
+} sk_fastq_lengths;
+
+int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                       const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order,
+                                       const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                       void *hip_stream);
 
 #ifdef __cplusplus
 }

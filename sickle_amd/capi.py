@@ -32,7 +32,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_bgzf_device_finish", "sk_bgzf_inflate_workspace_bytes", "sk_bgzf_inflate_device_async",
            "sk_bgzf_inflate_device_finish", "sk_gzip_inflate_workspace_bytes", "sk_gzip_inflate_device_async",
            "sk_gzip_inflate_device_finish", "sk_trim_fastq_ordered_workspace_bytes", "sk_trim_fastq_ordered_device_async",
-           "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches")
+           "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches",
+           "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words")
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
 
@@ -91,6 +92,10 @@ class TrimCounts(C.Structure):
 
 class FastqInput(C.Structure):
     _fields_ = [("text", C.c_void_p * 2), ("bytes", C.c_uint64 * 2), ("max_read_len", C.c_uint32)]
+
+
+class FastqLengths(C.Structure):
+    _fields_ = [("bytes_dev", C.c_void_p * 2), ("valid_dev", C.c_void_p * 2)]
 
 
 class FastqOutput(C.Structure):
@@ -292,6 +297,14 @@ def lib():
                                                           C.POINTER(FastqOrderCounts)]
         L.sk_trim_fastq_ordered_batches.restype = C.c_int
         L.sk_trim_fastq_ordered_batches.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.sk_trim_fastq_chained_device_async.restype = C.c_int
+        L.sk_trim_fastq_chained_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput),
+                                                         C.POINTER(FastqLengths), C.c_int, C.POINTER(FastqOrder),
+                                                         C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_bgzf_inflate_output_words.restype = C.c_int
+        L.sk_bgzf_inflate_output_words.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.sk_gzip_inflate_output_words.restype = C.c_int
+        L.sk_gzip_inflate_output_words.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sk_trim_fastq_output_words.restype = C.c_int
         L.sk_trim_fastq_output_words.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sk_bgzf_bound.restype = C.c_uint64
@@ -543,6 +556,23 @@ class Context:
         self._check(rc, c.range)
         return counts
 
+    def trim_fastq_chained_device_async(self, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes,
+                                        bytes_dev_ptrs=(), valid_dev_ptrs=(), mode="se", order=None, max_read_len=0,
+                                        stream=None):
+        """sk_trim_fastq_chained_device_async on raw device pointers: text_bounds are upper bounds on the texts' lengths,
+        bytes_dev_ptrs / valid_dev_ptrs (up to two entries each, None = not given) the device words that hold the lengths
+        and their validity, e.g. those of bgzf_inflate_output_words.  order: a FastqOrder or None (read order); the
+        workspace and the finish are those of trim_fastq_ordered_device_async / trim_fastq_device_async accordingly."""
+        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bounds) + [0] * (2 - len(text_bounds))
+        bd, vd = list(bytes_dev_ptrs) + [None] * (2 - len(bytes_dev_ptrs)), list(valid_dev_ptrs) + [None] * (2 - len(valid_dev_ptrs))
+        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
+        lengths = FastqLengths((C.c_void_p * 2)(*bd), (C.c_void_p * 2)(*vd))
+        arr = (FastqOutput * 3)(*list(outs)[:3])
+        self._check(lib().sk_trim_fastq_chained_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
+                                                             TRIM_MODES.get(mode, mode),
+                                                             None if order is None else C.byref(order), arr,
+                                                             workspace_ptr, workspace_bytes, stream))
+
     @staticmethod
     def trim_fastq_ordered_batches(workspace_ptr):
         """sk_trim_fastq_ordered_batches -> the device address of the table of first units (batches + 1 entries)."""
@@ -566,7 +596,8 @@ class Context:
         try:
             return call(first)
         except TrimError as e:
-            if e.rc != SK_ESPACE or e.counts["order"]["batches"] != first.batch_capacity + 1 or \
+            # only the trim's own SK_ESPACE for the batch table is retried: a reader's (its counts have no "order") goes up
+            if e.rc != SK_ESPACE or "order" not in e.counts or e.counts["order"]["batches"] != first.batch_capacity + 1 or \
                     second.batch_capacity <= first.batch_capacity:
                 raise
         return call(second)
@@ -784,12 +815,124 @@ class Context:
                 raise
         return self.gunzip(image)
 
-    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False):
+    @staticmethod
+    def bgzf_inflate_output_words(workspace_ptr):
+        """sk_bgzf_inflate_output_words -> (bytes_dev, written_dev) device addresses of a BGZF reader's call."""
+        b, w = C.c_void_p(), C.c_void_p()
+        if lib().sk_bgzf_inflate_output_words(workspace_ptr, C.byref(b), C.byref(w)) != SK_OK:
+            raise SickleError("sk_bgzf_inflate_output_words: bad arguments")
+        return b.value, w.value
+
+    @staticmethod
+    def gzip_inflate_output_words(workspace_ptr):
+        """sk_gzip_inflate_output_words -> (bytes_dev, written_dev) device addresses of a gzip reader's call."""
+        b, w = C.c_void_p(), C.c_void_p()
+        if lib().sk_gzip_inflate_output_words(workspace_ptr, C.byref(b), C.byref(w)) != SK_OK:
+            raise SickleError("sk_gzip_inflate_output_words: bad arguments")
+        return b.value, w.value
+
+    @staticmethod
+    def _gz_kind(image):
+        """"bgzf" for an image whose first member begins 1f 8b 08 04 with B C 02 00 at bytes 12-15, else "gzip" (the gzip
+        reader reads BGZF too: a BC subfield that does not come first is slow, not wrong)."""
+        head = bytes(image[:16].cpu().tolist())
+        return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
+
+    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search):
+        """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
+        words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
+        import torch
+        dev = images[0].device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        L = lib()
+        texts, readers, nbytes, valid = [], [], [], []
+        for image, cap, kind in zip(images, capacities, kinds):
+            n = image.numel()
+            text = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+            if kind == "bgzf":
+                rws_bytes = L.sk_bgzf_inflate_workspace_bytes(n)
+                run, fin, words = self.bgzf_inflate_device_async, self.bgzf_inflate_device_finish, self.bgzf_inflate_output_words
+            else:
+                rws_bytes = L.sk_gzip_inflate_workspace_bytes(n, cap)
+                run, fin, words = self.gzip_inflate_device_async, self.gzip_inflate_device_finish, self.gzip_inflate_output_words
+            rws = torch.empty(max(rws_bytes, 16), dtype=torch.uint8, device=dev)
+            run(image.data_ptr() if n else None, n, text.data_ptr(), cap, rws.data_ptr(), rws_bytes, stream=stream)
+            b, w = words(rws.data_ptr())
+            texts.append(text)
+            readers.append((fin, rws))
+            nbytes.append(b)
+            valid.append(w)
+        if order is None:
+            ws_bytes = L.sk_trim_fastq_workspace_bytes(sum(capacities), params.trunc_n)
+        else:
+            ws_bytes = L.sk_trim_fastq_ordered_workspace_bytes(sum(capacities), params.trunc_n, order.batch_capacity)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        cap = sum(capacities) + 2
+        bound = L.sk_bgzf_bound(cap, SK_BGZF_EOF)
+        zws_bytes = L.sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
+        outs, trimmed, out_images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
+        for o in used:
+            trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+            outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
+        self.trim_fastq_chained_device_async(params, [t.data_ptr() for t in texts], capacities, outs, ws.data_ptr(), ws_bytes,
+                                             bytes_dev_ptrs=nbytes, valid_dev_ptrs=valid, mode=mode, order=order,
+                                             max_read_len=max_read_len, stream=stream)
+        for o in used:
+            out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
+            zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
+            b, w = self.trim_fastq_output_words(ws.data_ptr(), o)
+            self.bgzf_device_async(trimmed[o].data_ptr(), cap, out_images[o].data_ptr(), bound, zws[o].data_ptr(), zws_bytes,
+                                   eof=True, bytes_dev_ptr=b, valid_dev_ptr=w, stream=stream, search=search)
+        trim_finish = self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish
+        failed, reader_counts = None, []
+        for fin, rws in readers:  # GzDataError, or TrimError (SK_ESPACE) whose counts["bytes_out"] is the need
+            try:
+                reader_counts.append(fin(rws.data_ptr(), stream))
+            except (GzDataError, TrimError) as e:
+                failed = failed or e
+                reader_counts.append(e.counts)
+        if failed is not None:
+            try:  # the trim saw an empty text for that image; its finish still reads and clears the stream's error word
+                trim_finish(ws.data_ptr(), stream)
+            except SickleError:
+                pass
+            failed.readers = reader_counts  # every image's counts, so that two short capacities are learnt in one call
+            raise failed
+        sizes_out = [None if out_images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
+                     for o in range(3)]
+        counts = trim_finish(ws.data_ptr(), stream)
+        return tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3)), counts
+
+    def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
+                kind=None):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
-        on the device: bgunzip (gunzip for plain gzip), then trim_fastq_gz.  The one host wait in between is the text's
-        length, which sk_fastq_input takes from the host.  Returns what trim_fastq_gz returns; raises GzDataError and what
-        it raises.  order: as trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as
-        bgzf's."""
+        on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
+        trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
+        text_capacity=None: two passes: bgunzip (gunzip for plain gzip), each a count-only call, a host wait and a decoding
+        call, then trim_fastq_gz on texts whose lengths the host has seen.
+        text_capacity given (an int, or a pair for two images: an upper bound on each image's text): one pass with one
+        wait at its end.  Each image gets one decoding reader call into a buffer of that capacity,
+        sk_trim_fastq_chained_device_async takes the lengths from the readers' device words and the writers theirs from
+        the trim's; then the finishes run: the readers' (GzDataError, or TrimError with SK_ESPACE whose
+        counts["bytes_out"] is the capacity that image needs: call again with it), the writers', the trim's.  The error
+        raised is the first image's that failed; its `readers` attribute lists every image's counts (bytes_out: its need),
+        so two short capacities are learnt from one call.  `order` does not change this: only the trim's own SK_ESPACE
+        for a batch table that was too small is retried.  Every
+        per-read step of the trim is sized by the capacity, so a tight bound is a fast call.  kind: "bgzf" or "gzip"
+        names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
+        enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more."""
+        if text_capacity is not None:
+            images = [image] if image2 is None else [image, image2]
+            caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
+            kinds = list(kind) if isinstance(kind, (tuple, list)) else [kind] * len(images)
+            if len(caps) != len(images) or len(kinds) != len(images):
+                raise SickleError("trim_gz: text_capacity and kind take one entry per image")
+            kinds = [self._gz_kind(im) if k is None else k for im, k in zip(images, kinds)]
+            if any(k not in ("bgzf", "gzip") for k in kinds):
+                raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
+            return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
+                                                                                       max_read_len, o, search))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search)

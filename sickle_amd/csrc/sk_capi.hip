@@ -793,13 +793,26 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
 
 namespace {
 // both FASTQ calls; order: NULL = read order
-int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in, int mode,
-                const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
-                void *hip_stream)
+int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
+                const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
+                void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
                               order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
     if (rc != SK_OK) return rc;
+    if (lengths) {
+        uintptr_t words = 0;
+        for (int i = 0; i < 2; ++i)
+            words |= reinterpret_cast<uintptr_t>(lengths->bytes_dev[i]) | reinterpret_cast<uintptr_t>(lengths->valid_dev[i]);
+        if (words & 7) {
+            set_error(ctx, "fastq: bytes_dev and valid_dev must be 8-byte aligned");
+            return SK_EINVAL;
+        }
+        if (mode != SK_TRIM_PE_SPLIT && (lengths->bytes_dev[1] || lengths->valid_dev[1])) {
+            set_error(ctx, "fastq: bytes_dev[1] and valid_dev[1] are only for SK_TRIM_PE_SPLIT");
+            return SK_EINVAL;
+        }
+    }
     sk_scan_args chk;
     const uint64_t no_reads = 0;
     sk_batch probe = {};
@@ -813,7 +826,7 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     SK_HIP(ctx, hipSetDevice(ctx->device));
     sk_batch packed;
     sk_cut_dev *cuts;
-    SK_HIP(ctx, sk_launch_fastq_front(in, mode, params->trunc_n, order, workspace, ctx->cu_count, stream, &packed, &cuts));
+    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, order, workspace, ctx->cu_count, stream, &packed, &cuts));
     rc = sk_scan_device_async(ctx, params, &packed, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
     SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, order, out, workspace, d_err, ctx->cu_count, stream));
@@ -824,7 +837,8 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
 int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
                                const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return fastq_async(ctx, "sk_trim_fastq_device_async", params, in, mode, nullptr, out, workspace, workspace_bytes, hip_stream);
+    return fastq_async(ctx, "sk_trim_fastq_device_async", params, in, nullptr, mode, nullptr, out, workspace, workspace_bytes,
+                       hip_stream);
 }
 
 namespace {
@@ -912,9 +926,11 @@ size_t sk_trim_fastq_ordered_workspace_bytes(uint64_t text_bytes, int32_t trunc_
     return sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + (size_t)sk_fq_order_shift(batch_capacity);
 }
 
-int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
-                                       const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace,
-                                       size_t workspace_bytes, void *hip_stream)
+namespace {
+// the ordered call; lengths: NULL = in->bytes are the lengths
+int fastq_ordered_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                        const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order,
+                        const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
     if (!order || order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN ||
@@ -922,8 +938,26 @@ int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, con
         set_error(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
         return SK_EINVAL;
     }
-    return fastq_async(ctx, "sk_trim_fastq_ordered_device_async", params, in, mode, order, out, workspace, workspace_bytes,
-                       hip_stream);
+    return fastq_async(ctx, "sk_trim_fastq_ordered_device_async", params, in, lengths, mode, order, out, workspace,
+                       workspace_bytes, hip_stream);
+}
+} // namespace
+
+int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
+                                       const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace,
+                                       size_t workspace_bytes, void *hip_stream)
+{
+    return fastq_ordered_async(ctx, params, in, nullptr, mode, order, out, workspace, workspace_bytes, hip_stream);
+}
+
+int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                       const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order,
+                                       const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                       void *hip_stream)
+{
+    if (order) return fastq_ordered_async(ctx, params, in, lengths, mode, order, out, workspace, workspace_bytes, hip_stream);
+    return fastq_async(ctx, "sk_trim_fastq_chained_device_async", params, in, lengths, mode, nullptr, out, workspace,
+                       workspace_bytes, hip_stream);
 }
 
 int sk_trim_fastq_ordered_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
@@ -936,6 +970,24 @@ int sk_trim_fastq_ordered_batches(void *workspace, const uint64_t **first_unit_d
 {
     if (!workspace || !first_unit_dev) return SK_EINVAL;
     *first_unit_dev = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(workspace) + SK_FQO_TABLE_BYTES_AT);
+    return SK_OK;
+}
+
+int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)
+{
+    if (!workspace || !bytes_dev || !written_dev) return SK_EINVAL;
+    const uint64_t *hdr = static_cast<const uint64_t *>(workspace);
+    *bytes_dev = hdr + SK_INFLATE_H_BYTES_OUT;
+    *written_dev = hdr + SK_INFLATE_H_WRITTEN;
+    return SK_OK;
+}
+
+int sk_gzip_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)
+{
+    if (!workspace || !bytes_dev || !written_dev) return SK_EINVAL;
+    const uint64_t *hdr = static_cast<const uint64_t *>(workspace);
+    *bytes_dev = hdr + SK_GUNZIP_H_BYTES_OUT;
+    *written_dev = hdr + SK_GUNZIP_H_WRITTEN;
     return SK_OK;
 }
 

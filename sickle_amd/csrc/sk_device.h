@@ -191,11 +191,15 @@ static inline void sk_fq_layout_of(uint64_t text_bytes, int trunc_n, sk_fq_layou
 // Ordered calls (sk_trim_fastq_ordered_device_async, sk_fastq_order.h): the same header (its words 21.. are theirs), then
 // the table of first units (8 * (batch_capacity + 1), rounded up to 16), then the sections above, shifted by the table.
 static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * (batch_capacity + 1) + 15) & ~15ull; }
-// order: NULL = read order (sk_trim_fastq_device_async)
-extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                  const sk_fastq_order *order, void *workspace,
-                                                                                  int cu_count, hipStream_t stream,
-                                                                                  sk_batch *packed, sk_cut_dev **cuts);
+// order: NULL = read order (sk_trim_fastq_device_async).  lengths: NULL = in->bytes are the texts' lengths; else
+// (sk_trim_fastq_chained_device_async) in->bytes are bounds and the framing kernels, the only ones that look at a text's
+// length, take it from the device words: everything behind them reads lines and records from the header.
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
+                                                                                  const sk_fastq_lengths *lengths, int mode,
+                                                                                  int trunc_n, const sk_fastq_order *order,
+                                                                                  void *workspace, int cu_count,
+                                                                                  hipStream_t stream, sk_batch *packed,
+                                                                                  sk_cut_dev **cuts);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  const sk_fastq_order *order,
                                                                                  const sk_fastq_output *out, void *workspace,
@@ -266,6 +270,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf(const
 #define SK_INFLATE_H_FRAME_KEY 5    // the same for the framing error alone
 #define SK_INFLATE_H_FRAME_OFFSET 6 // its byte offset (a member that framed has its offset in the table)
 #define SK_INFLATE_H_CANDIDATES 7
+#define SK_INFLATE_H_WRITTEN 8      // 1 iff the call decoded, without an error, a text within the capacity (sk_bgzf_inflate_output_words)
 struct sk_inflate_entry {
     uint64_t image_off, out_off;
     uint32_t body_off, body_len; // the deflate stream, relative to image_off
@@ -304,6 +309,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf_infla
 // The chunk: 32 KiB, doubled until 4096 chunks cover the image (the decode kernels' grids are 4096 single-wave
 // workgroups); SK_GZIP_CHUNK (a power of two of 256 or more) replaces it.
 #define SK_GUNZIP_HDR_WORDS 32u
+#define SK_GUNZIP_H_BYTES_OUT 2 // the header words sk_gzip_inflate_output_words hands out (== SKG_H_* of sk_gunzip_block.h)
+#define SK_GUNZIP_H_WRITTEN 11
 #define SK_GUNZIP_STRETCH_BYTES 128u
 #define SK_GUNZIP_MEMBER_BYTES 32u
 #define SK_GUNZIP_MIN_CHUNK 32768u

@@ -46,7 +46,8 @@ struct fq_out {
 
 struct fq_args {
     const uint8_t *text[2];
-    uint64_t bytes[2];
+    uint64_t bytes[2]; // the lengths, or their bounds
+    const uint64_t *bytes_dev[2], *valid_dev[2];
     uint64_t n_chunks[2];
     uint64_t slots[2];
     int32_t mode;
@@ -67,11 +68,20 @@ struct fq_args {
 // ------------------------------------------------------------------------------------------
 // shared pieces
 // ------------------------------------------------------------------------------------------
-// the '\n' bytes of the aligned 16-byte block at q (offset from the aligned base of text i) that lie inside the text:
-// bit b = byte q + b.  A block without a byte of the text is not loaded.
-__device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t q)
+// text i's length: never beyond the bound the launches and the workspace were sized by
+__device__ __forceinline__ uint64_t fq_length(const fq_args &a, int i)
 {
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, span = sh + a.bytes[i];
+    uint64_t n = a.bytes[i];
+    if (a.bytes_dev[i]) n = min(n, *a.bytes_dev[i]);
+    if (a.valid_dev[i] && *a.valid_dev[i] == 0) n = 0;
+    return n;
+}
+
+// the '\n' bytes of the aligned 16-byte block at q (offset from the aligned base of text i) that lie inside the text of
+// n bytes (fq_length, loaded once per workgroup): bit b = byte q + b.  A block without a byte of the text is not loaded.
+__device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t n, uint64_t q)
+{
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, span = sh + n;
     if (q + 16 <= sh || q >= span) return 0;
     const fq_u4 *blk = reinterpret_cast<const fq_u4 *>((reinterpret_cast<uintptr_t>(a.text[i]) & ~(uintptr_t)15) + q);
     const fq_u4 v = __builtin_nontemporal_load(blk);
@@ -205,11 +215,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_count_kernel(fq_args a
     __shared__ uint64_t lds[8];
     const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
     const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15;
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i);
     uint64_t cnt = 0, last = 0; // last: position + 1 of the lane's last '\n', 0 = none
     for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
         const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
-        const uint32_t m = fq_nl_mask(a, i, q);
+        const uint32_t m = fq_nl_mask(a, i, n, q);
         cnt += __builtin_popcount(m);
         if (m) last = q + (31 - __builtin_clz(m)) - sh + 1;
     }
@@ -248,8 +258,9 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_scan_kernel(fq_args a)
         }
         lines[i] = s_tot;
         // a last line without '\n' ends at the end of the text
-        if (threadIdx.x == 0 && a.bytes[i] && a.text[i][a.bytes[i] - 1] != '\n') {
-            fq_put_line(a, i, s_tot, m_tot, a.bytes[i]);
+        const uint64_t n = fq_length(a, i);
+        if (threadIdx.x == 0 && n && a.text[i][n - 1] != '\n') {
+            fq_put_line(a, i, s_tot, m_tot, n);
             lines[i] += 1;
         }
         __syncthreads(); // lds reuse
@@ -283,11 +294,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_lines_kernel(fq_args a
     __shared__ uint64_t lds[8];
     const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
     const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15;
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i);
     uint64_t ln0 = a.chunks[2 * blockIdx.x], prev = a.chunks[2 * blockIdx.x + 1]; // prev: start of the chunk's first line
     for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
         const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
-        uint32_t m = fq_nl_mask(a, i, q);
+        uint32_t m = fq_nl_mask(a, i, n, q);
         const uint64_t last = m ? q + (31 - __builtin_clz(m)) - sh + 1 : 0;
         uint64_t s_ex, m_ex, s_tot, m_tot;
         fq_scan2(__builtin_popcount(m), last, s_ex, m_ex, s_tot, m_tot, lds);
@@ -981,8 +992,9 @@ uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
 }
 
 // shift: bytes between the header and the sections (an ordered call's batch table lies there)
-void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fastq_output *out, void *workspace,
-                  const unsigned long long *errword, fq_args &a, uint64_t shift = 0)
+void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n,
+                  const sk_fastq_output *out, void *workspace, const unsigned long long *errword, fq_args &a,
+                  uint64_t shift = 0)
 {
     sk_fq_layout L;
     sk_fq_layout_of(in->bytes[0] + (mode == SK_TRIM_PE_SPLIT ? in->bytes[1] : 0), trunc_n, &L);
@@ -991,6 +1003,8 @@ void fq_make_args(const sk_fastq_input *in, int mode, int trunc_n, const sk_fast
     for (int i = 0; i < 2; ++i) {
         a.text[i] = i < n_in ? in->text[i] : nullptr;
         a.bytes[i] = i < n_in ? in->bytes[i] : 0;
+        a.bytes_dev[i] = i < n_in && lengths ? lengths->bytes_dev[i] : nullptr;
+        a.valid_dev[i] = i < n_in && lengths ? lengths->valid_dev[i] : nullptr;
         a.n_chunks[i] = fq_chunks_of(a.text[i], a.bytes[i]);
         a.slots[i] = i < n_in ? sk_fq_slots(a.bytes[i]) : 0;
     }
@@ -1025,14 +1039,17 @@ fq_order fq_make_order(const sk_fastq_order *order, void *workspace)
 }
 } // namespace
 
-// order: NULL = read order; else the batch chain and its check take the place of the check of every record
-extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                  const sk_fastq_order *order, void *workspace,
-                                                                                  int cu_count, hipStream_t stream,
-                                                                                  sk_batch *packed, sk_cut_dev **cuts)
+// order: NULL = read order; else the batch chain and its check take the place of the check of every record.  lengths:
+// NULL = in->bytes are the lengths; else the device words that hold them, in->bytes their bounds
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
+                                                                                  const sk_fastq_lengths *lengths, int mode,
+                                                                                  int trunc_n, const sk_fastq_order *order,
+                                                                                  void *workspace, int cu_count,
+                                                                                  hipStream_t stream, sk_batch *packed,
+                                                                                  sk_cut_dev **cuts)
 {
     fq_args a;
-    fq_make_args(in, mode, trunc_n, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    fq_make_args(in, lengths, mode, trunc_n, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
     const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
     if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
@@ -1065,7 +1082,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
                                                                                  hipStream_t stream)
 {
     fq_args a;
-    fq_make_args(in, mode, trunc_n, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    // no emission kernel looks at a text's length: lines and records come from the descriptors and the header
+    fq_make_args(in, nullptr, mode, trunc_n, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
     const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
     if (order) {
         const fq_order o = fq_make_order(order, workspace);

@@ -11,7 +11,7 @@
 //   6 resolve  the grid: symbols -> bytes of `out`, 16 per lane
 //   7 crc      one wavefront per 32 KiB piece of `out`: its spans' CRC terms, XORed into their members
 //   8 check    one lane per member: ISIZE, CRC-32
-//   9 final    one lane: the offset of the lowest failure
+//   9 final    one lane: the offset of the lowest failure, and the word sk_gzip_inflate_output_words hands out
 // Count-only calls (out == NULL) stop behind 3.  The workspace is the caller's: sk_device.h.
 #include <hip/hip_runtime.h>
 
@@ -22,7 +22,8 @@
 #define SG_WINDOW_THREADS 1024
 
 static_assert(sizeof(skg_stretch) == SK_GUNZIP_STRETCH_BYTES && sizeof(skg_member) == SK_GUNZIP_MEMBER_BYTES &&
-                  SKG_HDR_WORDS == SK_GUNZIP_HDR_WORDS && SKG_MIN_GAP == 18,
+                  SKG_HDR_WORDS == SK_GUNZIP_HDR_WORDS && SKG_MIN_GAP == 18 && SKG_H_BYTES_OUT == SK_GUNZIP_H_BYTES_OUT &&
+                  SKG_H_WRITTEN == SK_GUNZIP_H_WRITTEN,
               "the workspace sections of sk_device.h are those of sk_gunzip_block.h");
 
 // the fixed code's tables, once per workgroup

@@ -37,6 +37,7 @@
 #define SKG_H_CHAIN_KEY 8    // the failure that stopped the chain, or ~0
 #define SKG_H_CHAIN_OFFSET 9
 #define SKG_H_DECODED 10     // the call decodes (out != NULL)
+#define SKG_H_WRITTEN 11     // skg_final: 1 iff the call decoded, without an error, a text within the capacity
 
 #define SKG_S_JOIN 0u  // ended exactly on a later stretch's start
 #define SKG_S_END 1u   // ended with the image, behind a trailer
@@ -753,11 +754,14 @@ SKD_FN void skg_check_member(const uint32_t *power, const skg_args &a, uint64_t 
 }
 
 // ------------------------------------------------------------------------------------------
-// stage 9, final (one lane): the offset that goes with the lowest failure
+// stage 9, final (one lane): the written word, and the offset that goes with the lowest failure
 // ------------------------------------------------------------------------------------------
 SKD_FN void skg_final(const skg_args &a)
 {
     const uint64_t key = a.hdr[SKG_H_ERROR_KEY];
+    // nothing behind this stage lowers the key, and the stage runs in decoding calls whose text fitted only: in every
+    // other call the word keeps the 0 skg_search_first gave it
+    a.hdr[SKG_H_WRITTEN] = a.out != nullptr && key == SKG_NONE;
     if (key == SKG_NONE) return;
     const uint32_t why = (uint32_t)(key & 7u);
     const uint64_t m = key >> 3;

@@ -17,6 +17,9 @@
 //              the capacity
 //   8 inflate  one wavefront per member on a fixed persistent grid: ski_inflate_member (sk_inflate_block.h) straight
 //              into the member's span of `out`, its verdict to the table and, by atomicMin, to the error word
+//   9 written  one lane: the word sk_bgzf_inflate_output_words hands out.  A launch of its own, because any workgroup
+//              of 8 may be the last to lower the error word and none of them knows that it is
+// Count-only calls (out == NULL) stop behind 7, which has cleared the written word.
 // The workspace (caller's, device) holds the header, the tile counts, the candidate arrays and the table: sk_device.h.
 #include <hip/hip_runtime.h>
 
@@ -231,6 +234,7 @@ __global__ void __launch_bounds__(SI_THREADS) sk_inflate_scan_kernel(si_args a)
         a.hdr[SK_INFLATE_H_BYTES_OUT] = run;
         a.hdr[SK_INFLATE_H_FIT] = a.out == nullptr || run <= a.capacity;
         a.hdr[SK_INFLATE_H_ERROR_KEY] = worst;
+        a.hdr[SK_INFLATE_H_WRITTEN] = 0;
     }
 }
 
@@ -261,6 +265,11 @@ __global__ void __launch_bounds__(SKI_LANES) sk_inflate_member_kernel(si_args a)
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(64) sk_inflate_written_kernel(si_args a)
+{
+    if (threadIdx.x == 0) a.hdr[SK_INFLATE_H_WRITTEN] = a.hdr[SK_INFLATE_H_FIT] && a.hdr[SK_INFLATE_H_ERROR_KEY] == ~0ull;
 }
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf_inflate(const uint8_t *image, uint64_t image_bytes,
@@ -304,6 +313,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_bgzf_infla
     if (out) {
         const unsigned grid = (unsigned)(L.n_table < SK_INFLATE_GRID ? L.n_table : SK_INFLATE_GRID);
         hipLaunchKernelGGL(sk_inflate_member_kernel, dim3(grid), dim3(SKI_LANES), 0, stream, a);
+        hipLaunchKernelGGL(sk_inflate_written_kernel, dim3(1), dim3(64), 0, stream, a);
     }
     return hipGetLastError();
 }
