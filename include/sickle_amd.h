@@ -712,6 +712,25 @@ int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, con
                                        const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
                                        void *hip_stream);
 
+/*
+ * The device-resident scan with the read count taken from the device: sk_scan_device_async, and everything said there
+ * holds, with batch->n_reads an upper bound B on the read count instead of the count.
+ * The scan covers n = min(*n_reads_dev, B) reads; the word is read on the stream (it may be written by work the caller
+ * enqueued there earlier; a value above B is taken as B).  out[r] is written for r < n and not touched for r >= n.
+ * offsets[i] is read for i <= n only, and no byte of qual or seq at or beyond offsets[n] bears on a result: the entries
+ * and bytes behind them may be uninitialised.  Range errors come from reads below n only.  n == 0 scans nothing.
+ * The grids, the regrouping of a big mixed batch (whether it runs, and its scratch), the LDS buffers and what
+ * batch->stride hints at are sized by B on the host: the launches are those of sk_scan_device_async on a batch of B
+ * reads, so a tight bound is a fast call; windows, tiles, teams and spans at or beyond n return without a load, and the
+ * regrouping's verdict (a batch of one length is not regrouped) is taken over the n reads -- empty reads behind them do
+ * not make it a mixed batch.
+ * Only `offsets` batches: offsets != NULL, tiles == NULL, lengths == NULL; a word with any other layout, or a word that
+ * is not 8-byte aligned, is SK_EINVAL and enqueues nothing.  n_reads_dev == NULL is sk_scan_device_async bit for bit: the
+ * same launches, nothing more loaded.  Finished by sk_scan_device_finish, which is unchanged.
+ */
+int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch,
+                                 const uint64_t *n_reads_dev, sk_cut *out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

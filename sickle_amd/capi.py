@@ -33,7 +33,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_bgzf_inflate_device_finish", "sk_gzip_inflate_workspace_bytes", "sk_gzip_inflate_device_async",
            "sk_gzip_inflate_device_finish", "sk_trim_fastq_ordered_workspace_bytes", "sk_trim_fastq_ordered_device_async",
            "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches",
-           "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words")
+           "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words",
+           "sk_scan_counted_device_async")
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
 
@@ -249,6 +250,9 @@ def lib():
         L.sk_host_free.argtypes = [C.c_void_p, C.c_void_p]
         L.sk_scan_device_async.restype = C.c_int
         L.sk_scan_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Batch), C.c_void_p, C.c_void_p]
+        L.sk_scan_counted_device_async.restype = C.c_int
+        L.sk_scan_counted_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Batch), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
         L.sk_scan_device_finish.restype = C.c_int
         L.sk_scan_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Err)]
         L.sk_trim_batch.restype = C.c_int
@@ -421,6 +425,14 @@ class Context:
                           offsets_ptr=None, lengths_ptr=None, stream=None):
         b = Batch(qual_ptr, seq_ptr, offsets_ptr, stride, read_len, lengths_ptr, n_reads)
         self._check(lib().sk_scan_device_async(self._h, C.byref(params), C.byref(b), out_ptr, stream))
+
+    def scan_counted_device_async(self, params, qual_ptr, out_ptr, n_reads_bound, n_reads_dev_ptr, offsets_ptr, seq_ptr=None,
+                                  max_read_len=0, stream=None):
+        """sk_scan_counted_device_async on raw device pointers: an `offsets` batch of at most n_reads_bound reads whose
+        read count is the 8-byte device word at n_reads_dev_ptr, read on the stream (None: the bound is the count).
+        Cuts are written for the reads below min(word, bound) only; max_read_len is the longest-read hint (0 = unknown)."""
+        b = Batch(qual_ptr, seq_ptr, offsets_ptr, max_read_len, 0, None, n_reads_bound)
+        self._check(lib().sk_scan_counted_device_async(self._h, C.byref(params), C.byref(b), n_reads_dev_ptr, out_ptr, stream))
 
     def probe_read_bandwidth(self, dev_ptr, nbytes, launches=20, stream=None):
         """GB/s of a read-only stream over [dev_ptr, dev_ptr + nbytes) on this device."""

@@ -81,6 +81,18 @@ sk_scan_band_kernel(const uint8_t *__restrict__ qual, const uint8_t *__restrict_
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x; // single-wave workgroups
     const int half = lane >> 5, l32 = lane & 31;
+    // a counted scan (`offsets` batches): the reads below the device's count, as in the other kernels.  The word comes in
+    // by a vector load, every lane the same address, and readfirstlane: with sk_counted_reads' scalar load the form that
+    // takes every read with -n, at this kernel's register limit, spills a register (8 bytes of scratch per lane)
+    if (!UNI) {
+        if (a.n_reads_dev) {
+            const uint64_t word = *a.n_reads_dev;
+            const uint64_t n_dev = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(word >> 32)) << 32) |
+                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)word);
+            a.n_reads = min(a.n_reads, n_dev);
+        }
+        if (a.n_reads == 0) return;
+    }
     // A slot of the ring: a read's quality bytes [, its sequence bytes], a.team_rbuf bytes each (the longest read the
     // ring takes, rounded up).  The matrix chains read up to a KiB + the band's reach past a read's last window: into
     // the next slot (whatever lies there: those windows are masked), or into the overhang behind the last slot.

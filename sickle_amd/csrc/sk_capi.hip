@@ -188,6 +188,7 @@ int make_args(sk_ctx *ctx, const sk_params *p, const sk_batch *b, sk_scan_args *
     static const uint32_t seg_shift = [] { const char *e = getenv("SK_SEG_CHUNK_SHIFT"); return e ? (uint32_t)atoi(e) : 0u; }();
     a->seg_chunk_shift = seg_shift > 6u ? 6u : seg_shift;
     a->sort_flags = nullptr;
+    a->n_reads_dev = nullptr;
     a->band_table = ctx ? ctx->d_band : nullptr;
     return SK_OK;
 }
@@ -328,8 +329,8 @@ int enqueue_scan(sk_ctx *ctx, const sk_scan_args *a, const sk_batch *b, sk_cut_d
             uint32_t fit = rag_fit_len(ar.buf_bytes);
             if (b->stride && b->stride < fit) fit = b->stride;
             sort_counts = sort->counts + 16u * (sort->turn & 1u);
-            SK_HIP(ctx, sk_launch_sort(b->offsets, a->n_reads, fit, sort->perm, sort->lists, (uint32_t)sort->cap_list, sort_counts,
-                                       sort->counts + 16u * (~sort->turn & 1u), stream));
+            SK_HIP(ctx, sk_launch_sort_counted(b->offsets, a->n_reads, a->n_reads_dev, fit, sort->perm, sort->lists, (uint32_t)sort->cap_list,
+                                               sort_counts, sort->counts + 16u * (~sort->turn & 1u), stream));
             ++sort->turn;
             ar.sort_flags = sort_counts + 8;
         }
@@ -826,10 +827,16 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     SK_HIP(ctx, hipSetDevice(ctx->device));
     sk_batch packed;
     sk_cut_dev *cuts;
-    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, order, workspace, ctx->cu_count, stream, &packed, &cuts));
-    rc = sk_scan_device_async(ctx, params, &packed, reinterpret_cast<sk_cut *>(cuts), hip_stream);
+    // SK_FQ_COUNTED=0: the scan and the per-read steps walk the bound (the most records the text could hold) instead of
+    // stopping at the records the framing found.  Read on every call, so that a probe can alternate the two in one process.
+    const char *counted_env = getenv("SK_FQ_COUNTED");
+    const int counted = !(counted_env && *counted_env == '0');
+    const uint64_t *n_reads_dev = nullptr;
+    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, workspace, ctx->cu_count, stream, &packed,
+                                      &cuts, &n_reads_dev));
+    rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, order, out, workspace, d_err, ctx->cu_count, stream));
+    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, out, workspace, d_err, ctx->cu_count, stream));
     return SK_OK;
 }
 } // namespace
@@ -1231,12 +1238,28 @@ int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int 
     return SK_OK;
 }
 
-int sk_scan_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch, sk_cut *out, void *hip_stream)
+namespace {
+// both device-resident scans; n_reads_dev: NULL = batch->n_reads reads (sk_scan_device_async)
+int scan_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch, const uint64_t *n_reads_dev, sk_cut *out,
+                      void *hip_stream)
 {
     if (!ctx || !out) return SK_EINVAL;
     sk_scan_args a;
     int rc = make_args(ctx, params, batch, &a);
     if (rc != SK_OK) return rc;
+    if (n_reads_dev) {
+        // everything sized on the host -- grids, the regrouping's scratch and whether it runs, LDS -- stays a function
+        // of the bound; the kernels an `offsets` batch reaches lower their n_reads to the word (sk_counted_reads)
+        if (!batch->offsets || batch->tiles || batch->lengths) {
+            set_error(ctx, "sk_scan_counted_device_async: a device read count needs an `offsets` batch (no tiles, no lengths)");
+            return SK_EINVAL;
+        }
+        if (reinterpret_cast<uintptr_t>(n_reads_dev) & 7) {
+            set_error(ctx, "sk_scan_counted_device_async: n_reads_dev must be 8-byte aligned");
+            return SK_EINVAL;
+        }
+        a.n_reads_dev = n_reads_dev;
+    }
     // NULL is HIP's default (null) stream, like everywhere else in HIP: ordered after whatever the
     // caller queued there (e.g. the kernels that produced the batch)
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -1245,6 +1268,18 @@ int sk_scan_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *b
     rc = err_word_of(ctx, stream, &d_err, &h_err, &sort);
     if (rc != SK_OK) return rc;
     return enqueue_scan(ctx, &a, batch, reinterpret_cast<sk_cut_dev *>(out), d_err, stream, -1, sort);
+}
+} // namespace
+
+int sk_scan_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch, sk_cut *out, void *hip_stream)
+{
+    return scan_device_async(ctx, params, batch, nullptr, out, hip_stream);
+}
+
+int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch, const uint64_t *n_reads_dev,
+                                 sk_cut *out, void *hip_stream)
+{
+    return scan_device_async(ctx, params, batch, n_reads_dev, out, hip_stream);
 }
 
 int sk_scan_device_finish(sk_ctx *ctx, void *hip_stream, sk_err *err)

@@ -62,6 +62,8 @@ struct sk_scan_args {
                                 // tile's window width differs from the one before (segmented batches, regrouped ragged batches)
     const uint32_t *sort_flags; // ragged batches behind the device-side regrouping: {windows of mixed lengths, reads too long for the tiles}; the
                                 // plain tile kernel (and the general kernel behind it) return at once when the sorted scan runs, and vice versa
+    const uint64_t *n_reads_dev; // counted scans (sk_scan_counted_device_async, `offsets` batches): n_reads is a bound and the kernels an
+                                 // `offsets` batch reaches scan min(*n_reads_dev, n_reads) reads (sk_counted_reads); NULL: n_reads reads
 };
 
 // The band matrix of window width wu, as lane `lane` of a wave holds it for v_mfma_i32_32x32x32_i8 (sk_kernels.hip, MFMA path):
@@ -114,6 +116,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_wide(const
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sort(const uint64_t *offsets, uint64_t n_reads, uint32_t max_len, uint64_t *perm,
                                      unsigned long long *lists, uint32_t list_cap, uint32_t *counts, uint32_t *counts_of_next_scan,
                                      hipStream_t stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sort_counted(const uint64_t *offsets, uint64_t n_reads, const uint64_t *n_reads_dev,
+                                     uint32_t max_len, uint64_t *perm, unsigned long long *lists, uint32_t list_cap, uint32_t *counts,
+                                     uint32_t *counts_of_next_scan, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sorted(const uint8_t *qual, const uint8_t *seq, const uint64_t *offsets, const uint64_t *perm,
                                        const unsigned long long *lists, const uint32_t *counts, sk_cut_dev *out,
                                        unsigned long long *errword, const sk_scan_args *a, int cu_count, hipStream_t stream);
@@ -194,14 +199,18 @@ static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * 
 // order: NULL = read order (sk_trim_fastq_device_async).  lengths: NULL = in->bytes are the texts' lengths; else
 // (sk_trim_fastq_chained_device_async) in->bytes are bounds and the framing kernels, the only ones that look at a text's
 // length, take it from the device words: everything behind them reads lines and records from the header.
+// counted: the packed batch is for sk_scan_counted_device_async with *n_reads_dev (the header's SK_FQ_H_NREAL) -- packed->n_reads
+// stays the bound -- and the per-read steps of the pack and the emission stop at that word too; 0: everything walks the bound.
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
                                                                                   const sk_fastq_lengths *lengths, int mode,
-                                                                                  int trunc_n, const sk_fastq_order *order,
+                                                                                  int trunc_n, int counted,
+                                                                                  const sk_fastq_order *order,
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
-                                                                                  sk_cut_dev **cuts);
+                                                                                  sk_cut_dev **cuts,
+                                                                                  const uint64_t **n_reads_dev);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                 const sk_fastq_order *order,
+                                                                                 int counted, const sk_fastq_order *order,
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);

@@ -52,6 +52,7 @@ struct fq_args {
     uint64_t slots[2];
     int32_t mode;
     int32_t trunc_n;
+    int32_t counted; // the per-read steps stop at SK_FQ_H_NREAL (fq_block_empty) and the scan takes its read count from it
     uint64_t n_pack, n_blocks;
     uint64_t *hdr;
     uint64_t *chunks; // 2 words per chunk, input 0's chunks first
@@ -96,6 +97,14 @@ __device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t
     }
     const uint32_t lo = q < sh ? (uint32_t)(sh - q) : 0u, hi = span - q < 16 ? (uint32_t)(span - q) : 16u;
     return m & (((1u << hi) - 1u) & ~((1u << lo) - 1u));
+}
+
+// A block of SK_FQ_BLOCK_READS reads (or emission ranks) that lies wholly at or beyond the packed batch's records: it
+// contributes zeros to its block table entry and loads no descriptor, offset or cut (wave-uniform).  Only when the scan
+// behind the pack is the counted one (a.counted): then nothing beyond the records is scanned either.
+__device__ __forceinline__ bool fq_block_empty(const fq_args &a, uint64_t n_real)
+{
+    return a.counted && (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS >= n_real;
 }
 
 // exclusive prefix sum of s and exclusive prefix max of m over the workgroup, and both totals.  lds: 8 words.
@@ -360,6 +369,10 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_count_kernel(fq_args a)
 {
     __shared__ uint64_t lds[4];
     const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    if (fq_block_empty(a, n_real)) {
+        if (threadIdx.x == 0) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS] = 0;
+        return;
+    }
     const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     uint64_t v[1] = {0}, tot[1];
@@ -397,6 +410,8 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_scan_kernel(fq_args a)
     if (threadIdx.x == 0) {
         a.hdr[SK_FQ_H_PACKED] = run[0];
         a.offsets[a.n_pack] = run[0];
+        // the counted scan's batch ends at offsets[NREAL], and the place kernel's blocks beyond the records write nothing
+        if (a.counted) a.offsets[min(a.hdr[SK_FQ_H_NREAL], a.n_pack)] = run[0];
     }
 }
 
@@ -404,6 +419,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_place_kernel(fq_args a)
 {
     __shared__ uint64_t lds[4];
     const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    if (fq_block_empty(a, n_real)) return; // (offsets[NREAL] is the scan kernel's; nobody reads the offsets behind it)
     const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     uint64_t len[FQ_PER_THREAD];
@@ -466,6 +482,10 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_count_kernel(fq_args a)
 {
     __shared__ uint64_t lds[4 * 6];
     const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    if (fq_block_empty(a, n_real)) {
+        if (threadIdx.x < 6) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS + threadIdx.x] = 0;
+        return;
+    }
     const bool bad = a.hdr[SK_FQ_H_FMT] != ~0ull;
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     fq_emit_read rd[FQ_PER_THREAD];
@@ -516,6 +536,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_place_kernel(fq_args a)
     const bool fit[3] = {h[SK_FQ_H_FIT] != 0, h[SK_FQ_H_FIT + 1] != 0, h[SK_FQ_H_FIT + 2] != 0};
     if (!fit[0] && !fit[1] && !fit[2]) return; // uniform
     const uint64_t n_real = h[SK_FQ_H_NREAL];
+    if (fq_block_empty(a, n_real)) return;
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     fq_emit_read rd[FQ_PER_THREAD];
     fq_emit_load(a, first, n_real, false, rd);
@@ -679,7 +700,8 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int
             dbase += R;
             if (!h[SK_FQ_H_FIT + jb]) continue; // uniform
         } else {
-            j = {jb ? a.ps : a.pq, h[SK_FQ_H_PACKED], a.n_pack, a.offsets, 1, jb};
+            // (counted: the offsets end at offsets[NREAL] = the total; the reads behind are empty either way)
+            j = {jb ? a.ps : a.pq, h[SK_FQ_H_PACKED], a.counted ? min(h[SK_FQ_H_NREAL], a.n_pack) : a.n_pack, a.offsets, 1, jb};
         }
         if (j.total == 0) continue;
         const uint64_t n_chunks = (j.total + FQ_GCHUNK - 1) / FQ_GCHUNK;
@@ -854,15 +876,16 @@ __device__ __forceinline__ void fq_order_reads(const fq_args &a, const fq_order 
 }
 
 // fq_emit_load at the mapped reads
+// (cuts exist below n_cuts: n_pack, or NREAL behind the counted scan -- a read in between is empty, its cut {-1, -1})
 __device__ __forceinline__ void fq_order_emit_load(const fq_args &a, const uint64_t (&reads)[FQ_PER_THREAD], bool bad,
-                                                   fq_emit_read (&rd)[FQ_PER_THREAD])
+                                                   uint64_t n_cuts, fq_emit_read (&rd)[FQ_PER_THREAD])
 {
     bool kept[FQ_PER_THREAD];
     sk_cut_dev c[FQ_PER_THREAD];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j) {
         c[j] = {-1, -1};
-        if (!bad && reads[j] < a.n_pack) c[j] = a.cuts[reads[j]];
+        if (!bad && reads[j] < n_cuts) c[j] = a.cuts[reads[j]];
         kept[j] = c[j].three >= 0;
     }
 #pragma unroll
@@ -886,12 +909,16 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_a
 {
     __shared__ uint64_t lds[4 * 6];
     const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
+    if (fq_block_empty(a, n_real)) { // ranks at or beyond NREAL map to no read
+        if (threadIdx.x < 6) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS + threadIdx.x] = 0;
+        return;
+    }
     const bool bad = fq_order_bad(a.hdr);
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     uint64_t reads[FQ_PER_THREAD];
     fq_emit_read rd[FQ_PER_THREAD];
     fq_order_reads(a, o, first, bad ? 0 : n_real, reads);
-    fq_order_emit_load(a, reads, bad, rd);
+    fq_order_emit_load(a, reads, bad, a.counted ? n_real : a.n_pack, rd);
     uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j)
@@ -950,8 +977,9 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_a
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     uint64_t reads[FQ_PER_THREAD];
     fq_emit_read rd[FQ_PER_THREAD];
+    if (fq_block_empty(a, n_real)) return;
     fq_order_reads(a, o, first, n_real, reads);
-    fq_order_emit_load(a, reads, false, rd);
+    fq_order_emit_load(a, reads, false, a.counted ? n_real : a.n_pack, rd);
     uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j)
@@ -992,7 +1020,7 @@ uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
 }
 
 // shift: bytes between the header and the sections (an ordered call's batch table lies there)
-void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n,
+void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted,
                   const sk_fastq_output *out, void *workspace, const unsigned long long *errword, fq_args &a,
                   uint64_t shift = 0)
 {
@@ -1010,6 +1038,7 @@ void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int
     }
     a.mode = mode;
     a.trunc_n = trunc_n ? 1 : 0;
+    a.counted = counted ? 1 : 0;
     a.n_pack = sk_fq_pack_reads(a.bytes[0], a.bytes[1], mode);
     a.n_blocks = (a.n_pack + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
     a.hdr = static_cast<uint64_t *>(workspace);
@@ -1043,13 +1072,15 @@ fq_order fq_make_order(const sk_fastq_order *order, void *workspace)
 // NULL = in->bytes are the lengths; else the device words that hold them, in->bytes their bounds
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
                                                                                   const sk_fastq_lengths *lengths, int mode,
-                                                                                  int trunc_n, const sk_fastq_order *order,
+                                                                                  int trunc_n, int counted,
+                                                                                  const sk_fastq_order *order,
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
-                                                                                  sk_cut_dev **cuts)
+                                                                                  sk_cut_dev **cuts,
+                                                                                  const uint64_t **n_reads_dev)
 {
     fq_args a;
-    fq_make_args(in, lengths, mode, trunc_n, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
     const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
     if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
@@ -1072,18 +1103,19 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
     packed->stride = in->max_read_len;
     packed->n_reads = a.n_pack;
     *cuts = a.cuts;
+    *n_reads_dev = counted ? a.hdr + SK_FQ_H_NREAL : nullptr; // written by the frame scan / the ordered chain, before the pack
     return hipGetLastError();
 }
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
-                                                                                 const sk_fastq_order *order,
+                                                                                 int counted, const sk_fastq_order *order,
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream)
 {
     fq_args a;
     // no emission kernel looks at a text's length: lines and records come from the descriptors and the header
-    fq_make_args(in, nullptr, mode, trunc_n, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
     const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
     if (order) {
         const fq_order o = fq_make_order(order, workspace);

@@ -442,6 +442,17 @@ __device__ __forceinline__ uint32_t scalar_load(const uint32_t *p)
     return v;
 }
 
+// Counted scans (a.n_reads_dev != NULL): the reads this scan covers -- the device word, bounded by the host's a.n_reads.
+// One load per wave through the scalar cache: the word was written by a kernel before this one, and the result is one
+// value per wave (grids, scratch and LDS were sized for the bound on the host).  A kernel lowers ITS copy of a.n_reads
+// to this at its top and returns when it is 0: everything below -- rag_probe, rag_batch_end, a.n_reads - 1 -- reads
+// the copy as it does in a plain scan.
+__device__ __forceinline__ uint64_t sk_counted_reads(const uint64_t *n_reads_dev, uint64_t bound)
+{
+    if (!n_reads_dev) return bound;
+    return min((uint64_t)scalar_load(reinterpret_cast<const unsigned long long *>(n_reads_dev)), bound);
+}
+
 // what a wave needs to know about one tile
 struct sk_tile_view {
     uint64_t off;    // wave-uniform: byte offset of the tile (of its first read) in qual / seq

@@ -1176,6 +1176,12 @@ sk_scan_tile_any_kernel(const uint8_t *__restrict__ qual, const uint8_t *__restr
     // a ragged batch that went through the regrouping (sk_sort.hip) and turned out mixed, without reads too long for
     // the tiles, is the sorted scan's (enqueued right behind; it asks the opposite question)
     if (!UNIFORM && a.sort_flags && scalar_load(a.sort_flags) != 0 && scalar_load(a.sort_flags + 1) == 0) return;
+    // a counted scan: the tiles of the reads below the device's count (here, not in the body the other tile kernels share);
+    // none: no tile is skipped, so the hand-over words keep an earlier scan's number and the general kernel returns too
+    if (!UNIFORM) {
+        a.n_reads = sk_counted_reads(a.n_reads_dev, a.n_reads);
+        if (a.n_reads == 0) return;
+    }
     sk_scan_tile_body<UNIFORM, HAS_SEQ, MFMA, 1, 0, false, 0, true>(qual, seq, lengths, out, errword, a, nullptr, nullptr, offsets);
 }
 
@@ -1188,6 +1194,8 @@ sk_scan_tile_sorted_kernel(const uint8_t *__restrict__ qual, const uint8_t *__re
                            sk_cut_dev *__restrict__ out, unsigned long long *errword, sk_scan_args a)
 {
     if (scalar_load(a.sort_flags) == 0 || scalar_load(a.sort_flags + 1) != 0) return; // a uniform batch, or one with long reads
+    a.n_reads = sk_counted_reads(a.n_reads_dev, a.n_reads); // (a counted scan: the batch ends at offsets[that])
+    if (a.n_reads == 0) return;
     sk_scan_tile_body<false, HAS_SEQ, true, 1, 0, false, 0, true, true>(qual, seq, counts, out, errword, a, reinterpret_cast<const sk_tile_dev *>(lists),
                                                                          reinterpret_cast<const uint32_t *>(perm), offsets);
 }

@@ -29,10 +29,15 @@
 
 // the first eighth of every window: do its reads differ in length?
 __global__ void __launch_bounds__(256)
-sk_sort_sample_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, uint32_t *__restrict__ counts, uint32_t *__restrict__ counts_of_next_scan)
+sk_sort_sample_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, const uint64_t *__restrict__ n_reads_dev,
+                      uint32_t *__restrict__ counts, uint32_t *__restrict__ counts_of_next_scan)
 {
     if (blockIdx.x == 0 && threadIdx.x < 16) counts_of_next_scan[threadIdx.x] = 0; // (this scan's were cleared by the scan before)
     const uint64_t r0 = (uint64_t)blockIdx.x * SK_SORT_WINDOW;
+    // a counted scan: the verdict is about the reads below the device's count -- the empty reads a bound leaves behind
+    // them must not make a batch of one length a mixed one; a window at or beyond the count loads nothing
+    n_reads = sk_counted_reads(n_reads_dev, n_reads);
+    if (r0 >= n_reads) return;
     const uint32_t m = (uint32_t)min((uint64_t)(SK_SORT_WINDOW / 8), n_reads - r0);
     const uint64_t first = offsets[r0 + 1] - offsets[r0];
     bool differs = false;
@@ -49,7 +54,8 @@ sk_sort_sample_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, ui
 // two or three neighbouring waves' stretches of the window, ~200 KB instead of the window's 1.5 MB.
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS)
-sk_sort_windows_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, uint32_t max_len, uint64_t *__restrict__ perm,
+sk_sort_windows_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, const uint64_t *__restrict__ n_reads_dev, uint32_t max_len,
+                       uint64_t *__restrict__ perm,
                        unsigned long long *__restrict__ lists, uint32_t list_cap, uint32_t *__restrict__ counts /* [8] tiles per list, [8] flags[0], [9] flags[1] */)
 {
     constexpr int W = SK_SORT_WINDOW, PER = W / THREADS, NC = 64, NW = THREADS / 64, NT = W / 64 + NC; // NT: more tiles than a window can have
@@ -58,6 +64,8 @@ sk_sort_windows_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, u
     __shared__ uint32_t rel[W + 1]; // the window's offsets relative to its first (loaded lane by lane, read 9 per thread)
     const int t = threadIdx.x, wave = t >> 6;
     const uint64_t widx = blockIdx.x, r0 = widx * W;
+    n_reads = sk_counted_reads(n_reads_dev, n_reads); // a counted scan: the windows of the reads below the device's count
+    if (r0 >= n_reads) return;
     const uint64_t wstart = offsets[r0]; // (issued with the verdict's load, not behind it)
     if (counts[8] == 0) return; // a batch of one length (as far as the sample saw): nothing to regroup
     const uint32_t m = (uint32_t)min((uint64_t)W, n_reads - r0);
@@ -167,15 +175,23 @@ sk_sort_windows_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, u
     }
 }
 
+// n_reads_dev: NULL, or the device word of a counted scan (n_reads is then the bound the grid is sized by)
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sort_counted(const uint64_t *offsets, uint64_t n_reads, const uint64_t *n_reads_dev,
+                                     uint32_t max_len, uint64_t *perm, unsigned long long *lists, uint32_t list_cap, uint32_t *counts,
+                                     uint32_t *counts_of_next_scan, hipStream_t stream)
+{
+    const uint64_t windows = (n_reads + SK_SORT_WINDOW - 1) / SK_SORT_WINDOW;
+    hipLaunchKernelGGL(sk_sort_sample_kernel, dim3((unsigned)windows), dim3(256), 0, stream, offsets, n_reads, n_reads_dev, counts, counts_of_next_scan);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sk_sort_windows_kernel<1024>, dim3((unsigned)windows), dim3(1024), 0, stream, offsets, n_reads, n_reads_dev, max_len, perm, lists,
+                       list_cap, counts);
+    return hipGetLastError();
+}
+
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_sort(const uint64_t *offsets, uint64_t n_reads, uint32_t max_len, uint64_t *perm,
                                      unsigned long long *lists, uint32_t list_cap, uint32_t *counts, uint32_t *counts_of_next_scan,
                                      hipStream_t stream)
 {
-    const uint64_t windows = (n_reads + SK_SORT_WINDOW - 1) / SK_SORT_WINDOW;
-    hipLaunchKernelGGL(sk_sort_sample_kernel, dim3((unsigned)windows), dim3(256), 0, stream, offsets, n_reads, counts, counts_of_next_scan);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sk_sort_windows_kernel<1024>, dim3((unsigned)windows), dim3(1024), 0, stream, offsets, n_reads, max_len, perm, lists,
-                       list_cap, counts);
-    return hipGetLastError();
+    return sk_launch_sort_counted(offsets, n_reads, nullptr, max_len, perm, lists, list_cap, counts, counts_of_next_scan, stream);
 }

@@ -87,6 +87,9 @@ sk_scan_stream_kernel(const uint8_t *__restrict__ qual, const uint8_t *__restric
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x; // single-wave workgroups
+    // a counted scan: spans, runs of 8 and the count of tiles left (word 6 below) over the reads below the device's count
+    a.n_reads = sk_counted_reads(a.n_reads_dev, a.n_reads);
+    if (a.n_reads == 0) return;
     const int NB = (int)a.stream_nb;
     const uint32_t ring_bytes = (uint32_t)NB * 1024u;
     // P16 of the chunks behind the scan, indexed by chunk number modulo the table size (a power of two)

@@ -32,6 +32,8 @@ sk_scan_team_kernel(const uint8_t *__restrict__ qual, const uint8_t *__restrict_
     static_assert(TEAM == 16 || TEAM == 64, "teams of 16 or 64 lanes");
     constexpr int RPW = 64 / TEAM; // reads per wave
     constexpr bool SKIP = TEAM == 64; // whole-wave teams: prefix table + skip-ahead window search (see do_slot)
+    a.n_reads = sk_counted_reads(a.n_reads_dev, a.n_reads); // a counted scan: the slots and runs below the device's count
+    if (a.n_reads == 0) return;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x; // single-wave workgroups
     const int g = lane / TEAM, tl = lane % TEAM;
