@@ -378,7 +378,9 @@ size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n);
 /* Enqueues the trim of the FASTQ text(s) of *in.  Returns SK_EINVAL for bad arguments, without enqueueing anything. */
 int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
                                const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream);
-/* Waits for hip_stream and fills *counts: SK_OK, SK_EFORMAT, SK_ERANGE or SK_ESPACE (in this order of precedence). */
+/* Waits for hip_stream and fills *counts: SK_OK, SK_EFORMAT, SK_ERANGE or SK_ESPACE (in this order of precedence).
+ * The range verdict is the stream's error word as it is when this call reads it: with several text calls in flight on one
+ * stream, use sk_trim_fastq_piece_device_async and its finish, which takes every verdict from its own workspace. */
 int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts);
 
 /*
@@ -730,6 +732,111 @@ int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, con
  */
 int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_batch *batch,
                                  const uint64_t *n_reads_dev, sk_cut *out, void *hip_stream);
+
+/*
+ * The FASTQ trim in pieces: a text longer than one call's workspace allows is trimmed as a sequence of calls, each on a
+ * PIECE of the stream, and what a piece does not consume (the CARRY: an incomplete record, an unpaired one) becomes the
+ * front of the next piece's text -- without the host learning anything in between: the window's start, the lengths and the
+ * carry are device words, and a finish is the only call that waits.  Read order only (the -a T order is a property of the
+ * whole file).  This comment is the normative text.
+ *
+ * sk_trim_fastq_piece_device_async is sk_trim_fastq_chained_device_async(.., order = NULL, ..), and everything said there
+ * holds (the workspace is sk_trim_fastq_workspace_bytes(bytes[0] + bytes[1], trunc_n), everything sized on the host is a
+ * function of in->bytes), with what follows.  piece == NULL is that call bit for bit: the same launches, nothing more
+ * loaded, finished by sk_trim_fastq_device_finish.  A call with a piece is finished by sk_trim_fastq_piece_device_finish.
+ * Window.  n_i is text i's length as the chained call defines it (in->bytes, bytes_dev, valid_dev).  s_i = min(*start_dev[i],
+ * n_i), or 0 for a NULL word.  Text i of the call is text[i][s_i, n_i): the first line starts at s_i, no 16-byte block
+ * without a byte of the window is loaded, and no byte outside it bears on anything.  Offsets the call reports (consumed,
+ * end) count from text[i].  A start at or beyond n_i is an empty text.
+ * more == 0 (the stream's last piece).  Every count, verdict and output is what sk_trim_fastq_device_async gives on the
+ * texts text[i][s_i, n_i): the closed unterminated last line, SK_FQ_PAIR_COUNT and dropped_unpaired included.
+ * consumed = n_i.
+ * more != 0.  A line exists only if its '\n' lies in the window; the bytes behind the last '\n' are no line and are not
+ * closed.  With r_i = lines_i / 4 the piece takes u records from each input: SK_TRIM_SE u = r_0; SK_TRIM_PE_INTERLEAVED
+ * u = r_0 & ~1; SK_TRIM_PE_SPLIT u = min(r_0, r_1).  Records [0, u) of each input are checked, packed, scanned, routed and
+ * emitted exactly as sk_trim_fastq_device_async does on a text made of those records alone (read numbers count from the
+ * piece's first record).  Everything behind them is the carry: not checked, not scanned, no format or range error comes
+ * from it; SK_FQ_PAIR_COUNT never occurs and dropped_unpaired is 0.  records_in[i] = u; tail_lines[i] = the complete lines
+ * carried, lines_i - 4u, which may exceed 3.  consumed_i = s_i when u == 0, else one past the '\n' of line 4u - 1.  A text
+ * with more records than the call has descriptor slots ends in SK_EFORMAT, as in the whole-text call (a malformed record
+ * lies among the consumed ones).
+ * The stream's range-error word.  The frame scan captures the word as it is when the piece begins.  If it is set -- an
+ * earlier call on the stream met a range error that no finish has cleared yet -- the piece is void: it takes no record
+ * (u = 0, nothing checked, scanned or emitted, so the earlier error stays as it is), ok = 0, and its finish returns
+ * SK_ERANGE with counts->range = that earlier error (its read number is the earlier call's) and inherited_range = 1.
+ * Words on the stream.  sk_trim_fastq_piece_words(workspace, input, ..) gives the device addresses, inside the workspace's
+ * header, of the words the call's kernels write (no device access, no wait; SK_EINVAL for a NULL argument or an input
+ * other than 0 / 1): *consumed_dev and *end_dev (= n_i) of that input, and *ok_dev, one word per call, the same through
+ * either input: 1 iff there is no format error, the range-error word was clear when the piece began and as its emission
+ * saw it, and every produced output fitted.  They are written by the emission's scan kernel, which takes those verdicts.
+ * sk_trim_fastq_piece_device_finish waits for hip_stream, fills *counts as sk_trim_fastq_device_finish does and
+ * *piece_counts (may be NULL), and clears the stream's range-error word as that call does -- but takes EVERY verdict
+ * from this workspace: the range error is the word this piece's emission captured, never the live word, so that pieces
+ * enqueued behind this one neither lend it their errors nor lose theirs to it.  It returns, in this order of precedence:
+ * SK_ERANGE with inherited_range = 1 (the piece was void), SK_EFORMAT, SK_ERANGE, SK_ESPACE, SK_OK.
+ * Bad arguments (those of the chained call; piece->reserved != 0; a start word that is not 8-byte aligned; a start word for
+ * text[1] outside SK_TRIM_PE_SPLIT) return SK_EINVAL and enqueue nothing.
+ */
+typedef struct {
+    const uint64_t *start_dev[2]; /* device, 8-byte aligned, or NULL (= 0): text i is bytes [*start_dev[i], n_i) of text[i] */
+    uint32_t more;                /* != 0: more text follows this piece */
+    uint32_t reserved;            /* 0 */
+} sk_fastq_piece;
+
+typedef struct {
+    uint64_t consumed[2];      /* offset in text[i] of the first byte the piece did not consume */
+    uint64_t carried_bytes[2]; /* n_i - consumed[i] */
+    uint32_t ok;               /* the word a carry behind this piece goes by */
+    uint32_t inherited_range;  /* 1: the stream's range-error word was set when the piece began; the piece was void */
+} sk_fastq_piece_counts;
+
+int sk_trim_fastq_piece_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                     const sk_fastq_lengths *lengths, const sk_fastq_piece *piece, int mode,
+                                     const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                     void *hip_stream);
+int sk_trim_fastq_piece_words(void *workspace, int input, const uint64_t **consumed_dev, const uint64_t **end_dev,
+                              const uint64_t **ok_dev);
+int sk_trim_fastq_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                      sk_fastq_piece_counts *piece_counts);
+
+/*
+ * The carry between two pieces: enqueued behind the previous piece, it moves what that piece did not consume of input
+ * `input` in front of the next chunk of text and writes the words the next piece takes its window from.  The caller (or a
+ * reader: room is a multiple of 16, so a reader's `out` can point there) puts the next chunk at next_text + room; its length
+ * is min(*chunk_bytes_dev, chunk_bytes), or chunk_bytes for a NULL word.
+ * With c = end - consumed of the piece that used prev_workspace, for `input` (prev_workspace == NULL, the first piece:
+ * c = 0, ok = 1), the kernel sets status to the first of these that applies:
+ *   1. prev_words != NULL and prev_words->status != 0:                    prev_words->status (sticky)
+ *   1b. other_prev_words != NULL and other_prev_words->status != 0:       other_prev_words->status
+ *   2. the previous piece's ok == 0:                                      1
+ *   3. c > room:                                                          2
+ *   4. chunk_valid_dev != NULL and *chunk_valid_dev == 0:                 3
+ *   5. none of these:                                                     0
+ * status == 0: prev_text[consumed, end) is copied to next_text[room - c, room) and *words = {room - c, room + chunk length,
+ * 1, 0}.  status != 0: nothing is copied and *words = {room, room, 0, status}: the next piece sees an empty text, and every
+ * later carry inherits the status: a stream that has failed never resumes behind the failure.
+ * The words feed the next piece: in.text = next_text, in.bytes = room + chunk_bytes, lengths.bytes_dev = &words->end,
+ * lengths.valid_dev = &words->valid, piece.start_dev = &words->start.
+ * SK_TRIM_PE_SPLIT runs one carry per input, each with the OTHER input's previous words as other_prev_words (NULL
+ * elsewhere): a status that only one input meets (its carry beyond room, its chunk invalid) empties that input's text at
+ * once -- the piece then takes no record from either input -- and reaches the other input's words at the next carry, from
+ * where both are sticky.
+ * Source and destination have any alignment.  No byte of next_text outside [room - c, room) is written, none of prev_text
+ * outside [consumed, end) is read.  prev_bytes is the previous piece's in->bytes[input]: the buffers must not overlap,
+ * and [next_text, next_text + room) meeting [prev_text, prev_text + prev_bytes) is SK_EINVAL, as are a NULL ctx, next_text
+ * or words, prev_workspace given without prev_text, an input other than 0 / 1, room not a multiple of 16, words that are not
+ * 8-byte aligned, and `words` being one of the two previous words (keep two sets and alternate).  One kernel is enqueued,
+ * its grid sized by room: no allocation, no copy, no wait.
+ */
+typedef struct {
+    uint64_t start, end, valid, status;
+} sk_fastq_carry_words; /* device memory, 8-byte aligned */
+
+int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int input, const uint8_t *prev_text,
+                                uint64_t prev_bytes, uint8_t *next_text, uint64_t room, const uint64_t *chunk_bytes_dev,
+                                uint64_t chunk_bytes, const uint64_t *chunk_valid_dev,
+                                const sk_fastq_carry_words *prev_words, const sk_fastq_carry_words *other_prev_words,
+                                sk_fastq_carry_words *words, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,8 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_gzip_inflate_device_finish", "sk_trim_fastq_ordered_workspace_bytes", "sk_trim_fastq_ordered_device_async",
            "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches",
            "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words",
-           "sk_scan_counted_device_async")
+           "sk_scan_counted_device_async", "sk_trim_fastq_piece_device_async", "sk_trim_fastq_piece_words",
+           "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async")
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
 
@@ -115,6 +116,23 @@ class FastqCounts(C.Structure):
                 "bytes": list(self.bytes), "format_error": int(self.format_error),
                 "format_input": int(self.format_input), "format_record": int(self.format_record),
                 "range": (int(self.range.read), int(self.range.pos), int(self.range.ch))}
+
+
+class FastqPiece(C.Structure):
+    _fields_ = [("start_dev", C.c_void_p * 2), ("more", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FastqPieceCounts(C.Structure):
+    _fields_ = [("consumed", C.c_uint64 * 2), ("carried_bytes", C.c_uint64 * 2), ("ok", C.c_uint32),
+                ("inherited_range", C.c_uint32)]
+
+    def as_dict(self):
+        return {"consumed": list(self.consumed), "carried_bytes": list(self.carried_bytes), "ok": int(self.ok),
+                "inherited_range": int(self.inherited_range)}
+
+
+class FastqCarryWords(C.Structure):
+    _fields_ = [("start", C.c_uint64), ("end", C.c_uint64), ("valid", C.c_uint64), ("status", C.c_uint64)]
 
 
 class FastqOrder(C.Structure):
@@ -305,6 +323,20 @@ def lib():
         L.sk_trim_fastq_chained_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput),
                                                          C.POINTER(FastqLengths), C.c_int, C.POINTER(FastqOrder),
                                                          C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_trim_fastq_piece_device_async.restype = C.c_int
+        L.sk_trim_fastq_piece_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput),
+                                                       C.POINTER(FastqLengths), C.POINTER(FastqPiece), C.c_int,
+                                                       C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_trim_fastq_piece_words.restype = C.c_int
+        L.sk_trim_fastq_piece_words.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p)]
+        L.sk_trim_fastq_piece_device_finish.restype = C.c_int
+        L.sk_trim_fastq_piece_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts),
+                                                        C.POINTER(FastqPieceCounts)]
+        L.sk_fastq_carry_device_async.restype = C.c_int
+        L.sk_fastq_carry_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
         L.sk_bgzf_inflate_output_words.restype = C.c_int
         L.sk_bgzf_inflate_output_words.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.sk_gzip_inflate_output_words.restype = C.c_int
@@ -584,6 +616,85 @@ class Context:
                                                              TRIM_MODES.get(mode, mode),
                                                              None if order is None else C.byref(order), arr,
                                                              workspace_ptr, workspace_bytes, stream))
+
+    # ---- FASTQ text in pieces ------------------------------------------------------------------
+    def trim_fastq_piece_device_async(self, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes,
+                                      bytes_dev_ptrs=(), valid_dev_ptrs=(), start_dev_ptrs=(), more=False, mode="se",
+                                      max_read_len=0, stream=None, piece=True):
+        """sk_trim_fastq_piece_device_async on raw device pointers: trim_fastq_chained_device_async (read order) on the
+        window that starts at the device words start_dev_ptrs (None = 0); more: more text follows, so only whole records
+        (pairs) are taken and the rest is the carry.  piece=False passes piece == NULL: the chained call itself."""
+        pad = lambda xs, fill: list(xs) + [fill] * (2 - len(xs))
+        inp = FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), max_read_len)
+        lengths = FastqLengths((C.c_void_p * 2)(*pad(bytes_dev_ptrs, None)), (C.c_void_p * 2)(*pad(valid_dev_ptrs, None)))
+        pc = FastqPiece((C.c_void_p * 2)(*pad(start_dev_ptrs, None)), 1 if more else 0, 0)
+        arr = (FastqOutput * 3)(*list(outs)[:3])
+        self._check(lib().sk_trim_fastq_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
+                                                           C.byref(pc) if piece else None, TRIM_MODES.get(mode, mode), arr,
+                                                           workspace_ptr, workspace_bytes, stream))
+
+    def _piece_finish(self, workspace_ptr, stream):
+        c, pc = FastqCounts(), FastqPieceCounts()
+        rc = lib().sk_trim_fastq_piece_device_finish(self._h, workspace_ptr, stream, C.byref(c), C.byref(pc))
+        return rc, c, dict(c.as_dict(), piece=pc.as_dict())
+
+    def trim_fastq_piece_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_fastq_piece_device_finish -> counts (dict, with the piece counts under "piece"); raises FormatError,
+        RangeError (an inherited one too: counts["piece"]["inherited_range"] is not seen then) or TrimError (SK_ESPACE)."""
+        rc, c, counts = self._piece_finish(workspace_ptr, stream)
+        if rc == SK_EFORMAT:
+            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
+        self._check(rc, c.range)
+        return counts
+
+    @staticmethod
+    def trim_fastq_piece_words(workspace_ptr, input):
+        """sk_trim_fastq_piece_words -> (consumed_dev, end_dev, ok_dev) device addresses of a piece's words."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if lib().sk_trim_fastq_piece_words(workspace_ptr, input, C.byref(a), C.byref(b), C.byref(c)) != SK_OK:
+            raise SickleError("sk_trim_fastq_piece_words: bad arguments")
+        return a.value, b.value, c.value
+
+    def fastq_carry_device_async(self, prev_workspace_ptr, input, prev_text_ptr, prev_bytes, next_text_ptr, room, words_ptr,
+                                 chunk_bytes=0, chunk_bytes_dev_ptr=None, chunk_valid_dev_ptr=None, prev_words_ptr=None,
+                                 other_prev_words_ptr=None, stream=None):
+        """sk_fastq_carry_device_async on raw device pointers (words: a FastqCarryWords in device memory)."""
+        self._check(lib().sk_fastq_carry_device_async(self._h, prev_workspace_ptr, input, prev_text_ptr, prev_bytes,
+                                                      next_text_ptr, room, chunk_bytes_dev_ptr, chunk_bytes,
+                                                      chunk_valid_dev_ptr, prev_words_ptr, other_prev_words_ptr, words_ptr,
+                                                      stream))
+
+    def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
+                          search=False, max_read_len=0):
+        """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
+        and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
+        or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
+        FastqStream: iterating it yields, per piece, the tuple of the three outputs as bytes (None where the mode has no
+        such output); with gz=True each is a run of BGZF members, and only the last piece's carries the EOF member, so the
+        concatenation per output is one valid .gz file.  Afterwards .counts holds the summed counts (tail_lines and
+        dropped_unpaired are the last piece's) and .pieces the number of pieces; .device_bytes is what the driver
+        allocated, a function of piece_bytes and room alone: two text buffers per input, two workspaces, two sets of
+        outputs sized by the one-pass rule (and of images and writer workspaces), all reused.
+        Piece k + 1 is enqueued before piece k is finished and drained.  room (default piece_bytes, rounded up to 16) is
+        the longest carry: a record longer than it (or, in "pe_split", inputs that drift apart by more) ends the stream
+        with TrimError (SK_ESPACE) that names room.  A format or range error raises FormatError / RangeError at the first
+        failing piece, with stream-wide record / read numbers.  Unlike trim_fastq, a format error does not beat a range
+        error in an EARLIER piece: pieces are framed one by one, as the reference frames batch by batch."""
+        srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len)
+
+    def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
+                       max_read_len=0):
+        """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
+        each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
+        group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
+        words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
+        offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
+        (use trim_gz)."""
+        srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len)
 
     @staticmethod
     def trim_fastq_ordered_batches(workspace_ptr):
@@ -956,6 +1067,269 @@ class Context:
         if lib().sk_trim_fastq_output_words(fastq_workspace_ptr, output, C.byref(b), C.byref(w)) != SK_OK:
             raise SickleError("sk_trim_fastq_output_words: bad arguments")
         return b.value, w.value
+
+
+class _TextSource:
+    """bytes-like chunks of any sizes, re-cut on demand"""
+    compressed = False
+
+    def __init__(self, chunks):
+        if isinstance(chunks, (bytes, bytearray, memoryview, np.ndarray)):
+            chunks = [chunks]
+        self._it, self._buf, self._at = iter(chunks), None, 0
+
+    def more(self):
+        while self._buf is None or self._at >= len(self._buf):
+            try:
+                c = next(self._it)
+            except StopIteration:
+                return False
+            self._buf, self._at = (c if isinstance(c, np.ndarray) else np.frombuffer(c, dtype=np.uint8)).reshape(-1), 0
+        return True
+
+    def take(self, n):
+        """-> up to n bytes (uint8 array) and the text bytes they are"""
+        parts, got = [], 0
+        while got < n and self.more():
+            p = self._buf[self._at:self._at + (n - got)]
+            self._at += len(p)
+            got += len(p)
+            parts.append(p)
+        a = np.concatenate(parts) if len(parts) > 1 else (parts[0].copy() if parts else np.zeros(0, np.uint8))
+        return a, len(a)  # (a copy: the caller's buffer may be read-only)
+
+
+class _BgzfSource:
+    """a BGZF image on the host, cut into groups of whole members by their BSIZE and ISIZE fields"""
+    compressed = True
+
+    def __init__(self, image, piece_bytes):
+        self._im = (image if isinstance(image, np.ndarray) else np.frombuffer(image, dtype=np.uint8)).reshape(-1)
+        self._at = 0
+        self.group_cap = int(lib().sk_bgzf_bound(piece_bytes, SK_BGZF_EOF)) + 65536  # compressed bytes of a group
+        if piece_bytes < 65536:
+            raise ValueError("trim_gz_stream: piece_bytes must hold a BGZF member's text (65536)")
+        head = self._im[:16].tobytes()
+        if len(self._im) and not (head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00"):
+            raise ValueError("trim_gz_stream: not a BGZF image; plain gzip cannot be cut into pieces, use trim_gz")
+
+    def more(self):
+        return self._at < len(self._im)
+
+    def _member(self, at):
+        """-> (size, isize) of the member at `at`, or None if it does not frame (the reader will say why)"""
+        im = self._im
+        if at + 26 > len(im) or im[at:at + 4].tobytes() != b"\x1f\x8b\x08\x04" or im[at + 12:at + 16].tobytes() != b"BC\x02\x00":
+            return None
+        size = int(im[at + 16]) + (int(im[at + 17]) << 8) + 1
+        if size < 26 or at + size > len(im):
+            return None
+        return size, int.from_bytes(im[at + size - 4:at + size].tobytes(), "little")
+
+    def take(self, n):
+        """-> whole members of at most n bytes of text (one at least) and their ISIZE sum.  Bytes that do not frame as
+        described above go to the reader as they are, which reports them."""
+        start, text = self._at, 0
+        while self._at < len(self._im):
+            m = self._member(self._at)
+            if m is None:
+                if self._at == start:
+                    self._at = min(len(self._im), start + self.group_cap)
+                break
+            if self._at > start and (text + m[1] > n or self._at + m[0] - start > self.group_cap):
+                break
+            self._at += m[0]
+            text += m[1]
+        return self._im[start:self._at].copy(), text
+
+
+class FastqStream:
+    """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
+
+    def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len):
+        import torch
+        if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
+            raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
+        if piece_bytes < 1:
+            raise ValueError("piece_bytes must be positive")
+        self.ctx, self.params, self.src, self.mode = ctx, params, sources, mode
+        self.piece_bytes = int(piece_bytes)
+        self.room = ((self.piece_bytes if room is None else int(room)) + 15) & ~15
+        self.gz, self.search, self.max_read_len = gz, search, max_read_len
+        self.used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        self.counts = {"records_in": [0, 0], "tail_lines": [0, 0], "dropped_unpaired": 0, "records": [0, 0, 0],
+                       "bytes": [0, 0, 0]}
+        self.pieces = 0
+        L, n_in, dev = lib(), len(sources), "cuda"
+        self.device_bytes = 0
+
+        def alloc(n):
+            self.device_bytes += max(n, 16)
+            return torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
+        cap_in = self.room + self.piece_bytes
+        self.text = [[alloc(cap_in + 16) for _ in range(2)] for _ in range(n_in)]
+        self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
+        self.ws = [alloc(self.ws_bytes) for _ in range(2)]
+        self.out_cap = n_in * cap_in + 2
+        self.out = [[alloc(self.out_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
+        self.words = torch.zeros((n_in, 2, 4), dtype=torch.int64, device=dev)
+        self.device_bytes += self.words.numel() * 8
+        if gz:
+            self.img_cap = L.sk_bgzf_bound(self.out_cap, SK_BGZF_EOF)
+            self.zws_bytes = L.sk_bgzf_workspace_bytes_flags(self.out_cap, SK_BGZF_SEARCH if search else 0)
+            self.img = [[alloc(self.img_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
+            self.zws = [[alloc(self.zws_bytes) if o in self.used else None for o in range(3)] for _ in range(2)]
+        if sources[0].compressed:
+            self.rws_bytes = L.sk_bgzf_inflate_workspace_bytes(sources[0].group_cap)
+            self.comp = [[alloc(sources[0].group_cap) for _ in range(2)] for _ in range(n_in)]
+            self.rws = [[alloc(self.rws_bytes) for _ in range(2)] for _ in range(n_in)]
+        self.stream = torch.cuda.current_stream().cuda_stream
+        self._gen = self._run()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._gen)
+
+    def _words_ptr(self, i, slot):
+        return self.words.data_ptr() + 32 * (2 * i + slot)
+
+    def _enqueue(self, k, carried):
+        """upload (and inflate) the next chunk of every input, then carry and piece k (and its writers)"""
+        import torch
+        c, slot, prev = self.ctx, k & 1, (k - 1) & 1
+        n_in = len(self.src)
+        bounds, readers, taken = [], [], [0, 0]
+        # split inputs: an input that carries more than the other gets that much less text, or the one with the shorter
+        # records piles its carry up; of the inputs that still have text the one that carries least gets a whole piece, so
+        # the stream always moves on
+        active = [carried[i] for i, s in enumerate(self.src) if s.more()]
+        least = min(active) if active else 0
+        for i, s in enumerate(self.src):
+            target = max(self.piece_bytes - max(carried[i] - least, 0), 0)
+            data, text_bytes = s.take(target) if target or s.compressed else (np.zeros(0, np.uint8), 0)
+            taken[i] = text_bytes
+            buf = self.text[i][slot]
+            nb_dev = valid_dev = None
+            if s.compressed:
+                if text_bytes > self.piece_bytes:
+                    raise ValueError("trim_gz_stream: a member holds %d bytes of text, beyond piece_bytes" % text_bytes)
+                chunk = self.piece_bytes if len(data) else 0
+                if len(data):
+                    self.comp[i][slot][:len(data)].copy_(torch.from_numpy(data), non_blocking=False)
+                    c.bgzf_inflate_device_async(self.comp[i][slot].data_ptr(), len(data), buf.data_ptr() + self.room, chunk,
+                                                self.rws[i][slot].data_ptr(), self.rws_bytes, stream=self.stream)
+                    nb_dev, valid_dev = c.bgzf_inflate_output_words(self.rws[i][slot].data_ptr())
+                    readers.append((i, self.rws[i][slot]))
+            else:
+                chunk = len(data)
+                if chunk:
+                    buf[self.room:self.room + chunk].copy_(torch.from_numpy(data), non_blocking=False)
+            c.fastq_carry_device_async(self.ws[prev].data_ptr() if k else None, i, self.text[i][prev].data_ptr() if k else None,
+                                       self._bounds[i] if k else 0, buf.data_ptr(), self.room, self._words_ptr(i, slot),
+                                       chunk_bytes=chunk, chunk_bytes_dev_ptr=nb_dev, chunk_valid_dev_ptr=valid_dev,
+                                       prev_words_ptr=self._words_ptr(i, prev) if k else None,
+                                       other_prev_words_ptr=self._words_ptr(1 - i, prev) if k and n_in == 2 else None,
+                                       stream=self.stream)
+            bounds.append(self.room + chunk)
+        self._bounds = bounds
+        more = any(s.more() for s in self.src)
+        outs = [FastqOutput(t.data_ptr(), self.out_cap, None, 0) if t is not None else FastqOutput() for t in self.out[slot]]
+        c.trim_fastq_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds, outs,
+                                        self.ws[slot].data_ptr(), self.ws_bytes,
+                                        bytes_dev_ptrs=[self._words_ptr(i, slot) + 8 for i in range(n_in)],
+                                        valid_dev_ptrs=[self._words_ptr(i, slot) + 16 for i in range(n_in)],
+                                        start_dev_ptrs=[self._words_ptr(i, slot) for i in range(n_in)], more=more,
+                                        mode=self.mode, max_read_len=self.max_read_len, stream=self.stream)
+        if self.gz:
+            for o in self.used:
+                b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
+                c.bgzf_device_async(self.out[slot][o].data_ptr(), self.out_cap, self.img[slot][o].data_ptr(), self.img_cap,
+                                    self.zws[slot][o].data_ptr(), self.zws_bytes, eof=not more, bytes_dev_ptr=b,
+                                    valid_dev_ptr=w, stream=self.stream, search=self.search)
+        return {"k": k, "slot": slot, "more": more, "readers": readers, "taken": taken}
+
+    def _finish(self, p):
+        """wait for piece p, raise what it met, sum its counts; -> (outputs, bytes carried per input)"""
+        c, slot = self.ctx, p["slot"]
+        for i, rws in p["readers"]:
+            c.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
+        rc, raw, counts = c._piece_finish(self.ws[slot].data_ptr(), self.stream)
+        status = [int(x) for x in self.words[:, slot, 3].cpu().tolist()]
+        if 2 in status:
+            raise TrimError("fastq stream: input %d carries more than room = %d bytes into piece %d (a longer record, or "
+                            "split inputs that drift apart): pass a larger room" % (status.index(2), self.room, p["k"]),
+                            SK_ESPACE, counts)
+        base_reads = self._reads
+        per_input = base_reads // 2 if self.mode == "pe_split" else base_reads
+        if rc == SK_EFORMAT:
+            raise FormatError(int(raw.format_error), int(raw.format_input), int(raw.format_record) + per_input, counts)
+        if rc == SK_ERANGE:
+            raise RangeError(int(raw.range.read) + (0 if counts["piece"]["inherited_range"] else base_reads),
+                             int(raw.range.pos), int(raw.range.ch))
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(c._h).decode()), rc, counts)
+        c._check(rc)
+        if any(status):
+            raise SickleError("fastq stream: piece %d follows a failed carry (status %r)" % (p["k"], status))
+        res = [None] * 3
+        for o in self.used:
+            if self.gz:
+                n = c.bgzf_device_finish(self.zws[slot][o].data_ptr(), self.stream)["bytes_out"]
+                res[o] = self.img[slot][o][:n].cpu().numpy().tobytes()
+            else:
+                res[o] = self.out[slot][o][:counts["bytes"][o]].cpu().numpy().tobytes()
+        for key in ("records_in", "records", "bytes"):
+            self.counts[key] = [a + b for a, b in zip(self.counts[key], counts[key])]
+        self.counts["tail_lines"], self.counts["dropped_unpaired"] = counts["tail_lines"], counts["dropped_unpaired"]
+        self._reads += counts["records_in"][0] * (2 if self.mode == "pe_split" else 1)
+        if not p["more"] and self.mode == "pe_interleaved":
+            self._reads -= counts["dropped_unpaired"]
+        self.pieces += 1
+        carried = counts["piece"]["carried_bytes"]
+        # what the piece consumed of each input: what it was handed (the carry before it and its chunk) less what it carried
+        self._known = (p["k"], carried, [a + b - c for a, b, c in zip(self._carried_in, p["taken"], carried)])
+        self._carried_in = carried
+        return tuple(res)
+
+    def _estimate(self, last):
+        """bytes each input carries into the piece behind piece `last` (enqueued): what the last finished piece carried,
+        and, if that is the piece before `last`, plus last's chunk less what the finished piece consumed (the steady
+        state's consumption: a piece in flight has not told yet)"""
+        k, carried, consumed = self._known
+        if k == last["k"]:
+            return carried
+        return [max(c + t - u, 0) for c, t, u in zip(carried, last["taken"], consumed)]
+
+    def _run(self):
+        self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])
+        estimate, pending, k = [0, 0], None, 0
+        try:
+            while True:
+                nxt = self._enqueue(k, estimate)
+                if pending is not None:
+                    done, pending = pending, nxt
+                    yield self._finish(done)
+                pending = nxt
+                if not nxt["more"]:
+                    break
+                if k == 0 and len(self.src) == 2:  # split inputs: piece 1 is sized by what piece 0 carried, not by a guess
+                    done, pending = pending, None
+                    yield self._finish(done)
+                estimate = self._estimate(nxt) if self._known[0] >= 0 else [0, 0]
+                k += 1
+            if pending is not None:
+                done, pending = pending, None
+                yield self._finish(done)
+        finally:
+            if pending is not None:  # a piece still in flight behind a failure: wait for it and clear the stream's error word
+                for i, rws in pending["readers"]:
+                    try:
+                        self.ctx.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
+                    except SickleError:
+                        pass
+                self.ctx._piece_finish(self.ws[pending["slot"]].data_ptr(), self.stream)
 
 
 BGZF_INPUT = 65280   # bytes of text per BGZF block

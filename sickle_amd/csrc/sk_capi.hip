@@ -793,10 +793,10 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
 } // namespace
 
 namespace {
-// both FASTQ calls; order: NULL = read order
+// both FASTQ calls; order: NULL = read order; piece: NULL = the whole text (else order is NULL)
 int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
                 const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
-                void *workspace, size_t workspace_bytes, void *hip_stream)
+                void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr)
 {
     int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
                               order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
@@ -811,6 +811,20 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
         }
         if (mode != SK_TRIM_PE_SPLIT && (lengths->bytes_dev[1] || lengths->valid_dev[1])) {
             set_error(ctx, "fastq: bytes_dev[1] and valid_dev[1] are only for SK_TRIM_PE_SPLIT");
+            return SK_EINVAL;
+        }
+    }
+    if (piece) {
+        if (piece->reserved != 0) {
+            set_error(ctx, "fastq: piece->reserved must be 0");
+            return SK_EINVAL;
+        }
+        if ((reinterpret_cast<uintptr_t>(piece->start_dev[0]) | reinterpret_cast<uintptr_t>(piece->start_dev[1])) & 7) {
+            set_error(ctx, "fastq: start_dev must be 8-byte aligned");
+            return SK_EINVAL;
+        }
+        if (mode != SK_TRIM_PE_SPLIT && piece->start_dev[1]) {
+            set_error(ctx, "fastq: start_dev[1] is only for SK_TRIM_PE_SPLIT");
             return SK_EINVAL;
         }
     }
@@ -832,11 +846,12 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     const char *counted_env = getenv("SK_FQ_COUNTED");
     const int counted = !(counted_env && *counted_env == '0');
     const uint64_t *n_reads_dev = nullptr;
-    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, workspace, ctx->cu_count, stream, &packed,
-                                      &cuts, &n_reads_dev));
+    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, piece, d_err, workspace, ctx->cu_count,
+                                      stream, &packed, &cuts, &n_reads_dev));
     rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, out, workspace, d_err, ctx->cu_count, stream));
+    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, out, workspace, d_err,
+                                     ctx->cu_count, stream));
     return SK_OK;
 }
 } // namespace
@@ -965,6 +980,126 @@ int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, con
     if (order) return fastq_ordered_async(ctx, params, in, lengths, mode, order, out, workspace, workspace_bytes, hip_stream);
     return fastq_async(ctx, "sk_trim_fastq_chained_device_async", params, in, lengths, mode, nullptr, out, workspace,
                        workspace_bytes, hip_stream);
+}
+
+int sk_trim_fastq_piece_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                     const sk_fastq_lengths *lengths, const sk_fastq_piece *piece, int mode,
+                                     const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                     void *hip_stream)
+{
+    return fastq_async(ctx, piece ? "sk_trim_fastq_piece_device_async" : "sk_trim_fastq_chained_device_async", params, in, lengths,
+                       mode, nullptr, out, workspace, workspace_bytes, hip_stream, piece);
+}
+
+int sk_trim_fastq_piece_words(void *workspace, int input, const uint64_t **consumed_dev, const uint64_t **end_dev,
+                              const uint64_t **ok_dev)
+{
+    if (!workspace || input < 0 || input > 1 || !consumed_dev || !end_dev || !ok_dev) return SK_EINVAL;
+    const uint64_t *hdr = static_cast<const uint64_t *>(workspace);
+    *consumed_dev = hdr + SK_FQP_H_CONSUMED + input;
+    *end_dev = hdr + SK_FQP_H_END + input;
+    *ok_dev = hdr + SK_FQP_H_OK;
+    return SK_OK;
+}
+
+// Every verdict from the workspace's own words: the range error is the word the piece's emission captured
+// (SK_FQ_H_RANGE), or the one its frame scan found already set (SK_FQP_H_RANGE0).  The stream's live word is cleared, as
+// fastq_finish does, and never read.
+int sk_trim_fastq_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                      sk_fastq_piece_counts *pc)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    int rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    uint64_t h[SK_FQ_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    rc = reset_error_word(ctx, d_err, stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    *counts = sk_fastq_counts{};
+    const bool more = h[SK_FQP_H_MORE] != 0, split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
+    const bool inherited = h[SK_FQP_H_RANGE0] != ~0ull;
+    for (int i = 0; i < 2; ++i) {
+        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
+        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] - 4 * h[SK_FQ_H_RECORDS + i]; // a piece carries whole records too
+    }
+    const uint64_t fmt = h[SK_FQ_H_FMT];
+    const bool bad = fmt != ~0ull;
+    counts->dropped_unpaired = !more && h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
+    for (int o = 0; o < 3; ++o) {
+        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
+        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
+    }
+    if (pc) {
+        *pc = sk_fastq_piece_counts{};
+        for (int i = 0; i < 2; ++i) {
+            pc->consumed[i] = h[SK_FQP_H_CONSUMED + i];
+            pc->carried_bytes[i] = h[SK_FQP_H_END + i] - h[SK_FQP_H_CONSUMED + i];
+        }
+        pc->ok = (uint32_t)h[SK_FQP_H_OK];
+        pc->inherited_range = inherited;
+    }
+    if (inherited) {
+        decode_error(h[SK_FQP_H_RANGE0], &counts->range);
+        set_error(ctx, "fastq: an earlier call on the stream left a range error (read %u of that call); the piece took no record",
+                  counts->range.read);
+        return SK_ERANGE;
+    }
+    if (bad) {
+        const uint64_t read = fmt >> 3;
+        counts->format_error = (int32_t)(fmt & 7);
+        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
+        counts->format_record = split ? read >> 1 : read;
+        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
+                  (unsigned long long)counts->format_record, counts->format_error);
+        return SK_EFORMAT;
+    }
+    if (decode_error(h[SK_FQ_H_RANGE], &counts->range) == SK_ERANGE) {
+        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
+                  counts->range.pos + 1);
+        return SK_ERANGE;
+    }
+    for (int o = 0; o < 3; ++o)
+        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
+    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
+    return rc;
+}
+
+int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int input, const uint8_t *prev_text,
+                                uint64_t prev_bytes, uint8_t *next_text, uint64_t room, const uint64_t *chunk_bytes_dev,
+                                uint64_t chunk_bytes, const uint64_t *chunk_valid_dev,
+                                const sk_fastq_carry_words *prev_words, const sk_fastq_carry_words *other_prev_words,
+                                sk_fastq_carry_words *words, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+#define SK_FQC_BAD(...)               \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!next_text || !words) SK_FQC_BAD("carry: next_text and words are required");
+    if (input < 0 || input > 1) SK_FQC_BAD("carry: input is 0 or 1");
+    if (prev_workspace && !prev_text) SK_FQC_BAD("carry: prev_text is required with prev_workspace");
+    if (room & 15) SK_FQC_BAD("carry: room must be a multiple of 16");
+    uintptr_t w = reinterpret_cast<uintptr_t>(chunk_bytes_dev) | reinterpret_cast<uintptr_t>(chunk_valid_dev) |
+                  reinterpret_cast<uintptr_t>(prev_words) | reinterpret_cast<uintptr_t>(other_prev_words) |
+                  reinterpret_cast<uintptr_t>(words) | reinterpret_cast<uintptr_t>(prev_workspace);
+    if (w & 7) SK_FQC_BAD("carry: the device words and prev_workspace must be 8-byte aligned");
+    if (words == prev_words || words == other_prev_words) SK_FQC_BAD("carry: words must not be one of the previous words");
+    if (prev_workspace) {
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(prev_text), p1 = p0 + prev_bytes;
+        const uintptr_t n0 = reinterpret_cast<uintptr_t>(next_text), n1 = n0 + room;
+        if (p0 < n1 && n0 < p1) SK_FQC_BAD("carry: [next_text, next_text + room) overlaps the previous text");
+    }
+#undef SK_FQC_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_carry(static_cast<const uint64_t *>(prev_workspace), input, prev_text, next_text, room,
+                                      chunk_bytes_dev, chunk_bytes, chunk_valid_dev, prev_words, other_prev_words, words,
+                                      static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
 }
 
 int sk_trim_fastq_ordered_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,

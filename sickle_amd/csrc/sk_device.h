@@ -168,6 +168,14 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 #define SK_FQ_H_PRODUCED 16    // [3] out[o].text != NULL for an output of the mode
 #define SK_FQ_H_RANGE 19       // the stream's range-error word as the emission saw it
 #define SK_FQ_H_MODE 20        // the call's mode
+// Piece calls (sk_trim_fastq_piece_device_async with piece != NULL) use words 21..29, which are otherwise the ordered
+// calls' (sk_fastq_order.h): a piece is never ordered.
+#define SK_FQP_H_START 21      // [2] s_i: the window's first byte, offset in text[i]
+#define SK_FQP_H_END 23        // [2] n_i: the window's end (sk_trim_fastq_piece_words' end)
+#define SK_FQP_H_CONSUMED 25   // [2] offset in text[i] of the first byte the piece did not consume
+#define SK_FQP_H_OK 27         // 1 iff no format error, the range-error word clear at both looks, every produced output fitted
+#define SK_FQP_H_RANGE0 28     // the stream's range-error word as the frame scan saw it, before the piece's own scan
+#define SK_FQP_H_MORE 29       // the piece's `more`
 struct sk_fq_layout {
     uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
 };
@@ -199,19 +207,25 @@ static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * 
 // order: NULL = read order (sk_trim_fastq_device_async).  lengths: NULL = in->bytes are the texts' lengths; else
 // (sk_trim_fastq_chained_device_async) in->bytes are bounds and the framing kernels, the only ones that look at a text's
 // length, take it from the device words: everything behind them reads lines and records from the header.
+// piece: NULL = the whole text; else (sk_trim_fastq_piece_device_async) text i starts at *piece->start_dev[i], with
+// piece->more only whole records (pairs) are taken, and errword is the stream's range-error word for the frame scan to
+// capture.  The emission takes the piece from the header.
 // counted: the packed batch is for sk_scan_counted_device_async with *n_reads_dev (the header's SK_FQ_H_NREAL) -- packed->n_reads
 // stays the bound -- and the per-read steps of the pack and the emission stop at that word too; 0: everything walks the bound.
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
                                                                                   const sk_fastq_lengths *lengths, int mode,
                                                                                   int trunc_n, int counted,
                                                                                   const sk_fastq_order *order,
+                                                                                  const sk_fastq_piece *piece,
+                                                                                  const unsigned long long *errword,
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
                                                                                   sk_cut_dev **cuts,
                                                                                   const uint64_t **n_reads_dev);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  int counted, const sk_fastq_order *order,
-                                                                                 const sk_fastq_output *out, void *workspace,
+                                                                                 int piece, const sk_fastq_output *out,
+                                                                                 void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);
 // BGZF on the device (sk_bgzf.hip).  The caller's workspace (16-byte sections, sizes in bytes, NB = ceil(text bytes /
@@ -350,6 +364,16 @@ static inline void sk_gunzip_layout_of(uint64_t image_bytes, uint64_t capacity, 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_gunzip(const uint8_t *image, uint64_t image_bytes, uint8_t *out,
                                                                              uint64_t capacity, uint64_t forced_chunk,
                                                                              void *workspace, hipStream_t stream);
+// the carry between two pieces (sk_fastq_piece.hip): sk_fastq_carry_device_async's arguments as they are, prev_hdr the
+// previous piece's header or NULL
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_carry(const uint64_t *prev_hdr, int input,
+                                                                                  const uint8_t *prev_text, uint8_t *next_text,
+                                                                                  uint64_t room, const uint64_t *chunk_bytes_dev,
+                                                                                  uint64_t chunk_bytes,
+                                                                                  const uint64_t *chunk_valid_dev,
+                                                                                  const sk_fastq_carry_words *prev_words,
+                                                                                  const sk_fastq_carry_words *other_prev_words,
+                                                                                  sk_fastq_carry_words *words, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif

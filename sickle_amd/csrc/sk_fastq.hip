@@ -14,6 +14,9 @@
 //   (the scan: sk_scan_device_async on the packed batch, launched by sk_capi.hip)
 //   emit    9 count / 10 scan / 11 place  the pair rule over the cuts: output offset and read of every kept record
 //           12 gather the records' bytes: name line, seq[five:three], '\n', '+' line, qual[five:three], '\n'
+// Piece calls (sk_trim_fastq_piece_device_async): the three frame kernels start the text at a device word (fq_start), the
+// frame scan takes whole records (pairs) only when more text follows, and the emission's scan publishes what was consumed
+// and the ok word for the carry kernel of sk_fastq_piece.hip; everything else runs as it does for a whole text.
 // The workspace layout and the header words are in sk_device.h.  The gathers build aligned 16-byte granules from aligned
 // 16-byte loads funnel-shifted by v_alignbyte (fq_load_window, a copy of sk_trim.hip's load_window), so the text may
 // have any alignment and no load touches a 16-byte block without a wanted byte.
@@ -64,6 +67,10 @@ struct fq_args {
     uint8_t *pq, *ps;
     const unsigned long long *errword;
     fq_out out[3];
+    // piece calls (sk_trim_fastq_piece_device_async with a piece): text i is [*start_dev[i], n_i) of text[i]; the frame
+    // scan captures *errword
+    const uint64_t *start_dev[2];
+    int32_t piece; // 0: no piece (the words 21.. of the header are not touched), 1: a piece, more == 0, 2: more != 0
 };
 
 // ------------------------------------------------------------------------------------------
@@ -78,11 +85,18 @@ __device__ __forceinline__ uint64_t fq_length(const fq_args &a, int i)
     return n;
 }
 
-// the '\n' bytes of the aligned 16-byte block at q (offset from the aligned base of text i) that lie inside the text of
-// n bytes (fq_length, loaded once per workgroup): bit b = byte q + b.  A block without a byte of the text is not loaded.
-__device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t n, uint64_t q)
+// text i's first byte (a piece's window start; 0 without one): never beyond the length n
+__device__ __forceinline__ uint64_t fq_start(const fq_args &a, int i, uint64_t n)
 {
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, span = sh + n;
+    return a.start_dev[i] ? min(*a.start_dev[i], n) : 0;
+}
+
+// the '\n' bytes of the aligned 16-byte block at q (offset from the aligned base of text i) that lie inside the text
+// [s, n) (fq_start, fq_length, loaded once per workgroup): bit b = byte q + b.  A block without a byte of the text is not
+// loaded.  sh = the alignment shift + s: the text's first byte, from the aligned base.
+__device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t sh, uint64_t n, uint64_t q)
+{
+    const uint64_t span = (reinterpret_cast<uintptr_t>(a.text[i]) & 15) + n;
     if (q + 16 <= sh || q >= span) return 0;
     const fq_u4 *blk = reinterpret_cast<const fq_u4 *>((reinterpret_cast<uintptr_t>(a.text[i]) & ~(uintptr_t)15) + q);
     const fq_u4 v = __builtin_nontemporal_load(blk);
@@ -224,11 +238,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_count_kernel(fq_args a
     __shared__ uint64_t lds[8];
     const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
     const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i);
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i), s = fq_start(a, i, n);
     uint64_t cnt = 0, last = 0; // last: position + 1 of the lane's last '\n', 0 = none
     for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
         const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
-        const uint32_t m = fq_nl_mask(a, i, n, q);
+        const uint32_t m = fq_nl_mask(a, i, sh + s, n, q);
         cnt += __builtin_popcount(m);
         if (m) last = q + (31 - __builtin_clz(m)) - sh + 1;
     }
@@ -266,19 +280,34 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_scan_kernel(fq_args a)
             m_ex = max(m_ex, y);
         }
         lines[i] = s_tot;
-        // a last line without '\n' ends at the end of the text
-        const uint64_t n = fq_length(a, i);
-        if (threadIdx.x == 0 && n && a.text[i][n - 1] != '\n') {
-            fq_put_line(a, i, s_tot, m_tot, n);
+        // a last line without '\n' ends at the end of the text; behind a piece with more text to come it is no line
+        const uint64_t n = fq_length(a, i), first = fq_start(a, i, n);
+        if (threadIdx.x == 0 && a.piece != 2 && n > first && a.text[i][n - 1] != '\n') {
+            fq_put_line(a, i, s_tot, max(m_tot, first), n);
             lines[i] += 1;
+        }
+        if (threadIdx.x == 0 && a.piece) {
+            a.hdr[SK_FQP_H_START + i] = first;
+            a.hdr[SK_FQP_H_END + i] = n;
         }
         __syncthreads(); // lds reuse
     }
     if (threadIdx.x == 0) {
         uint64_t *h = a.hdr;
-        const uint64_t r0 = lines[0] >> 2, r1 = lines[1] >> 2;
+        uint64_t r0 = lines[0] >> 2, r1 = lines[1] >> 2;
         h[SK_FQ_H_LINES] = lines[0];
         h[SK_FQ_H_LINES + 1] = lines[1];
+        if (a.piece) {
+            // an earlier call's range error on the stream: the piece takes no record, so that its scan leaves the word alone
+            const unsigned long long range0 = *a.errword;
+            h[SK_FQP_H_RANGE0] = range0;
+            h[SK_FQP_H_MORE] = a.piece == 2;
+            if (a.piece == 2) { // whole records (pairs) only: the rest is the carry, no record of the piece
+                if (a.mode == SK_TRIM_PE_SPLIT) r0 = r1 = min(r0, r1);
+                else if (a.mode == SK_TRIM_PE_INTERLEAVED) r0 &= ~1ull;
+            }
+            if (range0 != ~0ull) r0 = r1 = 0;
+        }
         h[SK_FQ_H_RECORDS] = r0;
         h[SK_FQ_H_RECORDS + 1] = r1;
         uint64_t fmt = ~0ull, real;
@@ -303,11 +332,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_lines_kernel(fq_args a
     __shared__ uint64_t lds[8];
     const int i = blockIdx.x < a.n_chunks[0] ? 0 : 1;
     const uint64_t c = blockIdx.x - (i ? a.n_chunks[0] : 0);
-    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i);
-    uint64_t ln0 = a.chunks[2 * blockIdx.x], prev = a.chunks[2 * blockIdx.x + 1]; // prev: start of the chunk's first line
+    const uint64_t sh = reinterpret_cast<uintptr_t>(a.text[i]) & 15, n = fq_length(a, i), s = fq_start(a, i, n);
+    uint64_t ln0 = a.chunks[2 * blockIdx.x], prev = max(a.chunks[2 * blockIdx.x + 1], s); // prev: start of the chunk's first line
     for (uint32_t u = 0; u < SK_FQ_CHUNK_BYTES / FQ_SUB; ++u) {
         const uint64_t q = c * SK_FQ_CHUNK_BYTES + u * FQ_SUB + 16u * threadIdx.x;
-        uint32_t m = fq_nl_mask(a, i, n, q);
+        uint32_t m = fq_nl_mask(a, i, sh + s, n, q);
         const uint64_t last = m ? q + (31 - __builtin_clz(m)) - sh + 1 : 0;
         uint64_t s_ex, m_ex, s_tot, m_tot;
         fq_scan2(__builtin_popcount(m), last, s_ex, m_ex, s_tot, m_tot, lds);
@@ -526,6 +555,25 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_scan_kernel(fq_args a)
         a.hdr[SK_FQ_H_PRODUCED + o] = produced;
         a.hdr[SK_FQ_H_FIT + o] = fit;
         if (o == 0) a.hdr[SK_FQ_H_RANGE] = range;
+    }
+    if (a.piece && threadIdx.x == 3) { // the word a carry behind this piece goes by
+        bool ok = a.hdr[SK_FQ_H_FMT] == ~0ull && *a.errword == ~0ull && a.hdr[SK_FQP_H_RANGE0] == ~0ull;
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            const fq_out &out = a.out[o];
+            const uint64_t recs = o == 0 ? run[0] : o == 1 ? run[1] : run[2], bytes = o == 0 ? run[3] : o == 1 ? run[4] : run[5];
+            if (out.text && (bytes > out.cap || (out.index && recs > out.rec_cap))) ok = false;
+        }
+        a.hdr[SK_FQP_H_OK] = ok;
+    }
+    if (a.piece && (threadIdx.x == 4 || threadIdx.x == 5)) { // the first byte of text i the piece did not consume
+        const int i = threadIdx.x - 4;
+        const uint64_t u = a.hdr[SK_FQ_H_RECORDS + i], end = a.hdr[SK_FQP_H_END + i];
+        uint64_t consumed = a.hdr[SK_FQP_H_START + i];
+        if (!a.hdr[SK_FQP_H_MORE] || i >= (a.mode == SK_TRIM_PE_SPLIT ? 2 : 1)) consumed = end; // the stream ends here
+        else if (u > a.slots[i]) consumed = end; // only in a text with a malformed record among the consumed ones
+        else if (u) consumed = a.desc[i][5 * (u - 1) + 4] + 1;
+        a.hdr[SK_FQP_H_CONSUMED + i] = consumed;
     }
 }
 
@@ -1052,6 +1100,8 @@ void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int
     a.pq = ws + L.qual;
     a.ps = trunc_n ? ws + L.seq : nullptr;
     a.errword = errword;
+    a.start_dev[0] = a.start_dev[1] = nullptr;
+    a.piece = 0;
     for (int o = 0; o < 3; ++o) {
         const bool used = o == 0 || (mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2);
         a.out[o] = used && out ? fq_out{out[o].text, out[o].capacity, out[o].record_index, out[o].record_capacity} : fq_out{};
@@ -1069,18 +1119,26 @@ fq_order fq_make_order(const sk_fastq_order *order, void *workspace)
 } // namespace
 
 // order: NULL = read order; else the batch chain and its check take the place of the check of every record.  lengths:
-// NULL = in->bytes are the lengths; else the device words that hold them, in->bytes their bounds
+// NULL = in->bytes are the lengths; else the device words that hold them, in->bytes their bounds.  piece: NULL = the whole
+// text; else the window start and the piece rule of sk_trim_fastq_piece_device_async (read order only)
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
                                                                                   const sk_fastq_lengths *lengths, int mode,
                                                                                   int trunc_n, int counted,
                                                                                   const sk_fastq_order *order,
+                                                                                  const sk_fastq_piece *piece,
+                                                                                  const unsigned long long *errword,
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
                                                                                   sk_cut_dev **cuts,
                                                                                   const uint64_t **n_reads_dev)
 {
     fq_args a;
-    fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, nullptr, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, piece ? errword : nullptr, a,
+                 order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    if (piece) {
+        for (int i = 0; i < (mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
+        a.piece = piece->more ? 2 : 1;
+    }
     const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
     if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
@@ -1109,13 +1167,15 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  int counted, const sk_fastq_order *order,
-                                                                                 const sk_fastq_output *out, void *workspace,
+                                                                                 int piece, const sk_fastq_output *out,
+                                                                                 void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream)
 {
     fq_args a;
     // no emission kernel looks at a text's length: lines and records come from the descriptors and the header
     fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    a.piece = piece ? 1 : 0; // the emission takes `more` and the window from the header
     const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
     if (order) {
         const fq_order o = fq_make_order(order, workspace);
