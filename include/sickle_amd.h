@@ -688,6 +688,88 @@ int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, co
 int sk_gzip_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev);
 
 /*
+ * Plain gzip read on the device in PIECES: sk_gzip_inflate_device_async resumed at a block boundary, for streams whose
+ * text is beyond one call's workspace.  A deflate stream can be taken up again at any block boundary, given the bit
+ * position, the 32 KiB of text before it, and the running CRC-32 and length of the member in progress.  That is the
+ * STATE, in device memory; a piece call starts at *state_in and publishes *state_out, so pieces chain on a stream
+ * without a host wait.  A state of all zeros is the start of a stream.  These calls stand beside the whole-image calls,
+ * which are unchanged.
+ *
+ * Window.  With p = state_in->pos_bit >> 3 the piece's WINDOW is the stream bytes [p, min(p + window_bytes, image_offset +
+ * image_bytes)); image[0] is stream byte image_offset.  No image byte outside the window bears on anything, and none
+ * outside [image, image + image_bytes) is read.  The piece is CLOSING iff last != 0 and the window reaches the image's
+ * end.  From in_member == 0 the piece parses a member header at p (a closing piece whose window is empty ends the stream
+ * there); from in_member == 1 it takes a block header at pos_bit.
+ *
+ * Resume points are every block boundary inside a member (also the one behind a header, with member_text 0) and every
+ * member start behind a complete trailer.  A closing piece is sk_gzip_inflate_device_async on the rest of the stream:
+ * every failure is real, and on success done = 1.  A piece that is not closing ends in front of the first header, block
+ * or trailer that does not parse or decode inside the window, whether bits ran out or the image is damaged; R is the
+ * last resume point it reached.  R > pos: the piece succeeds with the text up to R, and nothing behind R is decoded or
+ * reported.  R == pos: the failure is reported as what it appears to be, with window_limited = 1; state_in is never
+ * written, so the caller may repeat the piece from it with a larger window.  A distance reaching before its member's first
+ * byte, SK_GZ_LENGTH and SK_GZ_CRC in the consumed part are always real.
+ *
+ * Capacity.  The piece also ends in front of the first stretch (sk_gzip_inflate_device_async) whose text would pass
+ * `capacity`; a stretch begins at a block boundary, a resume point.  If even the first stretch does not fit, the state's
+ * status is 2, finish returns SK_ESPACE with bytes_out = that stretch's need, and nothing is written to out.
+ *
+ * state_in->status != 0: the piece is void: it writes no text (the written word is 0), *state_out inherits the failure,
+ * and finish returns it with inherited = 1.  state_in->done: an empty successful piece.  A position outside the image
+ * handed in gives status 3 and SK_EINVAL from finish.  Member numbers and byte offsets in a state and in what finish
+ * reports are stream-wide; counts->members, bytes_in (the window) and bytes_out are the piece's own.  finish returns, in
+ * this order of precedence, SK_EDATA, SK_ESPACE, SK_OK.  Unlike the whole-image call, the FIRST failing piece reports: a
+ * lower-numbered reason for the same member that a later piece would have found (a cut trailer behind a distance that
+ * reaches too far) no longer wins.
+ *
+ * sk_gzip_inflate_output_words works on a piece's workspace: the piece's text length and its written word, which feed
+ * sk_fastq_carry_device_async as the BGZF reader's do.
+ *
+ * sk_gzip_inflate_piece_device_async only enqueues kernels (10) on hip_stream: no allocation, no copy, no wait.  Two pieces
+ * in flight need two workspaces and alternate two states.  With w = window_bytes, chunk and S taken on w as
+ * sk_gzip_inflate_workspace_bytes takes them on n (SK_GZIP_CHUNK applies likewise):
+ *   sk_gzip_inflate_piece_workspace_bytes(w, capacity) = 256 + 128 (S + 1) + A(8 (S + 1)) + A(4 (S + 1))
+ *                                                        + 32 (floor(w / 18) + 2) + 32 (S + 1) + A(2 (32768 + capacity))
+ * SK_EINVAL, nothing enqueued: NULL ctx, piece or states; image NULL with image_bytes != 0; state_out == state_in; states
+ * not 16-byte aligned; piece->reserved != 0; window_bytes 0 or above 8 GiB; out NULL or not 16-byte aligned; a capacity
+ * above 2^60; a workspace that is NULL, not 16-byte aligned or short.
+ */
+#define SK_GZIP_PIECE_STATE_BYTES (128 + 32768)
+typedef struct {            /* device memory, 16-byte aligned */
+    uint64_t pos_bit;       /* stream bit of the resume point (bit 0 = first bit of stream byte 0) */
+    uint64_t in_member;     /* 0: a member begins at byte pos_bit / 8 (or the stream ends there); 1: a block header begins at pos_bit */
+    uint64_t member_text;   /* text bytes of the member in progress so far */
+    uint64_t member_crc;    /* zlib's crc32 of that text */
+    uint64_t members, text_bytes;  /* completed members / text produced, stream-wide */
+    uint64_t status;        /* 0, or sticky: 1 data error, 2 text beyond capacity, 3 pos outside the image handed in */
+    uint64_t error, error_member, error_offset;  /* SK_GZ_*, stream-wide member number and byte offset */
+    uint64_t done;          /* the stream has ended cleanly */
+    uint64_t reserved[5];   /* the reader's own (reserved[0]: first byte of the member in progress); zero at a stream's start */
+    uint8_t  history[32768];/* the last 32 KiB of stream text, zeros in front of the stream's start */
+} sk_gzip_piece_state;
+typedef struct {
+    uint64_t image_offset;   /* stream offset of image[0] */
+    uint64_t window_bytes;   /* > 0 */
+    uint32_t last;           /* image's end is the stream's end */
+    uint32_t reserved;
+} sk_gzip_piece;
+typedef struct {
+    uint64_t pos_bit, in_member;   /* the state the piece published */
+    uint64_t image_bytes_consumed; /* image bytes in front of the byte that holds pos_bit: pos_bit / 8 - image_offset */
+    uint32_t window_limited;       /* SK_EDATA from a piece that is not closing, at its first header, block or trailer */
+    uint32_t inherited;            /* the failure is state_in's: the piece was void */
+    uint32_t done, reserved;
+} sk_gzip_piece_counts;
+
+size_t sk_gzip_inflate_piece_workspace_bytes(uint64_t window_bytes, uint64_t capacity);   /* pure, no device */
+int sk_gzip_inflate_piece_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, const sk_gzip_piece *piece,
+                                       const sk_gzip_piece_state *state_in, sk_gzip_piece_state *state_out, uint8_t *out,
+                                       uint64_t capacity, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills *counts and *piece_counts from the workspace. */
+int sk_gzip_inflate_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts,
+                                        sk_gzip_piece_counts *piece_counts);
+
+/*
  * The FASTQ trim with the texts' lengths taken from the device: sk_trim_fastq_device_async (order == NULL, a workspace of
  * sk_trim_fastq_workspace_bytes, finished by sk_trim_fastq_device_finish) or sk_trim_fastq_ordered_device_async (order !=
  * NULL, sk_trim_fastq_ordered_workspace_bytes, sk_trim_fastq_ordered_device_finish), and everything said there holds, with

@@ -35,7 +35,9 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_ordered_device_finish", "sk_trim_fastq_ordered_batches",
            "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words",
            "sk_scan_counted_device_async", "sk_trim_fastq_piece_device_async", "sk_trim_fastq_piece_words",
-           "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async")
+           "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async", "sk_gzip_inflate_piece_workspace_bytes",
+           "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish")
+SK_GZIP_PIECE_STATE_BYTES = 128 + 32768
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
 
@@ -182,6 +184,28 @@ class GzipInflateCounts(C.Structure):
         return {"bytes_in": int(self.bytes_in), "members": int(self.members), "bytes_out": int(self.bytes_out),
                 "stretches": int(self.stretches), "stretches_used": int(self.stretches_used), "error": int(self.error),
                 "error_member": int(self.error_member), "error_offset": int(self.error_offset)}
+
+
+class GzipPieceState(C.Structure):
+    """sk_gzip_piece_state: lives in device memory; this is its layout (and the host copy tests read)"""
+    _fields_ = [(n, C.c_uint64) for n in ("pos_bit", "in_member", "member_text", "member_crc", "members", "text_bytes", "status",
+                                          "error", "error_member", "error_offset", "done")] + \
+               [("reserved", C.c_uint64 * 5), ("history", C.c_uint8 * 32768)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:11]}
+
+
+class GzipPiece(C.Structure):
+    _fields_ = [("image_offset", C.c_uint64), ("window_bytes", C.c_uint64), ("last", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GzipPieceCounts(C.Structure):
+    _fields_ = [("pos_bit", C.c_uint64), ("in_member", C.c_uint64), ("image_bytes_consumed", C.c_uint64),
+                ("window_limited", C.c_uint32), ("inherited", C.c_uint32), ("done", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_[:6]}
 
 
 class SickleError(RuntimeError):
@@ -368,6 +392,14 @@ def lib():
                                                    C.c_size_t, C.c_void_p]
         L.sk_gzip_inflate_device_finish.restype = C.c_int
         L.sk_gzip_inflate_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GzipInflateCounts)]
+        L.sk_gzip_inflate_piece_workspace_bytes.restype = C.c_size_t
+        L.sk_gzip_inflate_piece_workspace_bytes.argtypes = [C.c_uint64, C.c_uint64]
+        L.sk_gzip_inflate_piece_device_async.restype = C.c_int
+        L.sk_gzip_inflate_piece_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(GzipPiece), C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_gzip_inflate_piece_device_finish.restype = C.c_int
+        L.sk_gzip_inflate_piece_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GzipInflateCounts),
+                                                          C.POINTER(GzipPieceCounts)]
         _lib = L
     return _lib
 
@@ -696,6 +728,24 @@ class Context:
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len)
 
+    def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
+                         search=False, max_read_len=0):
+        """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
+        write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
+        depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
+        sk_gzip_inflate_piece_device_async per FASTQ piece, straight in front of the carry, over window_bytes of the
+        image and into at most the text that FASTQ piece may take.  window_bytes defaults to piece_bytes // 3, a guess at
+        FASTQ's compression ratio and not a measurement: a smaller window only makes shorter pieces.  A piece whose first
+        deflate block does not end inside the window raises GzDataError naming window_bytes, one whose first stretch holds
+        more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
+        piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
+        the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one."""
+        window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
+        sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
+        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len)
+        st.device_bytes += sum(s.device_bytes for s in sources)
+        return st
+
     @staticmethod
     def trim_fastq_ordered_batches(workspace_ptr):
         """sk_trim_fastq_ordered_batches -> the device address of the table of first units (batches + 1 entries)."""
@@ -929,6 +979,69 @@ class Context:
         self.gzip_inflate_device_finish(ws.data_ptr(), stream)
         return out[:need]
 
+    # ---- plain gzip read on the device, in pieces -----------------------------------------------
+    def gzip_inflate_piece_device_async(self, image_ptr, image_bytes, state_in_ptr, state_out_ptr, out_ptr, capacity, workspace_ptr,
+                                        workspace_bytes, window_bytes, image_offset=0, last=True, stream=None, reserved=0):
+        """sk_gzip_inflate_piece_device_async on raw device pointers."""
+        piece = GzipPiece(image_offset, window_bytes, int(bool(last)), reserved)
+        self._check(lib().sk_gzip_inflate_piece_device_async(self._h, image_ptr, image_bytes, C.byref(piece), state_in_ptr,
+                                                             state_out_ptr, out_ptr, capacity, workspace_ptr, workspace_bytes, stream))
+
+    def gzip_inflate_piece_device_finish(self, workspace_ptr, stream=None, window_bytes=None, capacity=None):
+        """sk_gzip_inflate_piece_device_finish -> counts (dict: the reader's counts and the piece's).  Raises GzDataError
+        (.counts["window_limited"]: the failure may be the window's end; the message then names window_bytes), or
+        TrimError (with .counts) on SK_ESPACE: the capacity, which a driver derives from piece_bytes, is less than the
+        piece's first stretch needs."""
+        c, pc = GzipInflateCounts(), GzipPieceCounts()
+        rc = lib().sk_gzip_inflate_piece_device_finish(self._h, workspace_ptr, stream, C.byref(c), C.byref(pc))
+        counts = dict(c.as_dict(), **pc.as_dict())
+        if rc == SK_EDATA:
+            e = GzDataError(int(c.error), int(c.error_member), int(c.error_offset), counts)
+            if pc.window_limited:
+                e.args = ("%s; the piece's window ends before its first block does: window_bytes=%s may be too small"
+                          % (e.args[0], window_bytes),)
+            raise e
+        if rc == SK_ESPACE:
+            raise TrimError("gzip piece: its first stretch holds %d bytes of text, beyond the capacity%s: piece_bytes is too small"
+                            % (counts["bytes_out"], "" if capacity is None else " of %d" % capacity), rc, counts)
+        self._check(rc)
+        return counts
+
+    def gunzip_stream(self, image, window_bytes=16 << 20, text_capacity=None):
+        """Any gzip image in device memory (a uint8 torch tensor) -> an iterator over its text, piece by piece (uint8
+        tensors; each is valid, for work on the current stream, until the next is asked for): sk_gzip_inflate_piece_device_async over windows of
+        window_bytes of the image, each piece's text at most text_capacity bytes (default: 4 * window_bytes, a guess at
+        FASTQ's ratio and not a measurement; a piece ends earlier where the capacity says so).  The next piece is enqueued
+        before the previous one is finished: two workspaces, two text buffers and two states alternate, and the state
+        stays on the device.  Raises GzDataError (a window_limited failure is not retried: pass a larger window_bytes),
+        or TrimError when text_capacity is less than one stretch needs."""
+        import torch
+        dev, n = image.device, image.numel()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cap = 4 * window_bytes if text_capacity is None else text_capacity
+        ws_bytes = lib().sk_gzip_inflate_piece_workspace_bytes(window_bytes, cap)
+        ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        out = [torch.empty(max(cap, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
+        states = torch.zeros((2, SK_GZIP_PIECE_STATE_BYTES), dtype=torch.uint8, device=dev)
+        ptr = image.data_ptr() if n else None
+
+        def enqueue(k):
+            s = k & 1
+            self.gzip_inflate_piece_device_async(ptr, n, states[s].data_ptr(), states[s ^ 1].data_ptr(), out[s].data_ptr(), cap,
+                                                 ws[s].data_ptr(), ws_bytes, window_bytes, stream=stream)
+
+        enqueue(0)
+        k = 0
+        while True:
+            enqueue(k + 1)  # from the state piece k publishes; void if k fails, empty if k ends the stream
+            counts = self.gzip_inflate_piece_device_finish(ws[k & 1].data_ptr(), stream, window_bytes, cap)
+            if counts["bytes_out"]:
+                yield out[k & 1][:counts["bytes_out"]]
+            if counts["done"]:
+                torch.cuda.current_stream(dev).synchronize()  # piece k + 1, empty, still reads its buffers
+                return
+            k += 1
+
     def _gunzip_any(self, image):
         """bgunzip, and for an image the BGZF reader refuses at member 0 although it begins as gzip does, gunzip"""
         try:
@@ -1072,6 +1185,7 @@ class Context:
 class _TextSource:
     """bytes-like chunks of any sizes, re-cut on demand"""
     compressed = False
+    pieces = False
 
     def __init__(self, chunks):
         if isinstance(chunks, (bytes, bytearray, memoryview, np.ndarray)):
@@ -1102,6 +1216,7 @@ class _TextSource:
 class _BgzfSource:
     """a BGZF image on the host, cut into groups of whole members by their BSIZE and ISIZE fields"""
     compressed = True
+    pieces = False
 
     def __init__(self, image, piece_bytes):
         self._im = (image if isinstance(image, np.ndarray) else np.frombuffer(image, dtype=np.uint8)).reshape(-1)
@@ -1141,6 +1256,45 @@ class _BgzfSource:
             self._at += m[0]
             text += m[1]
         return self._im[start:self._at].copy(), text
+
+
+class _GzipPieceSource:
+    """any gzip image, uploaded once and read by sk_gzip_inflate_piece_device_async piece by piece: two states on the
+    device alternate, and a reader workspace per FASTQ slot.  The host learns that the stream has ended when a finished
+    reader piece says so."""
+    compressed = False  # nothing is cut or uploaded per piece
+    pieces = True
+
+    def __init__(self, image, window_bytes, piece_bytes):
+        import torch
+        im = (image if isinstance(image, np.ndarray) else np.frombuffer(image, dtype=np.uint8)).reshape(-1)
+        self.n, self.window, self.piece_bytes = len(im), int(window_bytes), int(piece_bytes)
+        if self.window < 1:
+            raise ValueError("trim_gzip_stream: window_bytes must be positive")
+        self.image = torch.from_numpy(im.copy()).cuda() if self.n else None
+        self.states = torch.zeros((2, SK_GZIP_PIECE_STATE_BYTES), dtype=torch.uint8, device="cuda")
+        self.ws_bytes = lib().sk_gzip_inflate_piece_workspace_bytes(self.window, self.piece_bytes)
+        self.ws = [torch.empty(self.ws_bytes, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        self.device_bytes = max(self.n, 0) + self.states.numel() + 2 * self.ws_bytes
+        self.k, self.done, self.last_taken, self._cap = 0, False, self.piece_bytes, [0, 0]
+
+    def more(self):
+        return not self.done
+
+    def enqueue(self, ctx, slot, out_ptr, capacity, stream):
+        ctx.gzip_inflate_piece_device_async(self.image.data_ptr() if self.n else None, self.n, self.states[self.k & 1].data_ptr(),
+                                            self.states[(self.k + 1) & 1].data_ptr(), out_ptr, capacity, self.ws[slot].data_ptr(),
+                                            self.ws_bytes, self.window, stream=stream)
+        self.k += 1
+        self._cap[slot] = capacity
+
+    def finish(self, ctx, slot, stream):
+        """-> the text bytes the piece took; raises GzDataError (naming window_bytes when the window may be the cause) or
+        TrimError (naming piece_bytes)"""
+        counts = ctx.gzip_inflate_piece_device_finish(self.ws[slot].data_ptr(), stream, self.window, self._cap[slot])
+        self.done = self.done or bool(counts["done"])
+        self.last_taken = counts["bytes_out"]
+        return counts["bytes_out"]
 
 
 class FastqStream:
@@ -1208,10 +1362,20 @@ class FastqStream:
         least = min(active) if active else 0
         for i, s in enumerate(self.src):
             target = max(self.piece_bytes - max(carried[i] - least, 0), 0)
-            data, text_bytes = s.take(target) if target or s.compressed else (np.zeros(0, np.uint8), 0)
-            taken[i] = text_bytes
             buf = self.text[i][slot]
             nb_dev = valid_dev = None
+            if s.pieces:  # a reader piece straight to next_text + room, its capacity the text this piece may take
+                data, text_bytes, chunk = None, 0, 0
+                # an input steered below half a piece sits this piece out (its carry is ahead of the other's): a capacity
+                # that small could be less than one stretch's text, which is an error only of piece_bytes itself
+                if 2 * target >= self.piece_bytes and not s.done:
+                    chunk, text_bytes = target, min(s.last_taken, target)  # in flight: it has not told what it took
+                    s.enqueue(c, slot, buf.data_ptr() + self.room, target, self.stream)
+                    nb_dev, valid_dev = c.gzip_inflate_output_words(s.ws[slot].data_ptr())
+                    readers.append((i, s))
+            else:
+                data, text_bytes = s.take(target) if target or s.compressed else (np.zeros(0, np.uint8), 0)
+            taken[i] = text_bytes
             if s.compressed:
                 if text_bytes > self.piece_bytes:
                     raise ValueError("trim_gz_stream: a member holds %d bytes of text, beyond piece_bytes" % text_bytes)
@@ -1222,7 +1386,7 @@ class FastqStream:
                                                 self.rws[i][slot].data_ptr(), self.rws_bytes, stream=self.stream)
                     nb_dev, valid_dev = c.bgzf_inflate_output_words(self.rws[i][slot].data_ptr())
                     readers.append((i, self.rws[i][slot]))
-            else:
+            elif not s.pieces:
                 chunk = len(data)
                 if chunk:
                     buf[self.room:self.room + chunk].copy_(torch.from_numpy(data), non_blocking=False)
@@ -1254,7 +1418,10 @@ class FastqStream:
         """wait for piece p, raise what it met, sum its counts; -> (outputs, bytes carried per input)"""
         c, slot = self.ctx, p["slot"]
         for i, rws in p["readers"]:
-            c.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
+            if self.src[i].pieces:
+                p["taken"][i] = rws.finish(c, slot, self.stream)  # what the piece took, now that it has told
+            else:
+                c.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
         rc, raw, counts = c._piece_finish(self.ws[slot].data_ptr(), self.stream)
         status = [int(x) for x in self.words[:, slot, 3].cpu().tolist()]
         if 2 in status:
@@ -1326,7 +1493,10 @@ class FastqStream:
             if pending is not None:  # a piece still in flight behind a failure: wait for it and clear the stream's error word
                 for i, rws in pending["readers"]:
                     try:
-                        self.ctx.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
+                        if self.src[i].pieces:
+                            rws.finish(self.ctx, pending["slot"], self.stream)
+                        else:
+                            self.ctx.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
                     except SickleError:
                         pass
                 self.ctx._piece_finish(self.ws[pending["slot"]].data_ptr(), self.stream)

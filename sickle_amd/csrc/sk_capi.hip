@@ -1351,6 +1351,93 @@ int sk_gzip_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream
     return SK_OK;
 }
 
+size_t sk_gzip_inflate_piece_workspace_bytes(uint64_t window_bytes, uint64_t capacity)
+{
+    sk_gunzip_piece_layout L;
+    sk_gunzip_piece_layout_of(window_bytes, capacity, gzip_forced_chunk(), &L);
+    return (size_t)L.total;
+}
+
+int sk_gzip_inflate_piece_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, const sk_gzip_piece *piece,
+                                       const sk_gzip_piece_state *state_in, sk_gzip_piece_state *state_out, uint8_t *out,
+                                       uint64_t capacity, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+#define SK_GZ_BAD(...)               \
+    do {                             \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;            \
+    } while (0)
+    if (!ctx) return SK_EINVAL;
+    if (!piece || !state_in || !state_out) SK_GZ_BAD("gzip piece: piece, state_in or state_out is NULL");
+    if (!image && image_bytes) SK_GZ_BAD("gzip piece: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (static_cast<const void *>(state_in) == static_cast<const void *>(state_out))
+        SK_GZ_BAD("gzip piece: state_out is state_in (pieces alternate two states)");
+    if ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15)
+        SK_GZ_BAD("gzip piece: the states must be 16-byte aligned");
+    if (piece->reserved) SK_GZ_BAD("gzip piece: reserved must be 0");
+    if (piece->window_bytes == 0 || piece->window_bytes > SK_GUNZIP_MAX_WINDOW)
+        SK_GZ_BAD("gzip piece: a window of %llu bytes (1 .. 8 GiB)", (unsigned long long)piece->window_bytes);
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) SK_GZ_BAD("gzip piece: out must be 16-byte aligned and not NULL");
+    if (capacity > (1ull << 60)) SK_GZ_BAD("gzip piece: a capacity of %llu bytes", (unsigned long long)capacity);
+    const uint64_t forced = gzip_forced_chunk();
+    sk_gunzip_piece_layout L;
+    sk_gunzip_piece_layout_of(piece->window_bytes, capacity, forced, &L);
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < L.total)
+        SK_GZ_BAD("gzip piece: workspace must be 16-byte aligned and hold sk_gzip_inflate_piece_workspace_bytes(%llu, %llu) = %llu bytes",
+                  (unsigned long long)piece->window_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
+#undef SK_GZ_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_gunzip_piece(image, image_bytes, piece, state_in, state_out, out, capacity, forced, workspace,
+                                       static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_gzip_inflate_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts,
+                                        sk_gzip_piece_counts *piece_counts)
+{
+    if (!ctx || !workspace || !counts || !piece_counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[SK_GUNZIP_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    memset(counts, 0, sizeof *counts);
+    memset(piece_counts, 0, sizeof *piece_counts);
+    counts->bytes_in = h[0];
+    counts->members = h[1];
+    counts->bytes_out = h[2];
+    counts->stretches = h[3];
+    counts->stretches_used = h[4];
+    piece_counts->pos_bit = h[SK_GUNZIP_H_P_POS_BIT];
+    piece_counts->in_member = h[SK_GUNZIP_H_P_IN_MEMBER];
+    if ((h[SK_GUNZIP_H_P_POS_BIT] >> 3) >= h[SK_GUNZIP_H_P_IMAGE_OFFSET])
+        piece_counts->image_bytes_consumed = (h[SK_GUNZIP_H_P_POS_BIT] >> 3) - h[SK_GUNZIP_H_P_IMAGE_OFFSET];
+    piece_counts->inherited = (uint32_t)h[SK_GUNZIP_H_P_INHERITED];
+    piece_counts->done = (uint32_t)h[SK_GUNZIP_H_P_DONE];
+    const uint64_t status = h[SK_GUNZIP_H_P_STATUS];
+    if (status == 1) {
+        counts->error = (int32_t)h[SK_GUNZIP_H_P_ERROR];
+        counts->error_member = h[SK_GUNZIP_H_P_ERROR_MEMBER];
+        counts->error_offset = h[SK_GUNZIP_H_P_ERROR_OFFSET];
+        piece_counts->window_limited = (uint32_t)(h[SK_GUNZIP_H_P_LIMITED] && !piece_counts->inherited);
+        set_error(ctx, "gzip piece: member %llu is not valid gzip at byte %llu (reason %d)%s",
+                  (unsigned long long)counts->error_member, (unsigned long long)counts->error_offset, counts->error,
+                  piece_counts->window_limited ? ", or the window ends inside its first block" : "");
+        return SK_EDATA;
+    }
+    if (status == 2) {
+        set_error(ctx, piece_counts->inherited ? "gzip piece: an earlier piece's text was beyond its capacity"
+                                               : "gzip piece: the first stretch needs %llu bytes, more than the capacity",
+                  (unsigned long long)counts->bytes_out);
+        return SK_ESPACE;
+    }
+    if (status) {
+        set_error(ctx, "gzip piece: the state's position is outside the image handed in");
+        return SK_EINVAL;
+    }
+    return SK_OK;
+}
+
 int sk_probe_read_bandwidth(sk_ctx *ctx, const void *dev_buf, size_t bytes, int launches, void *hip_stream, double *gb_per_s)
 {
     if (!ctx || !dev_buf || !gb_per_s || launches < 1 || bytes < (1u << 20) || (reinterpret_cast<uintptr_t>(dev_buf) & 15)) return SK_EINVAL;

@@ -364,6 +364,46 @@ static inline void sk_gunzip_layout_of(uint64_t image_bytes, uint64_t capacity, 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_gunzip(const uint8_t *image, uint64_t image_bytes, uint8_t *out,
                                                                              uint64_t capacity, uint64_t forced_chunk,
                                                                              void *workspace, hipStream_t stream);
+// Plain gzip read in pieces (sk_gunzip_piece.hip): the workspace above for an image of window_bytes, with
+//   symbols   2 * (32768 + capacity): the state's history as literals in front of the text
+//   members   one entry more: the member in progress at the piece's end
+//   resume    32 per stretch, S + 1: each stretch's last resume point, and the bit its decode stops at
+#define SK_GUNZIP_RESUME_BYTES 32u
+#define SK_GUNZIP_H_P_LIMITED 17 // the header words sk_gzip_inflate_piece_device_finish reads (== SKG_H_P_* of sk_gunzip_block.h)
+#define SK_GUNZIP_H_P_DONE 18
+#define SK_GUNZIP_H_P_STATUS 19
+#define SK_GUNZIP_H_P_ERROR 20
+#define SK_GUNZIP_H_P_ERROR_MEMBER 21
+#define SK_GUNZIP_H_P_ERROR_OFFSET 22
+#define SK_GUNZIP_H_P_INHERITED 23
+#define SK_GUNZIP_H_P_POS_BIT 24
+#define SK_GUNZIP_H_P_IN_MEMBER 25
+#define SK_GUNZIP_H_P_IMAGE_OFFSET 27
+#define SK_GUNZIP_PIECE_SHIFT 32768u
+#define SK_GUNZIP_MAX_WINDOW (1ull << 33)
+struct sk_gunzip_piece_layout {
+    sk_gunzip_layout g;
+    uint64_t resume, total;
+};
+static inline void sk_gunzip_piece_layout_of(uint64_t window_bytes, uint64_t capacity, uint64_t forced_chunk, sk_gunzip_piece_layout *L)
+{
+    sk_gunzip_layout *g = &L->g;
+    g->chunk = sk_gunzip_chunk_of(window_bytes, forced_chunk);
+    g->S = window_bytes / g->chunk + (window_bytes % g->chunk != 0);
+    g->n_members = window_bytes / 18 + 2;
+    g->stretches = 8 * SK_GUNZIP_HDR_WORDS;
+    g->u_off = g->stretches + SK_GUNZIP_STRETCH_BYTES * (g->S + 1);
+    g->u_id = g->u_off + sk_inflate_a16(8 * (g->S + 1));
+    g->members = g->u_id + sk_inflate_a16(4 * (g->S + 1));
+    L->resume = g->members + (uint64_t)SK_GUNZIP_MEMBER_BYTES * g->n_members;
+    g->sym = L->resume + SK_GUNZIP_RESUME_BYTES * (g->S + 1);
+    g->total = L->total = g->sym + sk_inflate_a16(2 * (SK_GUNZIP_PIECE_SHIFT + capacity));
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_gunzip_piece(const uint8_t *image, uint64_t image_bytes,
+                                                                                   const sk_gzip_piece *piece, const void *state_in,
+                                                                                   void *state_out, uint8_t *out, uint64_t capacity,
+                                                                                   uint64_t forced_chunk, void *workspace,
+                                                                                   hipStream_t stream);
 // the carry between two pieces (sk_fastq_piece.hip): sk_fastq_carry_device_async's arguments as they are, prev_hdr the
 // previous piece's header or NULL
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_carry(const uint64_t *prev_hdr, int input,

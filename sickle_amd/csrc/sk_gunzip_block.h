@@ -307,6 +307,14 @@ struct skg_walk { // shared (LDS on the device): every lane writes the same valu
     uint64_t derr_off, derr_nmem;
 };
 
+// a piece's walk (skg_walk_stretch<EMIT, true>) keeps more, shared in the same way: the last resume point it reached -- a
+// block boundary (in = 1) or a member start behind a complete trailer (in = 0) -- and the bit the decode stops at
+struct skg_piece_walk {
+    uint64_t stop;       // in (decode): a resume point of the count, or SKG_NONE
+    uint64_t r_bit, r_len; // out: the resume point, the stretch's text in front of it
+    uint32_t r_in, pad;
+};
+
 #ifdef __HIPCC__
 // a value every lane holds alike, read back from shared memory: told to the compiler
 SKD_FN uint64_t skg_uniform(uint64_t v)
@@ -319,10 +327,11 @@ SKD_FN uint64_t skg_uniform(uint64_t v) { return v; }
 
 // the member's end behind a final block: the trailer, then the next member's header or the image's end.  -> true: the
 // walk goes on at the next member's first block; false: it ends here (w->status, w->reason say how)
-template <bool EMIT>
-SKD_FN bool skg_member_end(const skg_args &a, skg_reader *r, skg_walk *w, uint64_t pos, int lane)
+template <bool EMIT, bool PIECE>
+SKD_FN bool skg_member_end(const skg_args &a, skg_reader *r, skg_walk *w, skg_piece_walk *pw, uint64_t pos, int lane)
 {
     (void)lane;
+    (void)pw;
     const uint64_t at = (skg_bitpos(r, a.image) + 7) >> 3;
     w->end = at * 8;
     if (a.n - at < 8) {
@@ -343,6 +352,15 @@ SKD_FN bool skg_member_end(const skg_args &a, skg_reader *r, skg_walk *w, uint64
     w->nmem = w->nmem + 1;
     w->tail_from = pos;
     w->end = (at + 8) * 8;
+    if (PIECE) {
+        pw->r_bit = (at + 8) * 8;
+        pw->r_len = pos;
+        pw->r_in = 0;
+        if (EMIT && pw->stop == (at + 8) * 8) {
+            w->status = SKG_S_END;
+            return false;
+        }
+    }
     if (at + 8 == a.n) {
         w->status = SKG_S_END;
         return false;
@@ -361,11 +379,12 @@ SKD_FN bool skg_member_end(const skg_args &a, skg_reader *r, skg_walk *w, uint64
     return true;
 }
 
-template <bool EMIT>
+template <bool EMIT, bool PIECE = false>
 SKD_FN void skg_walk_stretch(ski_shared *sh, const skg_args &a, uint64_t self, uint16_t *sym, uint64_t lim, int64_t floor,
-                             skg_walk *w, int lane)
+                             skg_walk *w, int lane, skg_piece_walk *pw = nullptr)
 {
     (void)lane;
+    (void)pw;
     SKG_PER_LANE(sym);
     SKG_PER_LANE(lim);
     SKG_PER_LANE(floor);
@@ -386,6 +405,16 @@ SKD_FN void skg_walk_stretch(ski_shared *sh, const skg_args &a, uint64_t self, u
             const uint64_t b = skg_bitpos(&r, a.image);
             const uint64_t c = b >> a.chunk_shift;
             w->block_bit = b;
+            if (PIECE) {
+                pw->r_bit = b;
+                pw->r_len = pos;
+                pw->r_in = 1;
+                if (EMIT && pw->stop == b) {
+                    w->status = SKG_S_JOIN;
+                    w->end = b;
+                    break;
+                }
+            }
             if (c > skg_uniform(w->self) && c < a.S && a.st[c].start == b) {
                 w->status = SKG_S_JOIN;
                 w->end = b;
@@ -438,7 +467,7 @@ SKD_FN void skg_walk_stretch(ski_shared *sh, const skg_args &a, uint64_t self, u
             break;
         }
         if (r.s.mode != SKI_M_DONE) continue;
-        if (!skg_member_end<EMIT>(a, &r, w, pos, lane)) break;
+        if (!skg_member_end<EMIT, PIECE>(a, &r, w, pw, pos, lane)) break;
         floor = (int64_t)pos;
         SKG_PER_LANE(floor);
     }
@@ -589,6 +618,20 @@ SKD_FN void skg_chain(const skg_args &a)
 // ------------------------------------------------------------------------------------------
 // stage 4, decode: used stretch number u, into symbols at its text offset
 // ------------------------------------------------------------------------------------------
+// a distance that reached before its member's first byte, to the stretch's record and the call's key
+SKD_FN void skg_decode_publish(skg_walk *w, const skg_args &a, int lane)
+{
+    (void)lane;
+    // the lane is compared here, on an opaque copy: "lane == 0" as a mask would live in a scalar pair through the walk
+    SKI_ALL(int who = lane; SKG_PER_LANE(who); if (who == 0 && w->derr) {
+        skg_stretch *t = &a.st[w->self];
+        t->derr = 1;
+        t->derr_off = w->derr_off;
+        t->derr_nmem = w->derr_nmem;
+        SKG_ATOMIC_MIN64(&a.hdr[SKG_H_ERROR_KEY], ((t->mbase + w->derr_nmem) << 3) | SKI_DEFLATE);
+    });
+}
+
 SKD_FN void skg_decode_stretch(ski_shared *sh, skg_walk *w, const skg_args &a, uint64_t u, int lane)
 {
     const uint64_t k = a.u_id[u];
@@ -598,14 +641,7 @@ SKD_FN void skg_decode_stretch(ski_shared *sh, skg_walk *w, const skg_args &a, u
     w->mem = a.mem + s->mbase;
     w->text_off = off;
     skg_walk_stretch<true>(sh, a, k, a.sym + off, s->len, floor, w, lane);
-    // the lane is compared here, on an opaque copy: "lane == 0" as a mask would live in a scalar pair through the walk
-    SKI_ALL(int who = lane; SKG_PER_LANE(who); if (who == 0 && w->derr) {
-        skg_stretch *t = &a.st[w->self];
-        t->derr = 1;
-        t->derr_off = w->derr_off;
-        t->derr_nmem = w->derr_nmem;
-        SKG_ATOMIC_MIN64(&a.hdr[SKG_H_ERROR_KEY], ((t->mbase + w->derr_nmem) << 3) | SKI_DEFLATE);
-    });
+    skg_decode_publish(w, a, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -780,6 +816,308 @@ SKD_FN void skg_final(const skg_args &a)
         off = m ? a.mem[m - 1].next_start : 0;
     }
     a.hdr[SKG_H_ERROR_OFFSET] = off;
+}
+
+// ==========================================================================================
+// Pieces (sk_gzip_inflate_piece_device_async, sk_gunzip_piece.hip): the call starts at a device-resident state and
+// publishes the next one.  The stages above run on the WINDOW: an skg_args whose image begins at the byte that holds the
+// state's position, so every bit and byte offset below is relative to it.  The symbols get a prefix of SKG_WINDOW
+// literals, the state's history, and every text offset is shifted by as much: stretch 0's placeholders then resolve as
+// every other stretch's do.  `out` is shifted the other way, and one more member entry, the open member's, ends the
+// table, so that its text has a CRC term too.
+// ==========================================================================================
+struct skg_piece_words {
+    uint64_t pos_bit, in_member, member_text, member_crc, members, text_bytes, status, error, error_member, error_offset, done;
+    uint64_t mstart; // reserved[0]: the header offset of the member in progress (of the member that begins, in_member 0)
+    uint64_t reserved[4];
+};
+struct skg_piece_state { // sk_gzip_piece_state of sickle_amd.h
+    skg_piece_words w;
+    uint8_t history[SKG_WINDOW];
+};
+
+struct skg_resume { // 32 bytes per stretch
+    uint64_t bit, len; // count: the last resume point of the stretch's walk, its text in front of it
+    uint64_t in;       // 1: a block boundary, 0: a member start
+    uint64_t stop;     // chain: the bit the decode stops at, or SKG_NONE
+};
+
+struct skg_piece_args {
+    const skg_piece_state *in;
+    skg_piece_state *out;
+    const uint8_t *image;
+    uint64_t image_bytes, image_offset, window_bytes;
+    uint8_t *text; // the caller's out
+    uint64_t capacity;
+    skg_resume *res;
+    uint32_t last, pad;
+};
+
+#define SKG_P_RUN 0u     // what the state asks of the call
+#define SKG_P_VOID 1u    // a failed state: nothing is done, the failure is handed on
+#define SKG_P_DONE 2u    // the stream has ended: an empty piece
+#define SKG_P_OUTSIDE 3u // the position is not in the image handed in
+// header words of a piece, behind those of the whole call
+#define SKG_H_P_KIND 12
+#define SKG_H_P_BASE 13    // stream offset of the window's first byte
+#define SKG_H_P_END_BIT 14 // chain: the resume point the piece ends at (window-relative), what it is, the header of its member
+#define SKG_H_P_END_IN 15
+#define SKG_H_P_END_MSTART 16
+#define SKG_H_P_LIMITED 17 // the failure is the first thing in the window of a piece that is not closing
+#define SKG_H_P_DONE 18
+#define SKG_H_P_STATUS 19  // state: what finish reports: the state's status, failure, position
+#define SKG_H_P_ERROR 20
+#define SKG_H_P_ERROR_MEMBER 21
+#define SKG_H_P_ERROR_OFFSET 22
+#define SKG_H_P_INHERITED 23
+#define SKG_H_P_POS_BIT 24
+#define SKG_H_P_IN_MEMBER 25
+#define SKG_H_P_CLOSING 26
+#define SKG_H_P_IMAGE_OFFSET 27
+
+// the window, from the state: a->image and a->n.  Once per workgroup; the state is never written
+SKD_FN uint32_t skg_piece_window(const skg_piece_args &p, skg_args *a, bool *closing)
+{
+    *closing = false;
+    if (p.in->w.status) return SKG_P_VOID;
+    if (p.in->w.done) return SKG_P_DONE;
+    const uint64_t pos = p.in->w.pos_bit >> 3, image_end = p.image_offset + p.image_bytes;
+    if (pos < p.image_offset || pos > image_end) return SKG_P_OUTSIDE;
+    const uint64_t end = image_end - pos < p.window_bytes ? image_end : pos + p.window_bytes;
+    a->image = p.image + (pos - p.image_offset);
+    a->n = end - pos;
+    *closing = p.last && end == image_end;
+    return SKG_P_RUN;
+}
+
+// stage 1, chunk 0 (one lane): the header words, and stretch 0's start: behind the header of the member that begins at
+// the position, or the position itself
+SKD_FN void skg_piece_first(const skg_args &a, const skg_piece_args &p, uint32_t kind, bool closing)
+{
+    for (uint32_t i = 0; i < SKG_HDR_WORDS; ++i) a.hdr[i] = 0;
+    a.hdr[SKG_H_STRETCHES] = a.S;
+    a.hdr[SKG_H_FIT] = 1;
+    a.hdr[SKG_H_DECODED] = 1;
+    a.hdr[SKG_H_ERROR_KEY] = a.hdr[SKG_H_CHAIN_KEY] = SKG_NONE;
+    a.hdr[SKG_H_P_KIND] = kind;
+    a.hdr[SKG_H_P_IMAGE_OFFSET] = p.image_offset;
+    if (kind != SKG_P_RUN) return;
+    a.hdr[SKG_H_BYTES_IN] = a.n;
+    a.hdr[SKG_H_P_BASE] = p.in->w.pos_bit >> 3;
+    a.hdr[SKG_H_P_CLOSING] = closing;
+    if (p.in->w.in_member) {
+        a.st[0].start = p.in->w.pos_bit & 7u;
+        return;
+    }
+    a.st[0].start = SKG_NONE;
+    if (a.n == 0 && closing) return; // the stream ends where a member may begin
+    uint64_t after = 0;
+    const uint32_t why = skg_parse_header(a.image, a.n, 0, &after);
+    if (why == SKI_OK) a.st[0].start = after * 8;
+    else a.hdr[SKG_H_CHAIN_KEY] = why; // member 0 of the piece
+}
+
+// stage 2
+SKD_FN void skg_count_stretch_piece(ski_shared *sh, skg_walk *w, skg_piece_walk *pw, const skg_args &a, const skg_piece_args &p,
+                                    uint64_t k, int lane)
+{
+    (void)lane;
+    pw->stop = SKG_NONE;
+    skg_walk_stretch<false, true>(sh, a, k, nullptr, 0, 0, w, lane, pw);
+    SKI_ALL(if (lane == 0) {
+        skg_stretch *s = &a.st[k];
+        s->end = w->end;
+        s->len = w->len;
+        s->tail = w->tail;
+        s->err_off = w->err_off;
+        s->last_mstart = w->last_mstart;
+        s->nmem = w->nmem;
+        s->status = w->status;
+        s->reason = w->reason;
+        s->err_nmem = w->err_nmem;
+        s->used = 0;
+        s->derr = 0;
+        skg_resume *r = &p.res[k];
+        r->bit = pw->r_bit;
+        r->len = pw->r_len;
+        r->in = pw->r_in;
+        r->stop = SKG_NONE;
+    });
+}
+
+// stage 3 (one lane): skg_chain from the state.  A piece that is not closing takes a stretch that failed up to its last
+// resume point and ends there; every piece ends in front of the first stretch whose text would pass the capacity.
+SKD_FN void skg_chain_piece(const skg_args &a, const skg_piece_args &p, bool closing)
+{
+    const skg_piece_state *in = p.in;
+    const uint64_t base = in->w.pos_bit >> 3;
+    uint64_t used = 0, off = SKG_WINDOW, members = 0;
+    uint64_t mtext = SKG_WINDOW - in->w.member_text, mstart = in->w.in_member ? in->w.mstart - base : 0; // both may wrap: they are only subtracted
+    uint64_t end_bit = in->w.pos_bit & 7u, end_in = in->w.in_member, need = 0;
+    bool fit = true, limited = false, ended = a.n == 0 && closing && !in->w.in_member;
+    if (a.st[0].start == SKG_NONE) {
+        limited = !closing && a.hdr[SKG_H_CHAIN_KEY] != SKG_NONE;
+        a.hdr[SKG_H_CHAIN_OFFSET] = 0;
+    } else {
+        uint64_t k = 0;
+        for (;;) { // k grows
+            skg_stretch *s = &a.st[k];
+            skg_resume *r = &p.res[k];
+            const bool failed = s->status == SKG_S_ERROR, first = used == 0;
+            bool cut = false;
+            uint64_t len = s->len;
+            if (failed && !closing) {
+                const bool progress = r->bit != s->start || (first && !in->w.in_member); // behind a header is a resume point
+                if (!progress && !first) break;
+                if (progress) {
+                    cut = true;
+                    len = r->len;
+                } else { // the failure is the first thing in the window: reported, and none of its text
+                    limited = true;
+                    len = 0;
+                }
+            }
+            if (off - SKG_WINDOW + len > p.capacity) {
+                if (first) {
+                    fit = false;
+                    need = len;
+                }
+                break;
+            }
+            s->used = 1;
+            s->off = off;
+            s->mtext = mtext;
+            s->mstart = mstart;
+            s->mbase = members;
+            a.u_off[used] = off;
+            a.u_id[used++] = (uint32_t)k;
+            r->stop = cut ? r->bit : SKG_NONE;
+            if (failed && !cut) {
+                a.hdr[SKG_H_CHAIN_KEY] = ((members + s->err_nmem) << 3) | s->reason;
+                a.hdr[SKG_H_CHAIN_OFFSET] = s->err_off != SKG_NONE ? s->err_off : mstart;
+            }
+            if (s->nmem) mtext = off + s->len - s->tail;
+            if (s->last_mstart != SKG_NONE) mstart = s->last_mstart;
+            s->len = len;
+            off += len;
+            members += s->nmem < a.mem_cap - 1 - members ? s->nmem : a.mem_cap - 1 - members; // never cut: skg_chain
+            end_bit = cut ? r->bit : s->end;
+            end_in = cut ? r->in : s->status != SKG_S_END;
+            if (!end_in) mstart = end_bit >> 3;
+            ended = closing && !cut && s->status == SKG_S_END;
+            if (cut || s->status != SKG_S_JOIN) break;
+            k = s->end >> a.chunk_shift;
+        }
+    }
+    skg_member open; // the member in progress at the end: its text is what lies behind the last member end
+    open.text_end = off;
+    open.next_start = 0;
+    open.crc = open.isize = open.acc = open.reserved = 0;
+    a.mem[members] = open;
+    a.u_off[used] = off;
+    a.hdr[SKG_H_USED] = used;
+    a.hdr[SKG_H_MEMBERS] = members + 1; // with the open member's entry, until skg_piece_publish
+    a.hdr[SKG_H_BYTES_OUT] = fit ? off : SKG_WINDOW + need;
+    a.hdr[SKG_H_FIT] = fit;
+    a.hdr[SKG_H_ERROR_KEY] = a.hdr[SKG_H_CHAIN_KEY];
+    a.hdr[SKG_H_ERROR_OFFSET] = a.hdr[SKG_H_CHAIN_OFFSET];
+    a.hdr[SKG_H_P_END_BIT] = end_bit;
+    a.hdr[SKG_H_P_END_IN] = end_in;
+    a.hdr[SKG_H_P_END_MSTART] = mstart;
+    a.hdr[SKG_H_P_LIMITED] = limited;
+    a.hdr[SKG_H_P_DONE] = ended;
+}
+
+// stage 4: skg_decode_stretch with the chain's stop bit
+SKD_FN void skg_decode_stretch_piece(ski_shared *sh, skg_walk *w, skg_piece_walk *pw, const skg_args &a, const skg_piece_args &p,
+                                     uint64_t u, int lane)
+{
+    const uint64_t k = a.u_id[u];
+    const skg_stretch *s = &a.st[k];
+    const uint64_t off = s->off, before = off - s->mtext;
+    const int64_t floor = before > (1ull << 40) ? -(int64_t)(1ull << 40) : -(int64_t)before;
+    w->mem = a.mem + s->mbase;
+    w->text_off = off;
+    pw->stop = p.res[k].stop;
+    skg_walk_stretch<true, true>(sh, a, k, a.sym + off, s->len, floor, w, lane, pw);
+    skg_decode_publish(w, a, lane);
+}
+
+// stage 8, member 0 of a piece: the state's length and CRC-32 go in front of the piece's
+SKD_FN void skg_check_first_piece(const uint32_t *power, const skg_args &a, const skg_piece_args &p)
+{
+    const skg_member e = a.mem[0];
+    const uint64_t len = e.text_end - SKG_WINDOW;
+    uint32_t why = SKI_OK;
+    if ((uint32_t)(p.in->w.member_text + len) != e.isize) why = SKI_LENGTH;
+    else if (~(skb_mul(~(uint32_t)p.in->w.member_crc, skg_shift_of(power, len)) ^ e.acc) != e.crc) why = SKI_CRC;
+    if (why != SKI_OK) SKG_ATOMIC_MIN64(&a.hdr[SKG_H_ERROR_KEY], (uint64_t)why);
+}
+
+// the last stage, behind skg_final.  Byte i of the next history: the last SKG_WINDOW bytes of history ++ text
+SKD_FN void skg_piece_history(const skg_args &a, const skg_piece_args &p, uint32_t i)
+{
+    const bool wrote = a.hdr[SKG_H_P_KIND] == SKG_P_RUN && a.hdr[SKG_H_FIT] && a.hdr[SKG_H_ERROR_KEY] == SKG_NONE;
+    const uint64_t text = wrote ? a.hdr[SKG_H_BYTES_OUT] - SKG_WINDOW : 0, at = text + i;
+    p.out->history[i] = at < SKG_WINDOW ? p.in->history[at] : p.text[at - SKG_WINDOW];
+}
+
+// (one lane) the next state, and the header words as the call's callers read them: counts of the piece, stream-wide
+// member numbers and offsets
+SKD_FN void skg_piece_publish(const skg_args &a, const skg_piece_args &p, const uint32_t *power)
+{
+    const skg_piece_words in = p.in->w;
+    skg_piece_words n = in;
+    uint64_t *h = a.hdr;
+    const uint64_t kind = h[SKG_H_P_KIND];
+    if (kind == SKG_P_VOID) {
+        h[SKG_H_P_INHERITED] = 1;
+    } else if (kind == SKG_P_DONE) {
+        h[SKG_H_WRITTEN] = 1;
+    } else if (kind == SKG_P_OUTSIDE) {
+        n.status = 3;
+    } else {
+        const uint64_t members = h[SKG_H_MEMBERS] - 1, base = h[SKG_H_P_BASE], key = h[SKG_H_ERROR_KEY];
+        h[SKG_H_MEMBERS] = members;
+        h[SKG_H_BYTES_OUT] -= SKG_WINDOW;
+        n.members = in.members + members;
+        if (key != SKG_NONE) {
+            const uint32_t why = (uint32_t)(key & 7u);
+            const uint64_t m = key >> 3;
+            n.status = 1;
+            n.error = why;
+            n.error_member = in.members + m;
+            // member 0's first byte lies before the window when the piece began inside it
+            n.error_offset = m == 0 && (why == SKI_LENGTH || why == SKI_CRC) && in.in_member ? in.mstart : base + h[SKG_H_ERROR_OFFSET];
+            n.text_bytes = in.text_bytes + h[SKG_H_BYTES_OUT];
+        } else if (!h[SKG_H_FIT]) {
+            n.status = 2;
+            n.members = in.members;
+        } else {
+            const skg_member open = a.mem[members];
+            const uint64_t tail = open.text_end - (members ? a.mem[members - 1].text_end : (uint64_t)SKG_WINDOW);
+            n.pos_bit = base * 8 + h[SKG_H_P_END_BIT];
+            n.in_member = h[SKG_H_P_END_IN];
+            n.member_text = n.member_crc = 0;
+            if (n.in_member) {
+                const uint32_t before = members ? 0u : (uint32_t)in.member_crc;
+                n.member_text = (members ? 0 : in.member_text) + tail;
+                n.member_crc = (uint32_t)~(skb_mul(~before, skg_shift_of(power, tail)) ^ open.acc);
+            }
+            n.mstart = base + h[SKG_H_P_END_MSTART];
+            n.text_bytes = in.text_bytes + h[SKG_H_BYTES_OUT];
+            n.done = h[SKG_H_P_DONE];
+        }
+    }
+    p.out->w = n;
+    h[SKG_H_P_STATUS] = n.status;
+    h[SKG_H_P_ERROR] = n.error;
+    h[SKG_H_P_ERROR_MEMBER] = n.error_member;
+    h[SKG_H_P_ERROR_OFFSET] = n.error_offset;
+    h[SKG_H_P_POS_BIT] = n.pos_bit;
+    h[SKG_H_P_IN_MEMBER] = n.in_member;
+    h[SKG_H_P_DONE] = n.done;
+    if (n.status) h[SKG_H_WRITTEN] = 0;
 }
 
 #endif
