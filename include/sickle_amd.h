@@ -819,8 +819,8 @@ int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_
  * The FASTQ trim in pieces: a text longer than one call's workspace allows is trimmed as a sequence of calls, each on a
  * PIECE of the stream, and what a piece does not consume (the CARRY: an incomplete record, an unpaired one) becomes the
  * front of the next piece's text -- without the host learning anything in between: the window's start, the lengths and the
- * carry are device words, and a finish is the only call that waits.  Read order only (the -a T order is a property of the
- * whole file).  This comment is the normative text.
+ * carry are device words, and a finish is the only call that waits.  This call writes read order; the -a T order in
+ * pieces is sk_trim_fastq_ordered_piece_device_async (below).  This comment is the normative text.
  *
  * sk_trim_fastq_piece_device_async is sk_trim_fastq_chained_device_async(.., order = NULL, ..), and everything said there
  * holds (the workspace is sk_trim_fastq_workspace_bytes(bytes[0] + bytes[1], trunc_n), everything sized on the host is a
@@ -919,6 +919,99 @@ int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int inp
                                 uint64_t chunk_bytes, const uint64_t *chunk_valid_dev,
                                 const sk_fastq_carry_words *prev_words, const sk_fastq_carry_words *other_prev_words,
                                 sk_fastq_carry_words *words, void *hip_stream);
+
+/*
+ * The FASTQ trim in pieces in the reference's -a T order: sk_trim_fastq_piece_device_async whose records are the lines of
+ * the reader's BATCHES (sk_trim_fastq_ordered_device_async's rule) that the piece can commit, emitted in the -a T order.
+ * The reader keeps little between batches: after a batch a is its end and c = e, c - a = (e - a) % m < m, and the next stop
+ * depends on lines [a, e) only.  So the k_i = c_i - a_i of every input, in a STATE in device memory, is all a piece needs
+ * to go on where the last one stopped; batches go in input order, so the pieces' outputs, one after the other, are the
+ * whole file's ordered output.  This comment is the normative text.
+ *
+ * What holds as sk_trim_fastq_piece_device_async defines it: the window, start_dev, lengths and more; "a line exists only
+ * if its '\n' lies in the window" when more != 0, and the closed unterminated last line when more == 0; the captured
+ * range-error word and the void piece behind it; read numbers counting from the piece's first record; nothing is written on
+ * an error; sk_trim_fastq_piece_words and sk_trim_fastq_output_words on this workspace, and sk_fastq_carry_device_async
+ * behind it.  piece, order and state_out are required.
+ * The walk.  Line numbers count from the window's first line.  The reader's rule with L = order->batch_len, m and the
+ * threads as in the ordered call, from a_i = 0 and c_i = min(state_in->carried_lines[i], lines_i) (state_in == NULL: a
+ * state of zeros); unless state_in->ended, batch after batch:
+ *   1. state_in->batches + the piece's batches == order->batch_limit != 0: the run has ended.
+ *   2. The stop e_i of every input.  more != 0: e_i exists only if the budget is used up on a line of the window (the
+ *      smallest e > c_i with sum(len(lines[a_i:e])) >= L); if c_i == lines_i, or the window's lines run out first, the
+ *      batch is UNDETERMINED.  more == 0: the text's end is the reader's end of input, exactly as in the ordered call.
+ *      The batch of input i is lines [a_i, e_i - (e_i - a_i) % m).
+ *   3. In this order: input 0's batch determined and empty: the run has ended.  A batch undetermined: the walk ends here
+ *      (undetermined = 1), nothing of this batch is committed.  PE split: input 1's batch empty: the run has ended; the
+ *      two batches differ in their line count: the run has ended, stopped_on_mismatch = 1.
+ *   4. The piece's table is full (order->batch_capacity batches committed): the walk ends here (table_full = 1).  This is
+ *      never an error, in a closing piece neither: the rest is carry and the state stays open; the caller runs further
+ *      pieces with more == 0 on the carry until one is not full.
+ *   5. The batch is committed: a_i = its end, c_i = e_i.
+ * The records of the piece are lines [0, a_i) of each input: they are checked, packed, scanned, routed and emitted as the
+ * ordered call does on a text made of them, with the table of the piece's own batches (record_index in emission order).
+ * Everything behind them is carry: not checked, not scanned, no format or range error comes from it.  SK_FQ_PAIR_COUNT never
+ * occurs, dropped_unpaired is 0.
+ * Counts.  consumed_i = the start of line a_i (s_i when nothing was committed; never beyond n_i).  records_in[i] = a_i / 4,
+ * tail_lines[i] = lines_i - a_i.  order_counts: batches, units, last_batch_units (0 without a batch), records_unbatched
+ * (lines_i / 4 - a_i / 4) and stopped_on_mismatch are the piece's own; error_batch is stream-wide (state_in->batches + the
+ * piece's batch).
+ * *state_out = *state_in with carried_lines[i] = c_i - a_i, batches and units advanced, last_batch_units replaced if the
+ * piece committed a batch, ended and stopped_on_mismatch set where they apply (sticky).  A piece that starts from `ended`
+ * commits nothing, ok = 1, and its whole window is carry.
+ * Lines gzgets would split.  Every complete line of the window is checked against batch_len - 1, committed or not, whatever
+ * the state, so carried lines are checked again in the next piece, and the stream refuses exactly the texts the ordered call
+ * refuses: SK_ELONGLINE with long_line counting from the window's first line; the piece writes nothing.  Deviation: the
+ * pieces before it have already been emitted.
+ * Failures.  Whenever finish returns anything but SK_OK for a piece, its emission has written ok = 0 and *state_out =
+ * *state_in with failed = 1, on the stream.  A piece that starts from `failed` is void: it commits nothing, checks
+ * nothing, ok = 0, inherited_failure = 1, every count is 0, *state_out = *state_in, and its finish returns SK_OK: the first
+ * failing piece is the one that reports.  A piece that finds the stream's range-error word set is void in the same way,
+ * and its finish returns SK_ERANGE with inherited_range = 1 (whether or not the state had failed too).
+ * finish returns, in this order of precedence: SK_ERANGE with inherited_range = 1, SK_OK with inherited_failure = 1,
+ * SK_ELONGLINE, SK_EFORMAT, SK_ERANGE, SK_ESPACE (the outputs only: the table never gives it), SK_OK.  It takes every verdict
+ * from this workspace, as sk_trim_fastq_piece_device_finish does.
+ *
+ * The workspace: the header keeps the piece's words, and the order words get a block of 256 bytes of their own in front of
+ * the batch table:
+ *   sk_trim_fastq_ordered_piece_workspace_bytes(text_bytes, trunc_n, batch_capacity)
+ *       = sk_trim_fastq_ordered_workspace_bytes(text_bytes, trunc_n, batch_capacity) + 256
+ * A batch usually holds about batch_len bytes, so batch_capacity = text_bytes / batch_len + 16 is a good guess, and a wrong
+ * one costs nothing but shorter pieces.  The walk's serial loop is bounded by batch_capacity + 1 steps.
+ * Same discipline: only kernels are enqueued, finish is the only call that waits.  SK_EINVAL, nothing enqueued: the bad
+ * arguments of sk_trim_fastq_ordered_device_async and of sk_trim_fastq_piece_device_async; piece, order or state_out NULL;
+ * state_in == state_out; a state that is not 8-byte aligned; a short workspace.
+ */
+typedef struct {                 /* device memory, 8-byte aligned, 64 bytes; all zero = the start of a stream */
+    uint64_t carried_lines[2];   /* k_i = c - a of input i: complete lines at the window's start that the reader had
+                                    already taken when the last batch was cut; always < m */
+    uint64_t batches, units;     /* stream-wide, up to this piece's start */
+    uint64_t last_batch_units;
+    uint32_t ended;              /* the run is over (empty batch, PE mismatch, batch_limit reached): later pieces take nothing */
+    uint32_t stopped_on_mismatch;
+    uint32_t failed;             /* a piece before this one failed: later pieces are void */
+    uint32_t reserved0;
+    uint64_t reserved1;
+} sk_fastq_order_state;
+
+typedef struct {
+    uint32_t table_full;        /* the walk stopped at a full batch table: call again on the carry */
+    uint32_t undetermined;      /* the walk stopped because a stop line is not in the window yet */
+    uint32_t inherited_failure; /* state_in->failed: the piece was void */
+    uint32_t reserved;
+    sk_fastq_order_state state; /* a host copy of *state_out as the piece wrote it */
+} sk_fastq_order_piece_counts;
+
+size_t sk_trim_fastq_ordered_piece_workspace_bytes(uint64_t text_bytes, int32_t trunc_n, uint64_t batch_capacity); /* pure */
+int sk_trim_fastq_ordered_piece_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                             const sk_fastq_lengths *lengths, const sk_fastq_piece *piece,
+                                             const sk_fastq_order *order, const sk_fastq_order_state *state_in,
+                                             sk_fastq_order_state *state_out, int mode, const sk_fastq_output out[3],
+                                             void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Waits for hip_stream and fills the counts (all but `counts` may be NULL). */
+int sk_trim_fastq_ordered_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                              sk_fastq_order_counts *order_counts, sk_fastq_piece_counts *piece_counts,
+                                              sk_fastq_order_piece_counts *order_piece_counts);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,9 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_chained_device_async", "sk_bgzf_inflate_output_words", "sk_gzip_inflate_output_words",
            "sk_scan_counted_device_async", "sk_trim_fastq_piece_device_async", "sk_trim_fastq_piece_words",
            "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async", "sk_gzip_inflate_piece_workspace_bytes",
-           "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish")
+           "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish",
+           "sk_trim_fastq_ordered_piece_workspace_bytes", "sk_trim_fastq_ordered_piece_device_async",
+           "sk_trim_fastq_ordered_piece_device_finish")
 SK_GZIP_PIECE_STATE_BYTES = 128 + 32768
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
@@ -152,6 +154,27 @@ class FastqOrderCounts(C.Structure):
                 "records_unbatched": list(self.records_unbatched), "stopped_on_mismatch": int(self.stopped_on_mismatch),
                 "long_line_input": int(self.long_line_input), "long_line": int(self.long_line),
                 "error_batch": int(self.error_batch)}
+
+
+class FastqOrderState(C.Structure):
+    """sk_fastq_order_state: lives in device memory; this is its layout (and the host copy a finish hands out)"""
+    _fields_ = [("carried_lines", C.c_uint64 * 2), ("batches", C.c_uint64), ("units", C.c_uint64),
+                ("last_batch_units", C.c_uint64), ("ended", C.c_uint32), ("stopped_on_mismatch", C.c_uint32),
+                ("failed", C.c_uint32), ("reserved0", C.c_uint32), ("reserved1", C.c_uint64)]
+
+    def as_dict(self):
+        return {"carried": list(self.carried_lines), "batches": int(self.batches), "units": int(self.units),
+                "last_batch_units": int(self.last_batch_units), "ended": int(self.ended),
+                "stopped_on_mismatch": int(self.stopped_on_mismatch), "failed": int(self.failed)}
+
+
+class FastqOrderPieceCounts(C.Structure):
+    _fields_ = [("table_full", C.c_uint32), ("undetermined", C.c_uint32), ("inherited_failure", C.c_uint32),
+                ("reserved", C.c_uint32), ("state", FastqOrderState)]
+
+    def as_dict(self):
+        return {"table_full": int(self.table_full), "undetermined": int(self.undetermined),
+                "inherited_failure": int(self.inherited_failure), "state": self.state.as_dict()}
 
 
 class BgzfInput(C.Structure):
@@ -357,6 +380,17 @@ def lib():
         L.sk_trim_fastq_piece_device_finish.restype = C.c_int
         L.sk_trim_fastq_piece_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts),
                                                         C.POINTER(FastqPieceCounts)]
+        L.sk_trim_fastq_ordered_piece_workspace_bytes.restype = C.c_size_t
+        L.sk_trim_fastq_ordered_piece_workspace_bytes.argtypes = [C.c_uint64, C.c_int32, C.c_uint64]
+        L.sk_trim_fastq_ordered_piece_device_async.restype = C.c_int
+        L.sk_trim_fastq_ordered_piece_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput),
+                                                               C.POINTER(FastqLengths), C.POINTER(FastqPiece),
+                                                               C.POINTER(FastqOrder), C.c_void_p, C.c_void_p, C.c_int,
+                                                               C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.sk_trim_fastq_ordered_piece_device_finish.restype = C.c_int
+        L.sk_trim_fastq_ordered_piece_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqCounts),
+                                                                C.POINTER(FastqOrderCounts), C.POINTER(FastqPieceCounts),
+                                                                C.POINTER(FastqOrderPieceCounts)]
         L.sk_fastq_carry_device_async.restype = C.c_int
         L.sk_fastq_carry_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
                                                   C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -681,6 +715,41 @@ class Context:
         self._check(rc, c.range)
         return counts
 
+    def trim_fastq_ordered_piece_device_async(self, params, text_ptrs, text_bounds, order, state_in_ptr, state_out_ptr, outs,
+                                              workspace_ptr, workspace_bytes, bytes_dev_ptrs=(), valid_dev_ptrs=(),
+                                              start_dev_ptrs=(), more=False, mode="se", max_read_len=0, stream=None):
+        """sk_trim_fastq_ordered_piece_device_async on raw device pointers: trim_fastq_piece_device_async whose records are
+        the batches the piece can commit, in the -a T order.  order: a FastqOrder; state_in_ptr (None: the start of a
+        stream) and state_out_ptr: FastqOrderState in device memory."""
+        pad = lambda xs, fill: list(xs) + [fill] * (2 - len(xs))
+        inp = FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), max_read_len)
+        lengths = FastqLengths((C.c_void_p * 2)(*pad(bytes_dev_ptrs, None)), (C.c_void_p * 2)(*pad(valid_dev_ptrs, None)))
+        pc = FastqPiece((C.c_void_p * 2)(*pad(start_dev_ptrs, None)), 1 if more else 0, 0)
+        arr = (FastqOutput * 3)(*list(outs)[:3])
+        self._check(lib().sk_trim_fastq_ordered_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
+                                                                   C.byref(pc), C.byref(order), state_in_ptr, state_out_ptr,
+                                                                   TRIM_MODES.get(mode, mode), arr, workspace_ptr,
+                                                                   workspace_bytes, stream))
+
+    def _ordered_piece_finish(self, workspace_ptr, stream):
+        c, oc, pc, opc = FastqCounts(), FastqOrderCounts(), FastqPieceCounts(), FastqOrderPieceCounts()
+        rc = lib().sk_trim_fastq_ordered_piece_device_finish(self._h, workspace_ptr, stream, C.byref(c), C.byref(oc),
+                                                             C.byref(pc), C.byref(opc))
+        return rc, c, dict(c.as_dict(), order=oc.as_dict(), piece=pc.as_dict(), order_piece=opc.as_dict())
+
+    def trim_fastq_ordered_piece_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_fastq_ordered_piece_device_finish -> counts (dict, with "order", "piece" and "order_piece"); raises
+        LongLineError, FormatError, RangeError (an inherited one too) or TrimError (SK_ESPACE: an output)."""
+        rc, c, counts = self._ordered_piece_finish(workspace_ptr, stream)
+        if rc == SK_ELONGLINE:
+            raise LongLineError(counts["order"]["long_line_input"], counts["order"]["long_line"], counts)
+        if rc == SK_EFORMAT:
+            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
+        self._check(rc, c.range)
+        return counts
+
     @staticmethod
     def trim_fastq_piece_words(workspace_ptr, input):
         """sk_trim_fastq_piece_words -> (consumed_dev, end_dev, ok_dev) device addresses of a piece's words."""
@@ -699,7 +768,7 @@ class Context:
                                                       stream))
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
-                          search=False, max_read_len=0):
+                          search=False, max_read_len=0, order=None, batch_capacity=None):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -713,23 +782,32 @@ class Context:
         the longest carry: a record longer than it (or, in "pe_split", inputs that drift apart by more) ends the stream
         with TrimError (SK_ESPACE) that names room.  A format or range error raises FormatError / RangeError at the first
         failing piece, with stream-wide record / read numbers.  Unlike trim_fastq, a format error does not beat a range
-        error in an EARLIER piece: pieces are framed one by one, as the reference frames batch by batch."""
+        error in an EARLIER piece: pieces are framed one by one, as the reference frames batch by batch.
+        order=(threads, batch_len): the records in the order the reference writes them at -a threads with its reader's
+        byte budget batch_len, as trim_fastq(order=) gives them on the whole text (sk_trim_fastq_ordered_piece_device_async:
+        every piece takes the batches it can tell, two states on the device alternate).  batch_capacity: the entries of a
+        piece's batch table, by default (room + piece_bytes) // batch_len + 16; a full table only makes a shorter piece, and
+        behind a closing piece whose table was full further closing pieces run on the carry alone (with gz=True each of
+        them ends in an EOF member, which readers step over).  .counts["order"] holds the summed order counts.  A piece
+        must hold a batch: a batch_len that piece_bytes and room cannot hold, or lines that never use the budget up, end the
+        stream with TrimError (SK_ESPACE) that names batch_len.  LongLineError counts its line within the piece.  When the
+        run ends before the text does (an empty batch, a split mismatch) the stream ends there, as the reference does."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0):
+                       max_read_len=0, order=None, batch_capacity=None):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz)."""
+        (use trim_gz).  order, batch_capacity: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
-                         search=False, max_read_len=0):
+                         search=False, max_read_len=0, order=None, batch_capacity=None):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -739,10 +817,11 @@ class Context:
         deflate block does not end inside the window raises GzDataError naming window_bytes, one whose first stretch holds
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
-        the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one."""
+        the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
+        batch_capacity: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
-        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len)
+        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1300,7 +1379,8 @@ class _GzipPieceSource:
 class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
-    def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len):
+    def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
+                 batch_capacity=None):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1322,7 +1402,17 @@ class FastqStream:
             return torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
         cap_in = self.room + self.piece_bytes
         self.text = [[alloc(cap_in + 16) for _ in range(2)] for _ in range(n_in)]
-        self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
+        self.order = None
+        if order is not None:
+            threads, batch_len = order
+            cap = cap_in // max(int(batch_len), 1) + 16 if batch_capacity is None else int(batch_capacity)
+            self.order = FastqOrder(threads, 0, batch_len, cap, 0)
+            self.counts["order"] = {"batches": 0, "units": 0, "last_batch_units": 0, "stopped_on_mismatch": 0}
+            self.states = torch.zeros((2, 8), dtype=torch.int64, device=dev)  # two sk_fastq_order_state, alternating
+            self.device_bytes += 128
+            self.ws_bytes = L.sk_trim_fastq_ordered_piece_workspace_bytes(n_in * cap_in, params.trunc_n, cap)
+        else:
+            self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
         self.ws = [alloc(self.ws_bytes) for _ in range(2)]
         self.out_cap = n_in * cap_in + 2
         self.out = [[alloc(self.out_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
@@ -1400,12 +1490,18 @@ class FastqStream:
         self._bounds = bounds
         more = any(s.more() for s in self.src)
         outs = [FastqOutput(t.data_ptr(), self.out_cap, None, 0) if t is not None else FastqOutput() for t in self.out[slot]]
-        c.trim_fastq_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds, outs,
-                                        self.ws[slot].data_ptr(), self.ws_bytes,
-                                        bytes_dev_ptrs=[self._words_ptr(i, slot) + 8 for i in range(n_in)],
-                                        valid_dev_ptrs=[self._words_ptr(i, slot) + 16 for i in range(n_in)],
-                                        start_dev_ptrs=[self._words_ptr(i, slot) for i in range(n_in)], more=more,
-                                        mode=self.mode, max_read_len=self.max_read_len, stream=self.stream)
+        words = dict(bytes_dev_ptrs=[self._words_ptr(i, slot) + 8 for i in range(n_in)],
+                     valid_dev_ptrs=[self._words_ptr(i, slot) + 16 for i in range(n_in)],
+                     start_dev_ptrs=[self._words_ptr(i, slot) for i in range(n_in)], more=more, mode=self.mode,
+                     max_read_len=self.max_read_len, stream=self.stream)
+        if self.order is None:
+            c.trim_fastq_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds, outs,
+                                            self.ws[slot].data_ptr(), self.ws_bytes, **words)
+        else:  # piece k starts from the state piece k - 1 wrote
+            c.trim_fastq_ordered_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
+                                                    self.order, self.states[k & 1].data_ptr(),
+                                                    self.states[(k + 1) & 1].data_ptr(), outs, self.ws[slot].data_ptr(),
+                                                    self.ws_bytes, **words)
         if self.gz:
             for o in self.used:
                 b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
@@ -1422,14 +1518,21 @@ class FastqStream:
                 p["taken"][i] = rws.finish(c, slot, self.stream)  # what the piece took, now that it has told
             else:
                 c.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
-        rc, raw, counts = c._piece_finish(self.ws[slot].data_ptr(), self.stream)
+        rc, raw, counts = self._raw_finish(slot)
         status = [int(x) for x in self.words[:, slot, 3].cpu().tolist()]
+        if 2 in status and self.order is not None:
+            raise TrimError("fastq stream: input %d carries more than room = %d bytes into piece %d without a batch to take: "
+                            "piece_bytes (%d) and room must hold one batch of batch_len = %d bytes (or the text's lines never "
+                            "use the budget up)" % (status.index(2), self.room, p["k"], self.piece_bytes,
+                                                    self.order.batch_len), SK_ESPACE, counts)
         if 2 in status:
             raise TrimError("fastq stream: input %d carries more than room = %d bytes into piece %d (a longer record, or "
                             "split inputs that drift apart): pass a larger room" % (status.index(2), self.room, p["k"]),
                             SK_ESPACE, counts)
         base_reads = self._reads
         per_input = base_reads // 2 if self.mode == "pe_split" else base_reads
+        if rc == SK_ELONGLINE:
+            raise LongLineError(counts["order"]["long_line_input"], counts["order"]["long_line"], counts)
         if rc == SK_EFORMAT:
             raise FormatError(int(raw.format_error), int(raw.format_input), int(raw.format_record) + per_input, counts)
         if rc == SK_ERANGE:
@@ -1450,6 +1553,14 @@ class FastqStream:
         for key in ("records_in", "records", "bytes"):
             self.counts[key] = [a + b for a, b in zip(self.counts[key], counts[key])]
         self.counts["tail_lines"], self.counts["dropped_unpaired"] = counts["tail_lines"], counts["dropped_unpaired"]
+        if self.order is not None:
+            oc, mine = counts["order"], self.counts["order"]
+            mine["batches"] += oc["batches"]
+            mine["units"] += oc["units"]
+            mine["last_batch_units"] = oc["last_batch_units"] if oc["batches"] else mine["last_batch_units"]
+            mine["stopped_on_mismatch"] |= oc["stopped_on_mismatch"]
+            self._table_full = bool(counts["order_piece"]["table_full"])
+            self._ended = bool(counts["order_piece"]["state"]["ended"])
         self._reads += counts["records_in"][0] * (2 if self.mode == "pe_split" else 1)
         if not p["more"] and self.mode == "pe_interleaved":
             self._reads -= counts["dropped_unpaired"]
@@ -1459,6 +1570,17 @@ class FastqStream:
         self._known = (p["k"], carried, [a + b - c for a, b, c in zip(self._carried_in, p["taken"], carried)])
         self._carried_in = carried
         return tuple(res)
+
+    def _raw_finish(self, slot):
+        if self.order is None:
+            return self.ctx._piece_finish(self.ws[slot].data_ptr(), self.stream)
+        return self.ctx._ordered_piece_finish(self.ws[slot].data_ptr(), self.stream)
+
+    def _eof_members(self, last):
+        """what closes the outputs when the run ended in a piece that was not a closing one"""
+        if not self.gz or not last["more"]:
+            return []
+        return [tuple(BGZF_EOF_MEMBER if o in self.used else None for o in range(3))]
 
     def _estimate(self, last):
         """bytes each input carries into the piece behind piece `last` (enqueued): what the last finished piece carried,
@@ -1471,6 +1593,7 @@ class FastqStream:
 
     def _run(self):
         self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])
+        self._table_full = self._ended = False  # ordered streams: the last finished piece's
         estimate, pending, k = [0, 0], None, 0
         try:
             while True:
@@ -1478,16 +1601,28 @@ class FastqStream:
                 if pending is not None:
                     done, pending = pending, nxt
                     yield self._finish(done)
+                    if self._ended:  # the run is over: the piece in flight takes nothing, and no further one is needed
+                        pending = None
+                        yield self._finish(nxt)
+                        yield from self._eof_members(nxt)
+                        return
                 pending = nxt
                 if not nxt["more"]:
                     break
                 if k == 0 and len(self.src) == 2:  # split inputs: piece 1 is sized by what piece 0 carried, not by a guess
                     done, pending = pending, None
                     yield self._finish(done)
+                    if self._ended:
+                        yield from self._eof_members(done)
+                        return
                 estimate = self._estimate(nxt) if self._known[0] >= 0 else [0, 0]
                 k += 1
             if pending is not None:
                 done, pending = pending, None
+                yield self._finish(done)
+            while self._table_full and not self._ended:  # a closing piece's table was full: go on, on the carry alone
+                k += 1
+                done = self._enqueue(k, self._carried_in)
                 yield self._finish(done)
         finally:
             if pending is not None:  # a piece still in flight behind a failure: wait for it and clear the stream's error word
@@ -1499,10 +1634,11 @@ class FastqStream:
                             self.ctx.bgzf_inflate_device_finish(rws.data_ptr(), self.stream)
                     except SickleError:
                         pass
-                self.ctx._piece_finish(self.ws[pending["slot"]].data_ptr(), self.stream)
+                self._raw_finish(pending["slot"])
 
 
 BGZF_INPUT = 65280   # bytes of text per BGZF block
+BGZF_EOF_MEMBER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 BGZF_SLOT = 65536    # bytes of output slot per block
 
 

@@ -793,14 +793,9 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
 } // namespace
 
 namespace {
-// both FASTQ calls; order: NULL = read order; piece: NULL = the whole text (else order is NULL)
-int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
-                const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
-                void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr)
+// the device words of the chained and the piece calls
+int fastq_check_words(sk_ctx *ctx, const sk_fastq_lengths *lengths, const sk_fastq_piece *piece, int mode)
 {
-    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
-                              order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
-    if (rc != SK_OK) return rc;
     if (lengths) {
         uintptr_t words = 0;
         for (int i = 0; i < 2; ++i)
@@ -828,6 +823,21 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
             return SK_EINVAL;
         }
     }
+    return SK_OK;
+}
+} // namespace
+
+namespace {
+// both FASTQ calls; order: NULL = read order; piece: NULL = the whole text (else order is NULL)
+int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
+                const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
+                void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr)
+{
+    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
+                              order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
+    if (rc != SK_OK) return rc;
+    rc = fastq_check_words(ctx, lengths, piece, mode);
+    if (rc != SK_OK) return rc;
     sk_scan_args chk;
     const uint64_t no_reads = 0;
     sk_batch probe = {};
@@ -1113,6 +1123,157 @@ int sk_trim_fastq_ordered_batches(void *workspace, const uint64_t **first_unit_d
     if (!workspace || !first_unit_dev) return SK_EINVAL;
     *first_unit_dev = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(workspace) + SK_FQO_TABLE_BYTES_AT);
     return SK_OK;
+}
+
+// ---- ordered pieces ----
+size_t sk_trim_fastq_ordered_piece_workspace_bytes(uint64_t text_bytes, int32_t trunc_n, uint64_t batch_capacity)
+{
+    return sk_trim_fastq_ordered_workspace_bytes(text_bytes, trunc_n, batch_capacity) + SK_FQOP_EXT_BYTES;
+}
+
+int sk_trim_fastq_ordered_piece_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
+                                             const sk_fastq_lengths *lengths, const sk_fastq_piece *piece,
+                                             const sk_fastq_order *order, const sk_fastq_order_state *state_in,
+                                             sk_fastq_order_state *state_out, int mode, const sk_fastq_output out[3],
+                                             void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    static_assert(sizeof(sk_fastq_order_state) == 64, "the kernels read the state as 8 words");
+    if (!ctx) return SK_EINVAL;
+    if (!piece || !order || !state_out) {
+        set_error(ctx, "fastq: an ordered piece needs piece, order and state_out");
+        return SK_EINVAL;
+    }
+    if (order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN || order->batch_capacity == 0 ||
+        order->batch_capacity > (1ull << 40)) {
+        set_error(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
+        return SK_EINVAL;
+    }
+    if (state_in == state_out || ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 7)) {
+        set_error(ctx, "fastq: state_in and state_out must be 8-byte aligned and differ");
+        return SK_EINVAL;
+    }
+    int rc = fastq_check_args(ctx, "sk_trim_fastq_ordered_piece_device_async", params, in, mode, out, workspace, workspace_bytes,
+                              (size_t)sk_fq_order_piece_shift(order->batch_capacity));
+    if (rc != SK_OK) return rc;
+    rc = fastq_check_words(ctx, lengths, piece, mode);
+    if (rc != SK_OK) return rc;
+    sk_scan_args chk;
+    const uint64_t no_reads = 0;
+    sk_batch probe = {};
+    probe.offsets = &no_reads; // an empty `offsets` batch: only params is checked
+    rc = make_args(ctx, params, &probe, &chk);
+    if (rc != SK_OK) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    sk_batch packed;
+    sk_cut_dev *cuts;
+    const char *counted_env = getenv("SK_FQ_COUNTED"); // as in fastq_async
+    const int counted = !(counted_env && *counted_env == '0');
+    const uint64_t *n_reads_dev = nullptr;
+    SK_HIP(ctx, sk_launch_fastq_order_piece_front(in, lengths, mode, params->trunc_n, counted, order, piece, state_in, state_out,
+                                                  d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev));
+    rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, sk_launch_fastq_order_piece_emit(in, mode, params->trunc_n, counted, order, state_in, state_out, out, workspace,
+                                                 d_err, ctx->cu_count, stream));
+    return SK_OK;
+}
+
+// Every verdict from the workspace's own words, as sk_trim_fastq_piece_device_finish takes them.
+int sk_trim_fastq_ordered_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
+                                              sk_fastq_order_counts *oc, sk_fastq_piece_counts *pc,
+                                              sk_fastq_order_piece_counts *opc)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    int rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    uint64_t h[SK_FQ_HDR_WORDS + SK_FQOP_EXT_BYTES / 8]; // the header and the extension block behind it
+    static_assert(SK_FQOP_EXT_BYTES_AT == 8 * SK_FQ_HDR_WORDS, "the block follows the header");
+    const uint64_t *x = h + SK_FQ_HDR_WORDS;
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    rc = reset_error_word(ctx, d_err, stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    *counts = sk_fastq_counts{};
+    const bool split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
+    const bool inherited_range = h[SK_FQP_H_RANGE0] != ~0ull, inherited = x[SK_FQOP_X_INHERITED] != 0;
+    const uint64_t fmt = h[SK_FQ_H_FMT], lng = x[SK_FQO_H_LONG];
+    const bool bad = fmt != ~0ull || lng != ~0ull;
+    for (int i = 0; i < 2; ++i) {
+        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
+        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] - 4 * h[SK_FQ_H_RECORDS + i];
+    }
+    for (int o = 0; o < 3; ++o) {
+        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
+        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
+    }
+    if (oc) {
+        *oc = sk_fastq_order_counts{};
+        oc->batches = x[SK_FQO_H_BATCHES];
+        oc->units = x[SK_FQO_H_UNITS];
+        oc->last_batch_units = x[SK_FQO_H_LAST_UNITS];
+        oc->records_unbatched[0] = x[SK_FQO_H_UNBATCHED];
+        oc->records_unbatched[1] = x[SK_FQO_H_UNBATCHED + 1];
+        oc->stopped_on_mismatch = (uint32_t)x[SK_FQO_H_MISMATCH];
+        oc->error_batch = lng != ~0ull || x[SK_FQO_H_ERROR_BATCH] == ~0ull ? UINT64_MAX
+                                                                            : x[SK_FQOP_X_BASE_BATCHES] + x[SK_FQO_H_ERROR_BATCH];
+        if (lng != ~0ull) {
+            oc->long_line_input = (uint32_t)(lng >> 63);
+            oc->long_line = lng & ~(1ull << 63);
+        }
+    }
+    if (pc) {
+        *pc = sk_fastq_piece_counts{};
+        for (int i = 0; i < 2; ++i) {
+            pc->consumed[i] = h[SK_FQP_H_CONSUMED + i];
+            pc->carried_bytes[i] = h[SK_FQP_H_END + i] - h[SK_FQP_H_CONSUMED + i];
+        }
+        pc->ok = (uint32_t)h[SK_FQP_H_OK];
+        pc->inherited_range = inherited_range;
+    }
+    if (opc) {
+        *opc = sk_fastq_order_piece_counts{};
+        opc->table_full = (uint32_t)x[SK_FQOP_X_TABLE_FULL];
+        opc->undetermined = (uint32_t)x[SK_FQOP_X_UNDETERMINED];
+        opc->inherited_failure = inherited;
+        memcpy(&opc->state, x + SK_FQOP_X_STATE, sizeof opc->state);
+    }
+    if (inherited_range) {
+        decode_error(h[SK_FQP_H_RANGE0], &counts->range);
+        set_error(ctx, "fastq: an earlier call on the stream left a range error (read %u of that call); the piece took no record",
+                  counts->range.read);
+        return SK_ERANGE;
+    }
+    if (inherited) return SK_OK; // void: the first failing piece is the one that reports
+    if (lng != ~0ull) {
+        set_error(ctx, "fastq: input %u, line %llu of the piece has batch_len - 1 bytes or more", (unsigned)(lng >> 63),
+                  (unsigned long long)(lng & ~(1ull << 63)));
+        return SK_ELONGLINE;
+    }
+    if (bad) {
+        const uint64_t read = fmt >> 3;
+        counts->format_error = (int32_t)(fmt & 7);
+        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
+        counts->format_record = split ? read >> 1 : read;
+        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
+                  (unsigned long long)counts->format_record, counts->format_error);
+        return SK_EFORMAT;
+    }
+    if (decode_error(h[SK_FQ_H_RANGE], &counts->range) == SK_ERANGE) {
+        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
+                  counts->range.pos + 1);
+        return SK_ERANGE;
+    }
+    for (int o = 0; o < 3; ++o)
+        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
+    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
+    return rc;
 }
 
 int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)

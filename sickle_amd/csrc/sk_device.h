@@ -169,7 +169,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 #define SK_FQ_H_RANGE 19       // the stream's range-error word as the emission saw it
 #define SK_FQ_H_MODE 20        // the call's mode
 // Piece calls (sk_trim_fastq_piece_device_async with piece != NULL) use words 21..29, which are otherwise the ordered
-// calls' (sk_fastq_order.h): a piece is never ordered.
+// calls' (sk_fastq_order.h); an ordered piece keeps these here and its order words in an extension block (below).
 #define SK_FQP_H_START 21      // [2] s_i: the window's first byte, offset in text[i]
 #define SK_FQP_H_END 23        // [2] n_i: the window's end (sk_trim_fastq_piece_words' end)
 #define SK_FQP_H_CONSUMED 25   // [2] offset in text[i] of the first byte the piece did not consume
@@ -228,6 +228,19 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
                                                                                  void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);
+// Ordered pieces (sk_trim_fastq_ordered_piece_device_async): the header with the PIECE's words 21.. (SK_FQP_H_*), then an
+// extension block of 256 bytes that holds the order words at their usual indices and the piece's own (sk_fastq_order.h:
+// SK_FQOP_*), then the table of first units, then the sections, shifted by block and table.  state_in / state_out:
+// sk_fastq_order_state in device memory (state_in NULL = the start of a stream).
+static inline uint64_t sk_fq_order_piece_shift(uint64_t batch_capacity) { return 256 + sk_fq_order_shift(batch_capacity); }
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_front(
+    const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted, const sk_fastq_order *order,
+    const sk_fastq_piece *piece, const void *state_in, void *state_out, const unsigned long long *errword, void *workspace,
+    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev);
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_emit(
+    const sk_fastq_input *in, int mode, int trunc_n, int counted, const sk_fastq_order *order, const void *state_in,
+    void *state_out, const sk_fastq_output *out, void *workspace, const unsigned long long *errword, int cu_count,
+    hipStream_t stream);
 // BGZF on the device (sk_bgzf.hip).  The caller's workspace (16-byte sections, sizes in bytes, NB = ceil(text bytes /
 // SK_BGZF_BLOCK) blocks, G = min(NB, SK_BGZF_GRID) workgroups of the block kernel):
 //   header    SK_BGZF_HDR_WORDS words

@@ -907,12 +907,52 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_check_kernel(fq_args a
     if (longest != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.hdr + SK_FQO_H_LONG), (unsigned long long)longest);
 }
 
+// The same check for an ordered piece, whose order words (SK_FQO_H_*) live at oh, its extension block.  (A copy: routing
+// the kernel above through it changes that kernel's register allocation.)
+__device__ __forceinline__ void fq_order_check(const fq_args &a, const fq_order &o, uint64_t *oh)
+{
+    const uint64_t nl[2] = {fq_order_lines(a, 0), a.mode == SK_TRIM_PE_SPLIT ? fq_order_lines(a, 1) : 0};
+    const uint64_t n0 = (nl[0] + 3) / 4, n1 = (nl[1] + 3) / 4; // records with a line, the last one maybe incomplete
+    const uint64_t inside = oh[SK_FQO_H_UNITS] * (a.mode == SK_TRIM_PE_INTERLEAVED ? 2u : 1u); // records per input
+    uint64_t best = ~0ull, longest = ~0ull;
+    for (uint64_t g = (uint64_t)blockIdx.x * FQ_THREADS + threadIdx.x; g < n0 + n1; g += (uint64_t)gridDim.x * FQ_THREADS) {
+        const int i = g < n0 ? 0 : 1;
+        const uint64_t r = g - (i ? n0 : 0);
+        const uint64_t *d = a.desc[i] + 5 * r;
+        const uint64_t have = min(nl[i] - 4 * r, (uint64_t)4);
+        uint64_t start = d[0], e[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((uint64_t)k < have) {
+                e[k] = d[1 + k];
+                if (e[k] - start + 1 >= o.batch_len) longest = min(longest, ((uint64_t)i << 63) | (4 * r + k));
+                start = e[k] + 1;
+            }
+        if (r >= inside) continue;
+        const uint64_t s0 = d[0], name = e[0] - s0, seq = e[1] - e[0] - 1, qual = e[3] - e[2] - 1;
+        uint64_t why = SK_FQ_OK;
+        if (name <= 1) why = SK_FQ_ID_SHORT;
+        else if (a.text[i][s0] != '@') why = SK_FQ_ID_NO_AT;
+        else if (seq == 0) why = SK_FQ_SEQ_EMPTY;
+        else if (qual == 0) why = SK_FQ_QUAL_EMPTY;
+        else if (qual != seq) why = SK_FQ_LENGTHS;
+        else if (qual > SK_MAX_READ_LEN_DEV) why = SK_FQ_TOO_LONG;
+        if (why != SK_FQ_OK) {
+            const uint64_t read = a.mode == SK_TRIM_PE_SPLIT ? 2 * r + i : r;
+            best = min(best, (read << 3) | why);
+        }
+    }
+    if (best != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(a.hdr + SK_FQ_H_FMT), (unsigned long long)best);
+    if (longest != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(oh + SK_FQO_H_LONG), (unsigned long long)longest);
+}
+
+
 // the reads at the lane's FQ_PER_THREAD consecutive ranks from `first` (even): mates share a pair rank, so they stay
 // neighbours.  Ranks at or beyond n_real get ~0.
-__device__ __forceinline__ void fq_order_reads(const fq_args &a, const fq_order &o, uint64_t first, uint64_t n_real,
-                                               uint64_t (&reads)[FQ_PER_THREAD])
+__device__ __forceinline__ void fq_order_reads(const fq_args &a, const fq_order &o, const uint64_t *oh, uint64_t first,
+                                               uint64_t n_real, uint64_t (&reads)[FQ_PER_THREAD])
 {
-    const uint64_t batches = a.hdr[SK_FQO_H_BATCHES];
+    const uint64_t batches = oh[SK_FQO_H_BATCHES];
     if (a.mode == SK_TRIM_SE) {
         fqo_lane_units<FQ_PER_THREAD>(o.tab, batches, o.threads, true, first, n_real, reads);
     } else {
@@ -948,12 +988,12 @@ __device__ __forceinline__ void fq_order_emit_load(const fq_args &a, const uint6
 }
 
 // nothing is trimmed after a format error, a line gzgets would split or a table that was too small
-__device__ __forceinline__ bool fq_order_bad(const uint64_t *h)
+__device__ __forceinline__ bool fq_order_bad(const uint64_t *h, const uint64_t *oh)
 {
-    return h[SK_FQ_H_FMT] != ~0ull || h[SK_FQO_H_LONG] != ~0ull || h[SK_FQO_H_OVERFLOW] != 0;
+    return h[SK_FQ_H_FMT] != ~0ull || oh[SK_FQO_H_LONG] != ~0ull || oh[SK_FQO_H_OVERFLOW] != 0;
 }
 
-__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_args a, fq_order o)
+__device__ __forceinline__ void fq_order_emit_count(const fq_args &a, const fq_order &o, const uint64_t *oh)
 {
     __shared__ uint64_t lds[4 * 6];
     const uint64_t n_real = a.hdr[SK_FQ_H_NREAL];
@@ -961,11 +1001,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_a
         if (threadIdx.x < 6) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS + threadIdx.x] = 0;
         return;
     }
-    const bool bad = fq_order_bad(a.hdr);
+    const bool bad = fq_order_bad(a.hdr, oh);
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + threadIdx.x * FQ_PER_THREAD;
     uint64_t reads[FQ_PER_THREAD];
     fq_emit_read rd[FQ_PER_THREAD];
-    fq_order_reads(a, o, first, bad ? 0 : n_real, reads);
+    fq_order_reads(a, o, oh, first, bad ? 0 : n_real, reads);
     fq_order_emit_load(a, reads, bad, a.counted ? n_real : a.n_pack, rd);
     uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
 #pragma unroll
@@ -985,6 +1025,11 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_a
     }
 }
 
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_count_kernel(fq_args a, fq_order o)
+{
+    fq_order_emit_count(a, o, a.hdr);
+}
+
 __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_scan_kernel(fq_args a, fq_order o)
 {
     __shared__ uint64_t lds[4 * 6];
@@ -994,7 +1039,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_scan_kernel(fq_ar
     if (threadIdx.x < 3) {
         const int k = threadIdx.x;
         const fq_out &out = a.out[k];
-        const bool ok = !fq_order_bad(a.hdr) && range == ~0ull;
+        const bool ok = !fq_order_bad(a.hdr, a.hdr) && range == ~0ull;
         const uint64_t recs = k == 0 ? run[0] : k == 1 ? run[1] : run[2], bytes = k == 0 ? run[3] : k == 1 ? run[4] : run[5];
         const bool produced = out.text != nullptr;
         const bool fit = produced && ok && bytes <= out.cap && (!out.index || recs <= out.rec_cap);
@@ -1015,7 +1060,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_scan_kernel(fq_ar
     }
 }
 
-__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_args a, fq_order o)
+__device__ __forceinline__ void fq_order_emit_place(const fq_args &a, const fq_order &o, const uint64_t *oh)
 {
     __shared__ uint64_t lds[4 * 6];
     const uint64_t *h = a.hdr;
@@ -1026,7 +1071,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_a
     uint64_t reads[FQ_PER_THREAD];
     fq_emit_read rd[FQ_PER_THREAD];
     if (fq_block_empty(a, n_real)) return;
-    fq_order_reads(a, o, first, n_real, reads);
+    fq_order_reads(a, o, oh, first, n_real, reads);
     fq_order_emit_load(a, reads, false, a.counted ? n_real : a.n_pack, rd);
     uint64_t v[6] = {0, 0, 0, 0, 0, 0}, tot[6];
 #pragma unroll
@@ -1055,6 +1100,165 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_a
                 a.emit[2 * (dbase[k] + at) + 1] = reads[j];
                 if (a.out[k].index) a.out[k].index[at] = reads[j];
             }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_emit_place_kernel(fq_args a, fq_order o)
+{
+    fq_order_emit_place(a, o, a.hdr);
+}
+
+// ------------------------------------------------------------------------------------------
+// ordered pieces (sk_trim_fastq_ordered_piece_device_async): a piece (the frame kernels with a.piece) whose records are
+// the lines of the batches it commits (fqo_chain_piece).  The header keeps the piece's words (SK_FQP_H_*); the order words
+// live in the extension block p.oh (sk_fastq_order.h).
+//   frame 1-3, then  P1 chain  one lane: *state_in, the walk over the window, the table, RECORDS / NREAL lowered to the
+//                              committed reads, the consumed offsets
+//                    O2 check  as above over p.oh (a void piece checks nothing)
+//   pack 5-8, the scan, O3 count as above over p.oh, then
+//                    P2 scan   O4, then the piece's words (consumed, ok) and *state_out
+//                    O5 place as above over p.oh, 12 gather
+// ------------------------------------------------------------------------------------------
+struct fq_opiece {
+    uint64_t *oh;              // the extension block
+    const uint64_t *state_in;  // sk_fastq_order_state as 8 words, or NULL: the start of a stream
+    uint64_t *state_out;
+};
+
+// sk_fastq_order_state's words
+#define FQ_ST_CARRIED 0 // [2]
+#define FQ_ST_BATCHES 2
+#define FQ_ST_UNITS 3
+#define FQ_ST_LAST_UNITS 4
+#define FQ_ST_ENDED_MISMATCH 5 // ended | stopped_on_mismatch << 32
+#define FQ_ST_FAILED 6         // failed | reserved0 << 32
+
+__global__ void __launch_bounds__(64) sk_fq_order_piece_chain_kernel(fq_args a, fq_order o, fq_opiece p)
+{
+    if (threadIdx.x != 0) return;
+    uint64_t *h = a.hdr, *oh = p.oh;
+    const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
+    uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (p.state_in)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) st[j] = p.state_in[j];
+    const bool inherited = (uint32_t)st[FQ_ST_FAILED] != 0;
+    // void: a failed stream, or the stream's range-error word set when the piece began (the frame scan's look)
+    const bool is_void = inherited || h[SK_FQP_H_RANGE0] != ~0ull;
+    const uint64_t *const desc[2] = {a.desc[0], a.desc[1]};
+    const uint64_t nl[2] = {is_void ? 0 : fq_order_lines(a, 0), n_in == 2 && !is_void ? fq_order_lines(a, 1) : 0};
+    const uint64_t first[2] = {h[SK_FQP_H_START], h[SK_FQP_H_START + 1]};
+    const fqo_piece_state ps = {{st[FQ_ST_CARRIED], st[FQ_ST_CARRIED + 1]}, st[FQ_ST_BATCHES],
+                                (uint32_t)st[FQ_ST_ENDED_MISMATCH] != 0 || is_void};
+    fqo_piece_result r;
+    fqo_chain_piece(desc, nl, first, n_in, a.mode == SK_TRIM_PE_INTERLEAVED ? 8u : 4u, o.batch_len, o.capacity, o.limit, &ps,
+                    h[SK_FQP_H_MORE] != 0, o.tab, &r);
+    oh[SK_FQO_H_BATCHES] = r.batches;
+    oh[SK_FQO_H_UNITS] = r.units;
+    oh[SK_FQO_H_LAST_UNITS] = r.last_units;
+    oh[SK_FQO_H_MISMATCH] = r.mismatch;
+    oh[SK_FQO_H_OVERFLOW] = 0; // a full table is no error in a piece
+    oh[SK_FQO_H_LONG] = ~0ull;
+    oh[SK_FQO_H_ERROR_BATCH] = ~0ull;
+    oh[SK_FQOP_X_TABLE_FULL] = r.table_full;
+    oh[SK_FQOP_X_UNDETERMINED] = r.undetermined;
+    oh[SK_FQOP_X_INHERITED] = inherited;
+    oh[SK_FQOP_X_BASE_BATCHES] = st[FQ_ST_BATCHES];
+    oh[SK_FQOP_X_LAST_UNITS] = r.batches ? r.last_units : st[FQ_ST_LAST_UNITS];
+    oh[SK_FQOP_X_ENDED] = is_void ? (uint32_t)st[FQ_ST_ENDED_MISMATCH] : r.ended;
+    oh[SK_FQOP_X_STICKY_MISMATCH] = (st[FQ_ST_ENDED_MISMATCH] >> 32) | r.mismatch;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const bool used = i < n_in;
+        // the unterminated last line a closing piece closes ends at the text's end: nothing lies behind it
+        oh[SK_FQOP_X_CONSUMED + i] = used ? min(fqo_line_start_from(desc[i], r.batched_lines[i], first[i]), h[SK_FQP_H_END + i])
+                                          : h[SK_FQP_H_END + i];
+        oh[SK_FQO_H_UNBATCHED + i] = used && !is_void ? h[SK_FQ_H_LINES + i] / 4 - r.batched_lines[i] / 4 : 0;
+        oh[SK_FQOP_X_STATE + FQ_ST_CARRIED + i] = is_void ? st[FQ_ST_CARRIED + i] : r.carried[i]; // for P2
+        h[SK_FQ_H_RECORDS + i] = used ? r.batched_lines[i] / 4 : 0;
+        if (is_void) h[SK_FQ_H_LINES + i] = 0; // all counts of a void piece are 0
+    }
+    h[SK_FQ_H_FMT] = ~0ull; // records without a mate are behind the last batch: no verdict
+    h[SK_FQ_H_NREAL] = min(r.units * (a.mode == SK_TRIM_SE ? 1u : 2u), a.n_pack);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_piece_check_kernel(fq_args a, fq_order o, fq_opiece p)
+{
+    if (p.oh[SK_FQOP_X_INHERITED] || a.hdr[SK_FQP_H_RANGE0] != ~0ull) return; // void: LINES is 0 anyway
+    fq_order_check(a, o, p.oh);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_piece_emit_count_kernel(fq_args a, fq_order o, fq_opiece p)
+{
+    fq_order_emit_count(a, o, p.oh);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_piece_emit_place_kernel(fq_args a, fq_order o, fq_opiece p)
+{
+    fq_order_emit_place(a, o, p.oh);
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_order_piece_emit_scan_kernel(fq_args a, fq_order o, fq_opiece p)
+{
+    __shared__ uint64_t lds[4 * 6];
+    uint64_t run[6];
+    fq_scan_blocks<6>(a, run, lds);
+    uint64_t *h = a.hdr, *oh = p.oh;
+    const unsigned long long range = *a.errword;
+    const bool sound = !fq_order_bad(h, oh) && range == ~0ull && h[SK_FQP_H_RANGE0] == ~0ull && !oh[SK_FQOP_X_INHERITED];
+    bool fits = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const fq_out &out = a.out[k];
+        const uint64_t recs = k == 0 ? run[0] : k == 1 ? run[1] : run[2], bytes = k == 0 ? run[3] : k == 1 ? run[4] : run[5];
+        if (out.text && (bytes > out.cap || (out.index && recs > out.rec_cap))) fits = false;
+    }
+    if (threadIdx.x < 3) {
+        const int k = threadIdx.x;
+        const fq_out &out = a.out[k];
+        const uint64_t recs = k == 0 ? run[0] : k == 1 ? run[1] : run[2], bytes = k == 0 ? run[3] : k == 1 ? run[4] : run[5];
+        const bool produced = out.text != nullptr;
+        const bool fit = produced && sound && bytes <= out.cap && (!out.index || recs <= out.rec_cap);
+        h[SK_FQ_H_OUT_RECORDS + k] = recs;
+        h[SK_FQ_H_OUT_BYTES + k] = bytes;
+        h[SK_FQ_H_PRODUCED + k] = produced;
+        h[SK_FQ_H_FIT + k] = fit;
+        if (k == 0) h[SK_FQ_H_RANGE] = range;
+    }
+    if (threadIdx.x == 3) { // the (local) batch of the record behind the error finish will report
+        const uint64_t fmt = h[SK_FQ_H_FMT], units = oh[SK_FQO_H_UNITS];
+        uint64_t read = ~0ull;
+        if (fmt != ~0ull) read = fmt >> 3;
+        else if (range != ~0ull) read = range >> 32;
+        const uint64_t unit = a.mode == SK_TRIM_SE ? read : read >> 1;
+        if (read != ~0ull && unit < units) oh[SK_FQO_H_ERROR_BATCH] = fqo_batch_of(o.tab, oh[SK_FQO_H_BATCHES], unit);
+    }
+    if (threadIdx.x == 4) { // the words a carry behind this piece goes by, and the state the next piece starts from
+        const bool ok = sound && fits;
+        h[SK_FQP_H_OK] = ok;
+        uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (p.state_in)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) st[j] = p.state_in[j];
+        if (ok) { // state_in advanced; a failed piece hands state_in on as it is, with `failed`
+            st[FQ_ST_CARRIED] = oh[SK_FQOP_X_STATE + FQ_ST_CARRIED];
+            st[FQ_ST_CARRIED + 1] = oh[SK_FQOP_X_STATE + FQ_ST_CARRIED + 1];
+            st[FQ_ST_BATCHES] += oh[SK_FQO_H_BATCHES];
+            st[FQ_ST_UNITS] += oh[SK_FQO_H_UNITS];
+            st[FQ_ST_LAST_UNITS] = oh[SK_FQOP_X_LAST_UNITS];
+            st[FQ_ST_ENDED_MISMATCH] = (oh[SK_FQOP_X_ENDED] != 0) | (oh[SK_FQOP_X_STICKY_MISMATCH] << 32);
+        }
+        st[FQ_ST_FAILED] = ok ? 0 : 1;
+        st[7] = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            p.state_out[j] = st[j];
+            oh[SK_FQOP_X_STATE + j] = st[j];
+        }
+    }
+    if (threadIdx.x == 5 || threadIdx.x == 6) {
+        const int i = threadIdx.x - 5;
+        h[SK_FQP_H_CONSUMED + i] = oh[SK_FQOP_X_CONSUMED + i];
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1187,6 +1391,70 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
         hipLaunchKernelGGL(sk_fq_emit_scan_kernel, dim3(1), threads, 0, stream, a);
         if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_place_kernel, blocks, threads, 0, stream, a);
     }
+    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
+    return hipGetLastError();
+}
+
+// ---- ordered pieces: the two launch functions of sk_trim_fastq_ordered_piece_device_async (sk_device.h) ----
+namespace {
+void fq_make_opiece(const sk_fastq_order *order, const void *state_in, void *state_out, void *workspace, fq_order &o, fq_opiece &p)
+{
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    o = {reinterpret_cast<uint64_t *>(ws + SK_FQOP_TABLE_BYTES_AT), order->batch_capacity, order->batch_len, order->batch_limit,
+         order->threads};
+    p = {reinterpret_cast<uint64_t *>(ws + SK_FQOP_EXT_BYTES_AT), static_cast<const uint64_t *>(state_in),
+         static_cast<uint64_t *>(state_out)};
+}
+} // namespace
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_front(
+    const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted, const sk_fastq_order *order,
+    const sk_fastq_piece *piece, const void *state_in, void *state_out, const unsigned long long *errword, void *workspace,
+    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev)
+{
+    fq_args a;
+    fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity));
+    for (int i = 0; i < (mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
+    a.piece = piece->more ? 2 : 1;
+    fq_order o;
+    fq_opiece p;
+    fq_make_opiece(order, state_in, state_out, workspace, o, p);
+    const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
+    if (nc) hipLaunchKernelGGL(sk_fq_frame_count_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_frame_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
+    if (nc) hipLaunchKernelGGL(sk_fq_frame_lines_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_order_piece_chain_kernel, dim3(1), dim3(64), 0, stream, a, o, p);
+    hipLaunchKernelGGL(sk_fq_order_piece_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a, o, p);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_pack_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 0);
+    *packed = sk_batch{};
+    packed->qual = a.pq;
+    packed->seq = a.ps;
+    packed->offsets = a.offsets;
+    packed->stride = in->max_read_len;
+    packed->n_reads = a.n_pack;
+    *cuts = a.cuts;
+    *n_reads_dev = counted ? a.hdr + SK_FQ_H_NREAL : nullptr; // written by the piece's chain, before the pack
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_emit(
+    const sk_fastq_input *in, int mode, int trunc_n, int counted, const sk_fastq_order *order, const void *state_in,
+    void *state_out, const sk_fastq_output *out, void *workspace, const unsigned long long *errword, int cu_count,
+    hipStream_t stream)
+{
+    fq_args a;
+    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity));
+    a.piece = 1;
+    fq_order o;
+    fq_opiece p;
+    fq_make_opiece(order, state_in, state_out, workspace, o, p);
+    const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_piece_emit_count_kernel, blocks, threads, 0, stream, a, o, p);
+    hipLaunchKernelGGL(sk_fq_order_piece_emit_scan_kernel, dim3(1), threads, 0, stream, a, o, p);
+    if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_piece_emit_place_kernel, blocks, threads, 0, stream, a, o, p);
     hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
     return hipGetLastError();
 }

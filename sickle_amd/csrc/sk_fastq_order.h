@@ -7,6 +7,9 @@
 //                first units (batch b holds units [tab[b], tab[b + 1])) and the counts.  One walker; per batch and input
 //                one binary search over the prefix content(l) = start(l) - l, the bytes of lines [0, l) without their
 //                newlines.  The walk ends after batch_capacity + 1 steps at the latest.
+//   fqo_chain_piece  the same walk over a WINDOW of the text from a state (sk_trim_fastq_ordered_piece_device_async, DESIGN
+//                4.15): it commits the batches whose stop line is complete in the window and hands the state on.
+//                tests/fastq_order_piece/piece_host.cpp runs it on the host.
 //   fqo_unit_of  rank j of a batch of n units at T threads -> the unit: the queues of reference
 //                src/trim_single.cpp:263-298 (read k to queue (k + 1) mod T) and src/trim_paired.cpp:388-403 (pair k to
 //                queue k mod T), written one after the other.
@@ -114,6 +117,123 @@ FQO_FN void fqo_chain(const uint64_t *const desc[2], const uint64_t nl[2], int n
     }
     r.batched_lines[0] = a[0];
     r.batched_lines[1] = a[1];
+    *res = r;
+}
+
+// ---- ordered pieces (sk_trim_fastq_ordered_piece_device_async) -------------------------------------------------------
+// The workspace of an ordered piece: the header's words 21.. are the piece's (SK_FQP_H_*, sk_device.h), so the order words
+// live in an extension block of 32 words behind the header, at the same indices (SK_FQO_H_* above); the block's other
+// words are the piece's own.  The table of first units follows the block.
+#define SK_FQOP_EXT_BYTES_AT 256u   // the extension block
+#define SK_FQOP_EXT_BYTES 256u
+#define SK_FQOP_TABLE_BYTES_AT (SK_FQOP_EXT_BYTES_AT + SK_FQOP_EXT_BYTES)
+#define SK_FQOP_X_STATE 0       // [8] the host's copy of *state_out (sk_fastq_order_state)
+#define SK_FQOP_X_TABLE_FULL 8  // the walk stopped at a full table
+#define SK_FQOP_X_UNDETERMINED 9 // the walk stopped at a batch whose stop line is not in the window yet
+#define SK_FQOP_X_INHERITED 10  // state_in->failed: the piece is void
+#define SK_FQOP_X_CONSUMED 11   // [2] start of the first line behind the last committed batch, offset in text[i]
+#define SK_FQOP_X_BASE_BATCHES 13 // state_in->batches: local batch numbers + this are stream-wide
+#define SK_FQOP_X_LAST_UNITS 14 // units of the stream's last batch so far
+#define SK_FQOP_X_ENDED 15      // the run is over, at this piece's end
+#define SK_FQOP_X_STICKY_MISMATCH 16 // the run ended on a PE-split mismatch, in this piece or before
+
+// start of line l of a window whose first line starts at `first`
+FQO_FN uint64_t fqo_line_start_from(const uint64_t *desc, uint64_t l, uint64_t first)
+{
+    return l == 0 ? first : fqo_line_start(desc, l);
+}
+
+struct fqo_piece_state { // what sk_fastq_order_state hands from piece to piece, as the walk needs it
+    uint64_t carried[2];  // k_i = c_i - a_i
+    uint64_t batches;     // stream-wide, for batch_limit
+    uint32_t ended;
+};
+
+struct fqo_piece_result {
+    uint64_t batches, units, last_units; // the piece's own; last_units 0 when it committed nothing
+    uint64_t batched_lines[2];           // a_i: lines of each input inside the committed batches
+    uint64_t carried[2];                 // the new k_i
+    uint32_t mismatch, ended, table_full, undetermined;
+};
+
+// The reader's rule on a WINDOW (include/sickle_amd.h, sk_trim_fastq_ordered_piece_device_async): fqo_chain from a_i = 0,
+// c_i = st->carried[i], over the nl[i] complete lines of each window, whose first line starts at first[i].  more: text
+// follows, so a stop exists only where the budget is used up on a line of the window; else the batch is undetermined and
+// the walk ends in front of it.  !more: the text's end is the reader's end of input, as in fqo_chain.  A full table ends the
+// walk too (no error).  One binary search per batch and input; capacity + 1 steps at most.
+FQO_FN void fqo_chain_piece(const uint64_t *const desc[2], const uint64_t nl[2], const uint64_t first[2], int n_in, uint32_t m,
+                            uint64_t batch_len, uint64_t capacity, uint64_t limit, const fqo_piece_state *st, bool more,
+                            uint64_t *tab, fqo_piece_result *res)
+{
+    uint64_t a[2] = {0, 0}, c[2] = {st->carried[0] < nl[0] ? st->carried[0] : nl[0], st->carried[1] < nl[1] ? st->carried[1] : nl[1]};
+    bool fin[2] = {false, false}; // !more only: the input has ended inside a committed batch
+    fqo_piece_result r = {0, 0, 0, {0, 0}, {0, 0}, 0, st->ended, 0, 0};
+    tab[0] = 0;
+    while (!r.ended) {
+        if (limit && st->batches + r.batches >= limit) {
+            r.ended = 1;
+            break;
+        }
+        uint64_t e[2] = {0, 0}, len[2] = {0, 0};
+        bool end_now[2] = {false, false}, open[2] = {false, false}; // open: undetermined
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (i >= n_in || fin[i]) continue; // no batch behind the end of the text
+            const uint64_t base = fqo_line_start_from(desc[i], a[i], first[i]) - a[i];
+            if (c[i] == nl[i] || fqo_line_start_from(desc[i], nl[i], first[i]) - nl[i] - base < batch_len) {
+                if (more) {
+                    open[i] = true;
+                    continue;
+                }
+                e[i] = nl[i];
+                end_now[i] = true;
+            } else {
+                uint64_t lo = c[i], hi = nl[i]; // the budget is used up at hi; lo is not a candidate
+                while (hi - lo > 1) {
+                    const uint64_t mid = lo + ((hi - lo) >> 1);
+                    if (fqo_line_start(desc[i], mid) - mid - base >= batch_len) hi = mid; else lo = mid; // mid > 0
+                }
+                e[i] = hi;
+            }
+            len[i] = (e[i] - a[i]) - (e[i] - a[i]) % m;
+        }
+        // fqo_chain's order of tests, each one only on determined batches
+        if (!open[0] && !len[0]) {
+            r.ended = 1;
+            break;
+        }
+        if (open[0] || (n_in == 2 && open[1])) {
+            r.undetermined = 1;
+            break;
+        }
+        if (n_in == 2 && !len[1]) {
+            r.ended = 1;
+            break;
+        }
+        if (n_in == 2 && len[0] != len[1]) {
+            r.mismatch = r.ended = 1;
+            break;
+        }
+        if (r.batches == capacity) {
+            r.table_full = 1;
+            break;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (i >= n_in) continue;
+            a[i] += len[i];
+            c[i] = e[i];
+            fin[i] = end_now[i];
+        }
+        r.last_units = len[0] / m;
+        r.units += r.last_units;
+        tab[++r.batches] = r.units;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        r.batched_lines[i] = a[i];
+        r.carried[i] = c[i] - a[i];
+    }
     *res = r;
 }
 
