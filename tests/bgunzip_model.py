@@ -1,6 +1,7 @@
 """The rules of sk_bgzf_inflate_device_async (include/sickle_amd.h) stated in Python, with zlib as the decoder: frame by
 walking, zlib.decompressobj(-15) per member, the reason codes.  And the test images: member() builds any BGZF member zlib
-can write, images() the valid ones the CPU harness and the GPU tests share, bad_images() the constructed bad ones."""
+can write, images() the valid ones the CPU harness and the GPU tests share, bad_images() the constructed bad ones.  Where
+zlib refuses a stream, text_before_failure() (gunzip_model's inflate) tells whether ISIZE was crossed before the fault."""
 import gzip
 import struct
 import zlib
@@ -74,7 +75,9 @@ def decode(body, crc, isize):
     try:
         text = d.decompress(body, isize + 1)
     except zlib.error:
-        return DEFLATE, b""
+        # zlib was let one byte beyond ISIZE and, with that byte out, reads on to the next token's codes; if the fault lies
+        # there, the byte beyond ISIZE came first, and the first check to fail is the member's reason
+        return (LENGTH if text_before_failure(body) > isize else DEFLATE), b""
     if len(text) > isize:
         return LENGTH, b""
     if not d.eof:
@@ -92,6 +95,28 @@ def decode(body, crc, isize):
     if zlib.crc32(text) != crc:
         return CRC, b""
     return OK, text
+
+
+def text_before_failure(body):
+    """The text bytes in front of the token or block header a raw stream fails at (zlib tells that it fails, not where):
+    gunzip_model's block-by-block inflate, which appends the text token by token and raises at the fault."""
+    import gunzip_model as gm
+
+    class Far(list):  # block() sets far[0] just before it appends the copy of a distance beyond the text
+        at = None
+
+        def __setitem__(self, i, v):
+            if self.at is None:
+                self.at = len(out)
+
+    out, r, far = bytearray(), gm.Reader(body, 0), Far([False])
+    try:
+        final = 0
+        while not final and far.at is None:
+            final = gm.block(r, out, 0, far)[1]
+    except gm.Bad:
+        pass
+    return len(out) if far.at is None else far.at
 
 
 def bgunzip(image):

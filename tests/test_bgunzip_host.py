@@ -1,7 +1,8 @@
 """The device's BGZF reader without a device: the functions of sickle_amd/csrc/sk_inflate_block.h run on the host lane
 after lane (tests/bgunzip_device/inflate_host, built with the address and undefined-behaviour sanitizers) against
 tests/bgunzip_model.py: every image the GPU tests use, the constructed bad ones reason by reason, and a few thousand seeded
-bit flips, byte changes and truncations.  CPU only."""
+bit flips, byte changes and truncations; and the legal streams zlib never writes (tests/foreign_images.py), constructed,
+drawn and bad.  CPU only."""
 import os
 import struct
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 
 import bgunzip_model as bm
 import cli_util as cu
+import foreign_images as fi
 
 HOST = os.path.join(cu.ROOT, "tests", "bgunzip_device", "inflate_host")
 
@@ -57,6 +59,39 @@ def test_constructed_bad_images(tool, tmp_path):
     for (name, image), g in zip(bad.items(), got):
         assert g == bm.bgunzip(image), name
         assert g["error"] != 0
+
+
+def test_foreign_valid_and_drawn_images(tool, tmp_path):
+    """What zlib never writes: no or one distance code, end-of-block alone, 15-bit codes, repeats across HLIT, 284 + 31,
+    set padding bits, thousands of one-symbol and of empty blocks; 40 drawn members in one image"""
+    images = fi.valid("bgzf")
+    got = run_host(tool, [v[0] for v in images.values()], tmp_path)
+    for (name, (image, text)), g in zip(images.items(), got):
+        assert g == fi.expected("bgzf")[name], name
+        assert g["error"] == 0 and g["text"] == text, name
+
+
+def test_foreign_drawn_around_the_wave_and_the_reencoded_fastq(tool, tmp_path):
+    """The images of tests/test_gpu_bgunzip.py::test_foreign_drawn and of the chain test, on the host first"""
+    images = {count: fi.drawn_members("bgzf", seeds)[:2] for count, seeds in fi.WAVE_SEEDS.items()}
+    text, bgzf, plain = fi.reencoded_fastq()
+    images["fastq"] = (bgzf, text)
+    got = run_host(tool, [v[0] for v in images.values()], tmp_path)
+    for (name, (image, text)), g in zip(images.items(), got):
+        assert (g["error"], g["bytes_out"]) == (0, len(text)) and g["text"] == text, name
+        assert g["members"] == (name if name != "fastq" else -(-len(text) // 30000) + 1), name
+
+
+def test_foreign_bad_images(tool, tmp_path):
+    """Reason, member and offset exactly; the two of fi.PRECEDENCE are SK_GZ_LENGTH: under ISIZE 0 the literal in front of
+    the failing match is the first token to fail"""
+    bad = fi.bad_images("bgzf")
+    got = run_host(tool, list(bad.values()), tmp_path)
+    reasons = {name: reason for name, (m, reason) in fi.foreign_bad("bgzf").items()}
+    for (name, image), g in zip(bad.items(), got):
+        assert g == fi.bad_expected("bgzf")[name], name
+        assert g["error"] == reasons[name.rsplit("@", 1)[0]], name
+    assert {reasons[n] for n in fi.PRECEDENCE} == {bm.LENGTH}
 
 
 def corruptions(count, seed):

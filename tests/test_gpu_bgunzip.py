@@ -1,6 +1,8 @@
 """GPU: BGZF read on the device (sk_bgzf_inflate_device_async / finish, Context.bgunzip, Context.trim_gz) against zlib and
 tests/bgunzip_model.py: the project's own writer round trip, every kind of member zlib writes, many members, capacity, bad
-arguments, every reason code, .gz in -> .gz out against the plain-text trim, and a slice of tests/soak_bgunzip.py."""
+arguments, every reason code, .gz in -> .gz out against the plain-text trim, a slice of tests/soak_bgunzip.py, and the legal
+streams zlib never writes (tests/foreign_images.py): constructed, drawn and bad, which tests/test_bgunzip_host.py runs
+through the same source on the host."""
 import ctypes as C
 import gzip
 
@@ -8,6 +10,7 @@ import pytest
 
 import bgunzip_model as bm
 import cli_util as cu
+import foreign_images as fi
 import trim_model as tm
 from bgzf_raw import SENTINEL, to_device, torch_mod, upload
 from sickle_amd import capi
@@ -70,6 +73,43 @@ def test_every_kind_of_member(sk_ctx, images):
         assert c["members"] == bm.bgunzip(image)["members"] and c["bytes_out"] == len(text), name
         assert text_of(out, c) == text, name
     assert sk_ctx.bgunzip(to_device(images["all"][0])).cpu().numpy().tobytes() == images["all"][1]
+
+
+# ---- 2b what zlib never writes -------------------------------------------------------------------------------------
+def test_foreign_members(sk_ctx):
+    """Every constructed member singly, and all of them in one image with EOF members between some: on the device the
+    tables are built by the 64 lanes block after block, thousands of times a member in tiny_blocks_*"""
+    for name, (image, text) in fi.foreign_images("bgzf").items():
+        want = fi.expected("bgzf")[name]
+        rc, c, out = inflate(sk_ctx, image, shift=len(name) % 16, capacity=len(text))
+        assert rc == capi.SK_OK, (name, c)
+        assert (c["error"], c["members"], c["bytes_out"]) == (0, want["members"], len(text)), (name, c)
+        assert text_of(out, c) == text, name
+    image, text = fi.foreign_images("bgzf")["foreign_members"]
+    assert sk_ctx.bgunzip(to_device(image)).cpu().numpy().tobytes() == text
+
+
+@pytest.mark.parametrize("count", [64, 65])
+def test_foreign_drawn(sk_ctx, count):
+    """Drawn members around the wave: drawn texts, token streams, block cuts, code lengths, 16/17/18 spellings, padding"""
+    image, text, features = fi.drawn_members("bgzf", fi.WAVE_SEEDS[count])
+    rc, c, out = inflate(sk_ctx, image, shift=count % 16, capacity=len(text))
+    assert rc == capi.SK_OK, c
+    assert (c["error"], c["members"], c["bytes_out"]) == (0, count, len(text)), c
+    assert text_of(out, c) == text
+
+
+def test_foreign_bad(sk_ctx):
+    """Every constructed bad member at index 0, in the middle and last: reason, member and offset exactly.  The two of
+    fi.PRECEDENCE state ISIZE 0 and are SK_GZ_LENGTH: the literal in front of the failing match is the first token to fail."""
+    reasons = {name: reason for name, (m, reason) in fi.foreign_bad("bgzf").items()}
+    for k, (name, image) in enumerate(fi.bad_images("bgzf").items()):
+        want = fi.bad_expected("bgzf")[name]
+        rc, c, out = inflate(sk_ctx, image, shift=k % 16, capacity=want["bytes_out"])
+        assert rc == capi.SK_EDATA, name
+        assert (c["error"], c["error_member"], c["error_offset"], c["members"], c["bytes_out"]) == \
+            (want["error"], want["error_member"], want["error_offset"], want["members"], want["bytes_out"]), (name, c)
+        assert c["error"] == reasons[name.rsplit("@", 1)[0]], name
 
 
 def test_empty_image(sk_ctx):

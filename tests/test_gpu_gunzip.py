@@ -3,7 +3,8 @@ tests/gunzip_model.py and the host run of the same stages (tests/test_gunzip_hos
 images cut into one, a few and hundreds of stretches, the placeholder cases, many members, capacity, every reason code at
 member 0 and in a later stretch, bad arguments, and plain .gz in -> .gz out against the BGZF path.  Beyond the fixtures'
 sizes: images of more than 16 MiB read by one stretch, a guessed block beyond the text cap, 6 000 members, one member of
-more than 4 GiB of text, and a slice of tests/soak_gunzip.py."""
+more than 4 GiB of text, a slice of tests/soak_gunzip.py, and the legal streams zlib never writes
+(tests/foreign_images.py) at the default chunk and at 256, 1 024 and 4 096."""
 import ctypes as C
 import gzip
 import struct
@@ -12,12 +13,13 @@ import pytest
 
 import bgunzip_model as bm
 import cli_util as cu
+import foreign_images as fi
 import gunzip_model as gm
 import trim_model as tm
 from bgzf_raw import SENTINEL, to_device, torch_mod, upload
 from sickle_amd import capi
 from test_fastq_api import golden_texts
-from test_gunzip_host import long_runs, run_host, tool  # noqa: F401 (the fixtures that build and run the host harness)
+from test_gunzip_host import host_chunk, long_runs, run_host, tool  # noqa: F401 (the fixtures that build and run the host harness)
 
 pytestmark = pytest.mark.gpu
 GUARD = 64
@@ -109,6 +111,32 @@ def test_bgzf_image_and_long_member(sk_ctx, monkeypatch):
     image, text, _ = gm.big_images()["fq5m_gzip1"]
     got = sk_ctx.gunzip(to_device(image))
     assert got.cpu().numpy().tobytes() == text
+
+
+# ---- 2b what zlib never writes -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("chunk", [0, 256, 1024, 4096])
+def test_foreign_images(sk_ctx, monkeypatch, tool, tmp_path, chunk):  # noqa: F811
+    """Text and counts are the model's; stretches and stretches_used are the host run's of the same stages"""
+    images = fi.valid("gzip")
+    host = run_host(tool, [(v[0], host_chunk(chunk)) for v in images.values()], tmp_path)
+    for (name, (image, text)), h in zip(images.items(), host):
+        want = fi.expected("gzip")[name]
+        rc, c, out = inflate(sk_ctx, image, shift=len(name) % 16, capacity=len(text), chunk=chunk, monkeypatch=monkeypatch)
+        assert rc == capi.SK_OK, (name, chunk, c)
+        assert (c["error"], c["members"], c["bytes_out"]) == (0, want["members"], len(text)), (name, chunk, c)
+        assert text_of(out, c) == text == h["text"], (name, chunk)
+        assert (c["stretches"], c["stretches_used"]) == (h["stretches"], h["stretches_used"]), (name, chunk, c)
+
+
+def test_foreign_bad_and_shifted(sk_ctx, monkeypatch):
+    for k, (name, (image, chunk)) in enumerate(fi.bad_images("gzip").items()):
+        want = fi.bad_expected("gzip")[name]
+        rc, c, out = inflate(sk_ctx, image, shift=k % 16, capacity=want["bytes_out"], chunk=chunk, monkeypatch=monkeypatch)
+        assert rc == capi.SK_EDATA and c["error"] == capi.SK_GZ_DEFLATE, (name, c)
+        assert tuple(c[x] for x in KEYS) == tuple(want[x] for x in KEYS), (name, c)
+    image, text = fi.valid("gzip")["foreign_members"]
+    rc, c, out = inflate(sk_ctx, image, shift=9, capacity=len(text), chunk=1024, monkeypatch=monkeypatch)
+    assert rc == capi.SK_OK and c["members"] == fi.expected("gzip")["foreign_members"]["members"] and text_of(out, c) == text
 
 
 # ---- 3 capacity ----------------------------------------------------------------------------------------------------

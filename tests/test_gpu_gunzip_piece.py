@@ -2,13 +2,16 @@
 against tests/gunzip_piece_model.py: every piece's state and text over images of many small blocks at windows of 600 bytes
 to 1 MiB, every kind of member at windows that hold a piece and that stall, a window end swept over a member boundary,
 the capacity cut, every damaged image, a sliding image buffer, and the driver.  The pieces of a stream are all enqueued
-before the first is finished: each has its own workspace, text buffer and state."""
+before the first is finished: each has its own workspace, text buffer and state.  And the legal streams zlib never writes
+(tests/foreign_images.py): one-symbol blocks, runs of empty blocks and set padding bits in pieces, where nearly every
+state carries a bit offset inside a byte."""
 import ctypes as C
 import functools
 import gzip
 
 import pytest
 
+import foreign_images as fi
 import gunzip_model as gm
 import gunzip_piece_model as pm
 from bgzf_raw import SENTINEL, to_device, torch_mod, upload
@@ -229,6 +232,79 @@ def test_damaged_images(sk_ctx, monkeypatch, name):
     for g in got[len(want):]:  # void
         assert g["rc"] == capi.SK_EDATA and g["counts"]["inherited"] == 1 and g["counts"]["bytes_out"] == 0 and g["text"] == b""
         assert {k: g["state"][k] for k in verdict} == verdict and g["raw"] == bad["raw"], name
+
+
+# ---- 5b what zlib never writes --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("window", [600, 4096])
+@pytest.mark.parametrize("name", list(fi.TINY) + ["empty_runs", "empty_runs_fixed", "empty_runs_pigz", "pad_bits", "foreign_members"])
+def test_foreign_images_in_pieces(sk_ctx, monkeypatch, name, window):
+    """Every piece's state and text against the model, all pieces enqueued before the first finish.  foreign_members holds
+    blocks wider than the window: such a piece is window-limited, leaves its state_in as it was and is repeated at 70 000."""
+    set_chunk(monkeypatch, 256)
+    image, text = fi.valid("gzip")[name]
+    want, whole = fi.piece_stream("valid", name, window)
+    assert whole == text
+    p = Pieces(sk_ctx, image, 2 * len(want) + 2, shift=len(name) % 16)
+    spare = len(want) + 1  # states that take what a stalled piece publishes
+    capacity = max(len(t) for _, t, _ in want)
+    for i, (w, t, info) in enumerate(want):
+        if info["stalled"]:
+            p.add(window, capacity, i, spare + i)
+        p.add(info["window"], capacity, i, i + 1)
+    got, real = p.finish(), []
+    for i, (w, t, info) in enumerate(want):
+        if info["stalled"]:
+            g = got.pop(0)
+            assert g["rc"] == capi.SK_EDATA and g["counts"]["window_limited"] == 1 and g["state"]["status"] == 1, (name, i, g["counts"])
+        real.append(got.pop(0))
+    check_against_model(real, want, text, (name, window))
+    assert name != "foreign_members" or sum(info["stalled"] for _, _, info in want) >= 5
+
+
+@pytest.mark.parametrize("name", ["tiny_blocks_match", "tiny_blocks_batch"])
+def test_foreign_capacity_cut(sk_ctx, monkeypatch, name):
+    """The whole image in the window and 4 096 bytes of text a piece: every block boundary is a resume point, and each
+    piece ends at one, within the capacity (tests/test_gunzip_piece_host.py::test_foreign_capacity_cut: no stretch of
+    these images at chunk 256 holds more)"""
+    image, text = fi.valid("gzip")[name]
+    set_chunk(monkeypatch, 256)
+    points = pm.resume_points(image)
+    p = Pieces(sk_ctx, image, 8)
+    for i in range(8):
+        p.add(len(image), 4096, i, i + 1)
+    got, pos = p.finish(), -1
+    for g in got:
+        assert g["rc"] == capi.SK_OK and g["counts"]["bytes_out"] <= 4096, g["counts"]
+        if g["counts"]["bytes_out"] or not g["state"]["done"]:
+            assert g["state"]["pos_bit"] > pos and (g["state"]["pos_bit"], g["state"]["in_member"]) in points, g["counts"]
+            pos = g["state"]["pos_bit"]
+    assert b"".join(g["text"] for g in got) == text and got[-1]["state"]["done"] == 1
+    assert sum(1 for g in got if g["text"]) >= -(-len(text) // 4096)
+
+
+@pytest.mark.parametrize("name", ["one_dist_unassigned@1", "stored_nlen@last"])
+def test_foreign_bad_images_in_pieces(sk_ctx, monkeypatch, name):
+    """The failing piece's verdict is the whole-image model's, and the pieces behind it are void"""
+    image, chunk = fi.bad_images("gzip")[name]
+    set_chunk(monkeypatch, chunk)
+    want, whole = fi.piece_stream("bad", name, 4096, 0)
+    ref = fi.bad_expected("gzip")[name]
+    assert whole is None
+    p = Pieces(sk_ctx, image, len(want) + 2, shift=len(name) % 16)
+    for i in range(len(want) + 2):
+        p.add(4096, 65536, i, i + 1)
+    got = p.finish()
+    for g, (w, t, info) in zip(got[:len(want) - 1], want):
+        assert g["rc"] == capi.SK_OK and g["text"] == t and {k: g["state"][k] for k in FIELDS} == {k: w[k] for k in FIELDS}, name
+    bad = got[len(want) - 1]
+    # a block that fails in a window that does not reach the image's end might be one the window cuts: window_limited
+    assert bad["rc"] == capi.SK_EDATA and bad["counts"]["inherited"] == 0, bad["counts"]
+    assert bad["counts"]["window_limited"] == want[-1][2]["window_limited"] == int(name.endswith("@1")), bad["counts"]
+    verdict = {k: bad["state"][k] for k in ("error", "error_member", "error_offset")}
+    assert verdict == {k: ref[k] for k in verdict} and verdict["error"] == gm.DEFLATE, (name, verdict)
+    for g in got[len(want):]:  # void
+        assert g["rc"] == capi.SK_EDATA and g["counts"]["inherited"] == 1 and g["counts"]["bytes_out"] == 0 and g["text"] == b""
+        assert g["raw"] == bad["raw"], name
 
 
 # ---- 6 a sliding image buffer ---------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """GPU: Context.trim_gzip_stream, the FASTQ trim in pieces fed by the plain-gzip reader in pieces, against trim_fastq on
 the whole text: every golden run with plain gzip in (mate 2 compressed at another level) and FASTQ or BGZF out, a BGZF
 image as input, 50 drawn texts of tests/soak_fastq.py's generator at piece sizes from 4 096 to 100 000, and the two
-failures that name a parameter.  The images have small blocks (gunzip_model.small_blocks) and are read with
+failures that name a parameter, and the golden FASTQ re-encoded by tests/deflate_writer.py's drawn tokenizer and block cutter
+through trim_gz and trim_gzip_stream.  The images have small blocks (gunzip_model.small_blocks) and are read with
 SK_GZIP_CHUNK = 1024 or 256, so that a piece of a few KB holds several stretches."""
 import gzip
 
@@ -10,6 +11,7 @@ import pytest
 
 import cli_util as cu
 import fastq_model as fm
+import foreign_images as fi
 import gunzip_model as gm
 import soak_fastq
 import trim_model as tm
@@ -80,6 +82,24 @@ def test_bgzf_image_and_failures(sk_ctx, monkeypatch):
     with pytest.raises(capi.TrimError, match="piece_bytes") as e:  # a stretch of ordinary gzip holds far more than 4 096 bytes
         run_stream(sk_ctx.trim_gzip_stream(params, plain, piece_bytes=4096, window_bytes=1 << 20, gz=False))
     assert e.value.rc == capi.SK_ESPACE
+
+
+def test_foreign_encoding_of_the_golden_fastq(sk_ctx, monkeypatch):
+    """tests/golden/inputs/test.fastq as BGZF members and as one plain gzip member of drawn blocks, code lengths, repeats and
+    padding: .gz in -> .gz out and the stream in pieces give what trim_fastq gives on the text"""
+    monkeypatch.setenv("SK_GZIP_CHUNK", "1024")
+    text, bgzf, plain = fi.reencoded_fastq()
+    params = capi.make_params("illumina", 20, 20, False, False)
+    want, counts = sk_ctx.trim_fastq(params, to_device(text), mode="se")
+    want = want[0].cpu().numpy().tobytes()
+    assert 0 < len(want) < len(text)
+    for image in (bgzf, plain):
+        got, counts2 = sk_ctx.trim_gz(params, to_device(image), mode="se")
+        assert counts2 == counts and gzip.decompress(got[0].cpu().numpy().tobytes()) == want
+        got, st = run_stream(sk_ctx.trim_gzip_stream(params, image, piece_bytes=200_000, gz=False))
+        assert got[0] == want and st.pieces >= 4
+        for key in ("records_in", "records", "bytes", "tail_lines"):
+            assert st.counts[key] == counts[key], key
 
 
 @pytest.mark.parametrize("group", range(2))

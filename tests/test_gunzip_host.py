@@ -4,7 +4,7 @@ undefined-behaviour sanitizers) against tests/gunzip_model.py: every image the G
 into one, a few and hundreds of stretches, every damaged image, and seeded corruptions.  The same once more with a second
 build of the harness whose bit reader re-bases every 64 bytes (gunzip_host_rebase), the images beyond 16 MiB, beyond the
 guess's text cap and with 6 000 members (gunzip_model.long_images), and the CRC-32 shift table against Python integers.
-CPU only."""
+And the legal streams zlib never writes (tests/foreign_images.py) through both builds.  CPU only."""
 import os
 import struct
 import subprocess
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import cli_util as cu
+import foreign_images as fi
 import gunzip_model as gm
 
 HOST = os.path.join(cu.ROOT, "tests", "gunzip_device", "gunzip_host")
@@ -158,6 +159,41 @@ def test_rebase_damaged_images_and_corruptions(rebase_tool, tmp_path):
         assert tuple(g[k] for k in KEYS) == tuple(want[k] for k in KEYS), (what, g, want)
         if want["error"] == 0:
             assert g["text"] == want["text"], what
+
+
+# ---- legal streams zlib never writes -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("build", ["", "_rebase"])
+def test_foreign_images(tool, tmp_path, build):
+    """Every key of the model at chunks of 256, 1 024 and 32 768 (for `nested`, whose stored text is full of block starts,
+    the text alone).  At 256 the chain joins at guessed starts inside the one-symbol blocks and between the empty ones: more
+    than half the stretches are used.  (empty_runs_fixed alone is 20 000 fixed blocks and has no start to guess: the search
+    takes non-final dynamic blocks only.)"""
+    images = fi.valid("gzip")
+    items = [(name, image, text, chunk) for chunk in (256, 1024, 32768) for name, (image, text) in images.items()]
+    got = run_host(tool + build, [(i[1], i[3]) for i in items], tmp_path)
+    for (name, image, text, chunk), g in zip(items, got):
+        want = fi.expected("gzip")[name]
+        assert g["text"] == text, (name, chunk)
+        if name not in fi.NESTED:
+            assert {k: g[k] for k in want} == want and g["stretches"] == -(-len(image) // chunk), (name, chunk)
+        if chunk == 256 and name in fi.TINY + ("empty_runs", "empty_runs_pigz"):
+            assert g["stretches_used"] > g["stretches"] / 2, (name, g["stretches_used"], g["stretches"])
+
+
+def test_reencoded_fastq(tool, tmp_path):
+    """The chain test's plain member and its BGZF image, on the host first, at the chunk that test reads them with"""
+    text, bgzf, plain = fi.reencoded_fastq()
+    for g in run_host(tool, [(plain, 1024), (bgzf, 1024)], tmp_path):
+        assert g["error"] == 0 and g["text"] == text and g["stretches_used"] > g["stretches"] / 4, (g["stretches"], g["stretches_used"])
+
+
+@pytest.mark.parametrize("build", ["", "_rebase"])
+def test_foreign_bad_images(tool, tmp_path, build):
+    bad = fi.bad_images("gzip")
+    got = run_host(tool + build, list(bad.values()), tmp_path)
+    for (name, (image, chunk)), g in zip(bad.items(), got):
+        want = fi.bad_expected("gzip")[name]
+        assert want["error"] == gm.DEFLATE and tuple(g[k] for k in KEYS) == tuple(want[k] for k in KEYS), (name, g)
 
 
 # ---- the long images, with the threshold where the library has it ------------------------------------------------------

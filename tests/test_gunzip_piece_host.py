@@ -2,7 +2,8 @@
 sickle_amd/csrc/sk_gunzip_block.h in the order of sk_gunzip_piece.hip's launches, lane after lane, built with the address
 and undefined-behaviour sanitizers) streams images from the zero state and is held against tests/gunzip_piece_model.py:
 every piece's state, the texts, the verdict on damaged images, window-limited pieces and their repeat, the capacity cut.
-The same once more with the build whose bit reader re-bases every 64 bytes.  CPU only."""
+The same once more with the build whose bit reader re-bases every 64 bytes, and the legal streams zlib never writes
+(tests/foreign_images.py).  CPU only."""
 import os
 import struct
 import subprocess
@@ -10,6 +11,7 @@ import subprocess
 import pytest
 
 import cli_util as cu
+import foreign_images as fi
 import gunzip_model as gm
 import gunzip_piece_model as pm
 
@@ -49,9 +51,9 @@ def run_host(tool, items, d, tag="batch"):
     return out
 
 
-def check_stream(name, got, image, text, window, grow=0):
+def check_stream(name, got, image, text, window, grow=0, model=None):
     """got: the harness's pieces; every piece against the model's, in order"""
-    want, whole = pm.stream(image, window, grow)
+    want, whole = model if model is not None else pm.stream(image, window, grow)
     got = [g for g in got if not (g["window_limited"] and grow)]  # the repeat is the model's piece
     assert len(got) == len(want), (name, window, len(got), len(want))
     for i, (g, (w, t, info)) in enumerate(zip(got, want)):
@@ -115,6 +117,53 @@ def test_damaged_images_in_pieces(tool, tmp_path):
         # behind the one that failed are void, so the stream's count ends with that piece
         stops = want["error"] in (gm.HEADER, gm.TRUNCATED) or (want["error"] == gm.DEFLATE and not name.startswith("far@"))
         assert last["members"] == want["members"] if stops else want["error_member"] <= last["members"] <= want["members"], (name, last)
+
+
+@pytest.mark.parametrize("build", ["", "_rebase"])
+def test_foreign_images_in_pieces(tool, tmp_path, build):
+    """Every published state against the model at windows of 600, 4 096 and 70 000 (a block wider than the window stalls and
+    is repeated at 70 000); the one-symbol blocks also at the smallest window in which each of their blocks fits, where
+    nearly every piece is one block and resumes inside a byte"""
+    from test_gunzip_piece_model import foreign_cases
+    cases = [c for c in foreign_cases() if not build or c[3] in (600,) or c[3] < 600]
+    got = run_host(tool + build, [(image, 256, w, len(text), 70000) for name, image, text, w in cases], tmp_path)
+    for (name, image, text, w), g in zip(cases, got):
+        g = check_stream(name, g, image, text, w, 70000, fi.piece_stream("valid", name, w))
+        assert g[-1]["done"] == 1, (name, w)
+        if name in fi.TINY and w < 600:
+            assert sum(1 for p in g if p["pos_bit"] & 7) > len(g) // 2 and len(g) > 100, (name, w, len(g))
+
+
+def test_foreign_bad_images_in_pieces(tool, tmp_path):
+    bad = fi.bad_images("gzip")
+    items = [(name, image, w) for w in (600, 4096, 70000) for name, (image, chunk) in bad.items()]
+    got = run_host(tool, [(image, 256, w, 200000, 70000) for name, image, w in items], tmp_path)
+    for (name, image, w), g in zip(items, got):
+        g = check_stream(name, g, image, None, w, 70000, fi.piece_stream("bad", name, w))
+        want, last = fi.bad_expected("gzip")[name], g[-1]
+        assert last["status"] == 1 and last["written"] == 0, name
+        assert {k: last[k] for k in ("error", "error_member", "error_offset")} == \
+            {k: want[k] for k in ("error", "error_member", "error_offset")}, (name, w, last)
+
+
+def test_reencoded_fastq_in_pieces(tool, tmp_path):
+    """The chain test's images through windows of 66 666 bytes (a third of its pieces of 200 000), the text alone"""
+    text, bgzf, plain = fi.reencoded_fastq()
+    for g in run_host(tool, [(plain, 1024, 66666, len(text), 0), (bgzf, 1024, 66666, len(text), 0)], tmp_path):
+        assert all(p["status"] == 0 for p in g) and g[-1]["done"] == 1 and len(g) > 8
+        assert b"".join(p["text"] for p in g) == text
+
+
+def test_foreign_capacity_cut(tool, tmp_path):
+    """One-token blocks, the whole image in the window, 4 096 bytes of text a piece: each piece ends at a block boundary
+    within the capacity and the next goes on from there"""
+    for name in ("tiny_blocks_match", "tiny_blocks_batch"):
+        image, text = fi.valid("gzip")[name]
+        points = pm.resume_points(image)
+        g = run_host(tool, [(image, 256, len(image), 4096, 0)], tmp_path)[0]
+        assert all(p["status"] == 0 and (p["pos_bit"], p["in_member"]) in points and p["bytes_out"] <= 4096 for p in g), name
+        assert max(p["max_stretch_text"] for p in g) <= 4096 and all(b["pos_bit"] > a["pos_bit"] for a, b in zip(g, g[1:])), name
+        assert b"".join(p["text"] for p in g) == text and g[-1]["done"] == 1 and len(g) >= -(-len(text) // 4096), name
 
 
 def test_capacity_cut(tool, tmp_path):

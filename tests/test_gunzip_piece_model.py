@@ -1,10 +1,12 @@
 """CPU: tests/gunzip_piece_model.py, the rules of the piece call in Python, against gunzip_model.gunzip: streamed at
 windows of 600, 1 024, 4 096 and 70 000 bytes it reproduces the text of every valid image and the verdict on every damaged
-one, and every state's member_crc is zlib's crc32 of the open member's text."""
+one, and every state's member_crc is zlib's crc32 of the open member's text.  The same for the legal streams zlib never writes (tests/foreign_images.py), the
+one-symbol blocks also at the smallest window in which every block fits."""
 import zlib
 
 import pytest
 
+import foreign_images as fi
 import gunzip_model as gm
 import gunzip_piece_model as pm
 
@@ -60,6 +62,53 @@ def test_damaged_images(window):
         # a void piece hands the failure on
         st, t, info = pm.piece(image, pieces[-1][0], window, 1)
         assert st == pieces[-1][0] and t == b"" and info["inherited"] == 1
+
+
+FOREIGN_WINDOWS = (600, 4096, 70000)
+
+
+def smallest_window(image):
+    """The smallest window at which no piece of the image stalls: the widest block, a header in front of it or a trailer
+    behind it included (searched from a little below the widest block, and the window one byte smaller stalls)"""
+    w = max(fi.block_spans(image)) - 2
+    while any(info["window_limited"] for _, _, info in pm.stream(image, w)[0]):
+        w += 1
+    assert any(info["window_limited"] for _, _, info in pm.stream(image, w - 1)[0])
+    return w
+
+
+def foreign_cases():
+    """(name, image, text, window): every image at the three windows, the one-symbol blocks at their smallest too"""
+    images = fi.valid("gzip")
+    out = [(name, image, text, w) for w in FOREIGN_WINDOWS for name, (image, text) in images.items()]
+    return out + [(name, images[name][0], images[name][1], smallest_window(images[name][0])) for name in fi.TINY]
+
+
+def test_foreign_images():
+    """Blocks wider than the window stall and are repeated at 70 000 (no block here is wider than that)"""
+    for name, image, text, window in foreign_cases():
+        pieces, whole = fi.piece_stream("valid", name, window)
+        want = fi.expected("gzip")[name]
+        assert whole == text == want["text"], (name, window)
+        last = pieces[-1][0]
+        assert last["done"] == 1 and last["in_member"] == 0 and last["text_bytes"] == len(text), (name, window)
+        assert last["members"] == want["members"] and last["pos_bit"] == 8 * len(image), (name, window)
+        at = 0
+        for st, t, info in pieces:
+            at += len(t)
+            assert st["text_bytes"] == at and st["history"] == (bytes(32768) + text[:at])[-32768:], (name, window)
+    assert [c[3] for c in foreign_cases()[-3:]] < [100, 100, 400]
+
+
+def test_foreign_bad_images():
+    for name, (image, chunk) in fi.bad_images("gzip").items():
+        want = fi.bad_expected("gzip")[name]
+        for window in FOREIGN_WINDOWS:
+            pieces, whole = fi.piece_stream("bad", name, window)
+            got = pm.verdict(pieces)
+            assert whole is None and pieces[-1][0]["status"] == 1, (name, window)
+            assert {k: got[k] for k in ("error", "error_member", "error_offset")} == \
+                {k: want[k] for k in ("error", "error_member", "error_offset")}, (name, window, got, want)
 
 
 def test_resume_points_hold_every_state():

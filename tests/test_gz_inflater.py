@@ -2,7 +2,7 @@
 on the same bytes: every compression level and strategy, stored / fixed / dynamic blocks, long
 Huffman codes (subtables), matches at the far end of the window, concatenated members with trailing
 garbage, all optional header fields, odd read sizes, and randomly damaged or truncated files (no
-crash, never silently wrong bytes).  CPU only; tests/cpu_shim/inflate_check is test infrastructure."""
+crash, never silently wrong bytes), and the legal streams zlib never writes (tests/foreign_images.py).  CPU only; tests/cpu_shim/inflate_check is test infrastructure."""
 import gzip
 import os
 import struct
@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import cli_util as cu
+import foreign_images as fi
 
 BIN = os.path.join(cu.ROOT, "tests", "cpu_shim", "inflate_check")
 PAR = os.path.join(cu.ROOT, "tests", "cpu_shim", "parallel_check")
@@ -147,6 +148,32 @@ def test_parallel_decoder_damaged_input(inflate_check, tmp_path):
         else:
             assert b"error:" in pr.stderr
     assert clean < 10
+
+
+def test_foreign_streams_decode_like_zlib(inflate_check, tmp_path):
+    """No or one distance code, end-of-block alone, 15-bit codes, repeats across HLIT, 284 + 31, set padding bits, thousands
+    of one-symbol and of empty blocks, gzip inside stored blocks, 40 drawn members: GzInflater at four read sizes, GzParallel
+    at four (chunk, width)"""
+    for name, (blob, want) in fi.valid("gzip").items():
+        path = str(tmp_path / (name + ".gz"))
+        open(path, "wb").write(blob)
+        for piece in (32 << 20, 1, 7, 4096):
+            pr = subprocess.run([inflate_check, path, str(piece)], capture_output=True)
+            assert pr.returncode == 0 and pr.stdout == want, (name, piece, pr.stderr[:200])
+        for chunk, width in ((256, 8), (4096, 8), (30000, 3), (70000, 1)):
+            pr = subprocess.run([PAR, path, str(chunk), str(width), str(1 << 20)], capture_output=True)
+            assert pr.returncode == 0 and pr.stdout == want, (name, chunk, width, pr.stderr[-200:])
+
+
+def test_foreign_bad_streams_are_reported(inflate_check, tmp_path):
+    good = fi.valid("gzip")["tiny_blocks_batch"][0]
+    for name, (member, reason) in fi.foreign_bad("gzip").items():
+        for k, blob in enumerate((member, good + member)):
+            path = str(tmp_path / ("%s_%d.gz" % (name, k)))
+            open(path, "wb").write(blob)
+            for tool, args in ((inflate_check, ["4096"]), (PAR, ["256", "8"]), (PAR, ["30000", "3"])):
+                pr = subprocess.run([tool, path] + args, capture_output=True)
+                assert pr.returncode == 2 and b"error:" in pr.stderr, (name, k, tool, args, pr.returncode)
 
 
 def test_fast_encoder_round_trips(inflate_check, tmp_path):
