@@ -287,7 +287,9 @@ typedef struct {
     uint64_t record_capacity; /* entries available in read_index; offsets holds record_capacity + 1 */
 } sk_trim_output;
 
-enum { SK_TRIM_SE = 0, SK_TRIM_PE_SPLIT = 1, SK_TRIM_PE_INTERLEAVED = 2 };
+/* SK_TRIM_PE_COMBO_ALL is a mode of the FASTQ text calls only (below): sk_trim_device_async returns SK_EINVAL for it, since
+ * a packed read has no name line for an N record to keep. */
+enum { SK_TRIM_SE = 0, SK_TRIM_PE_SPLIT = 1, SK_TRIM_PE_INTERLEAVED = 2, SK_TRIM_PE_COMBO_ALL = 3 };
 
 typedef struct {
     uint64_t records[3], bytes[3]; /* what each output needs, also when it was not produced or did not fit */
@@ -331,6 +333,25 @@ int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_tri
  *   SK_TRIM_SE              out[0]: every kept record
  *   SK_TRIM_PE_SPLIT        out[0]: mate 1 of the pairs with both kept, out[1]: their mate 2, out[2]: singles
  *   SK_TRIM_PE_INTERLEAVED  out[0]: both mates of such pairs, out[2]: singles
+ *   SK_TRIM_PE_COMBO_ALL    out[0]: both mates of EVERY pair, a mate that is not kept as an N record   (out[1], out[2] unused)
+ * SK_TRIM_PE_COMBO_ALL is sickle's documented -M (reference README.md:116-120; the record layout is upstream sickle 1.33's).
+ * Its input and framing are SK_TRIM_PE_INTERLEAVED's in every respect: one text (text[1] NULL), pairs are records 2k and
+ * 2k + 1, an odd last record is checked and dropped (dropped_unpaired = 1), and the checks and their precedence are the
+ * same.  Every read of every framed pair goes to out[0], mate 1 then mate 2, so records 2k and 2k + 1 of the output are
+ * always pair k, also when neither mate is kept.  A kept read (three >= 0) is emitted as above.  A read that is not kept is
+ * emitted as an N record: its name line verbatim (the whole first line, a comment and a trailing '\r' included), then the
+ * six bytes 'N' '\n' '+' '\n' Q '\n'.  The '+' of an N record is bare: the record is synthetic, its own '+' line is not
+ * copied.  Q is the byte sk_quality_constants(params->qualtype)[1], the type's lowest quality (phred 4, sanger 33, solexa
+ * 58, illumina 64).  out[1] and out[2] are ignored (never written, whatever they hold) and records[1] = records[2] =
+ * bytes[1] = bytes[2] = 0.  record_index gets the read number of every record, N records included.  After an error
+ * nothing is written, N records neither.  The N records are not counted on their own (sk_fastq_counts is fixed): their
+ * number is records[0] less the records[0] + records[2] of a counting SK_TRIM_PE_INTERLEAVED call on the same text.
+ * Output size: for the other modes an output never exceeds its text(s) by more than one '\n' each (the one an
+ * unterminated last line gains).  An N record is one byte LONGER than the record it stands for when that is a 1-base read
+ * with an empty '+' line (name + 7 bytes against name + 6), so out[0] of SK_TRIM_PE_COMBO_ALL can exceed the text:
+ *   bytes[0] <= bytes of text + records_in + 1 <= T + floor((T + 1) / 8) + 1
+ * (a valid record has 8 bytes or more, 7 if it is the unterminated last one).  Size out[0] by this, or by a counting call.
+ * The workspace formula is the same: its emission table has room for every record of the packed batch.
  * An output is produced iff its text is not NULL (16-byte aligned); record_index (8-byte aligned, or NULL) then gets the
  * read number of each record.  An output whose bytes exceed capacity, or whose records exceed record_capacity while
  * record_index is given, gets nothing written; finish then returns SK_ESPACE with the counts.  With every text NULL the
@@ -366,7 +387,7 @@ typedef struct {
 typedef struct {
     uint64_t records_in[2];        /* complete records framed per input */
     uint64_t tail_lines[2];        /* lines after the last complete record: not trimmed, not an error */
-    uint64_t dropped_unpaired;     /* SK_TRIM_PE_INTERLEAVED with an odd record count: 1 */
+    uint64_t dropped_unpaired;     /* SK_TRIM_PE_INTERLEAVED, SK_TRIM_PE_COMBO_ALL with an odd record count: 1 */
     uint64_t records[3], bytes[3]; /* what each output needs, also when not produced or too small (0 after an error) */
     int32_t format_error;          /* SK_FQ_* of the lowest malformed record, SK_FQ_OK if none */
     uint32_t format_input;         /* 0 / 1 */
@@ -390,7 +411,8 @@ int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, 
  * for what follows.  This comment is the normative text of the rule.
  *
  * Lines and units.  A line ends at '\n'; len(line) does not count it.  m = 4 lines (SK_TRIM_SE, SK_TRIM_PE_SPLIT) or 8
- * (SK_TRIM_PE_INTERLEAVED), L = order->batch_len.  The unit of ordering is a read (SE) or a pair (both PE modes).
+ * (SK_TRIM_PE_INTERLEAVED, SK_TRIM_PE_COMBO_ALL), L = order->batch_len.  The unit of ordering is a read (SE) or a pair (every
+ * PE mode).
  * Batches (the reference's reader, src/GZReader.cpp:59-132), per input text, on line numbers.  Start with a = c = 0, then:
  *   1. if c is already the number of lines the input has ended, and the current set is the carried lines [a, c);
  *   2. else e = the smallest line number > c with sum(len(lines[a:e])) >= L; without one e = the number of lines and the
@@ -835,7 +857,7 @@ int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_
  * consumed = n_i.
  * more != 0.  A line exists only if its '\n' lies in the window; the bytes behind the last '\n' are no line and are not
  * closed.  With r_i = lines_i / 4 the piece takes u records from each input: SK_TRIM_SE u = r_0; SK_TRIM_PE_INTERLEAVED
- * u = r_0 & ~1; SK_TRIM_PE_SPLIT u = min(r_0, r_1).  Records [0, u) of each input are checked, packed, scanned, routed and
+ * and SK_TRIM_PE_COMBO_ALL u = r_0 & ~1; SK_TRIM_PE_SPLIT u = min(r_0, r_1).  Records [0, u) of each input are checked, packed, scanned, routed and
  * emitted exactly as sk_trim_fastq_device_async does on a text made of those records alone (read numbers count from the
  * piece's first record).  Everything behind them is the carry: not checked, not scanned, no format or range error comes
  * from it; SK_FQ_PAIR_COUNT never occurs and dropped_unpaired is 0.  records_in[i] = u; tail_lines[i] = the complete lines

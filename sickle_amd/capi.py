@@ -16,8 +16,20 @@ SK_GZ_OK, SK_GZ_HEADER, SK_GZ_TRUNCATED, SK_GZ_DEFLATE, SK_GZ_LENGTH, SK_GZ_CRC 
 # why a FASTQ record is malformed (sk_trim_fastq_device_finish), in the order the reference checks
 (SK_FQ_OK, SK_FQ_ID_SHORT, SK_FQ_ID_NO_AT, SK_FQ_SEQ_EMPTY, SK_FQ_QUAL_EMPTY, SK_FQ_LENGTHS, SK_FQ_TOO_LONG,
  SK_FQ_PAIR_COUNT) = range(8)
-SK_TRIM_SE, SK_TRIM_PE_SPLIT, SK_TRIM_PE_INTERLEAVED = 0, 1, 2
-TRIM_MODES = {"se": SK_TRIM_SE, "pe_split": SK_TRIM_PE_SPLIT, "pe_interleaved": SK_TRIM_PE_INTERLEAVED}
+SK_TRIM_SE, SK_TRIM_PE_SPLIT, SK_TRIM_PE_INTERLEAVED, SK_TRIM_PE_COMBO_ALL = 0, 1, 2, 3
+# "pe_combo_all" (sickle's -M) is a mode of the FASTQ text calls only
+TRIM_MODES = {"se": SK_TRIM_SE, "pe_split": SK_TRIM_PE_SPLIT, "pe_interleaved": SK_TRIM_PE_INTERLEAVED,
+              "pe_combo_all": SK_TRIM_PE_COMBO_ALL}
+# the outputs each mode uses
+TRIM_OUTPUTS = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2), "pe_combo_all": (0,)}
+
+
+def fastq_output_bound(text_bytes, mode):
+    """The most bytes one output of a FASTQ text call can need for text_bytes bytes of text, without a look at the text
+    (include/sickle_amd.h): the text plus the '\\n' an unterminated last line of each input gains; "pe_combo_all" adds one
+    byte per record, since an N record is one byte longer than a 1-base read with an empty '+' line, and a valid record
+    has 8 bytes or more (7 for an unterminated last one)."""
+    return text_bytes + 2 + ((text_bytes + 1) // 8 if mode == "pe_combo_all" else 0)
 QUALTYPES = {"phred": 0, "sanger": 1, "solexa": 2, "illumina": 3}
 
 # every entry point include/sickle_amd.h declares
@@ -600,7 +612,7 @@ class Context:
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         counts = self.trim_device(cuts.data_ptr(), n, [TrimOutput() for _ in range(3)], ws.data_ptr(), ws_bytes,
                                   mode=mode, stream=stream, **batch)
-        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        used = TRIM_OUTPUTS[mode]
         bufs, outs = [None] * 3, [TrimOutput() for _ in range(3)]
         for o in used:
             R, B = counts["records"][o], counts["bytes"][o]
@@ -860,6 +872,8 @@ class Context:
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
         record_index=True a pair (text, index) with the read number of each record (int64).  Raises FormatError,
         RangeError or TrimError.
+        mode "pe_combo_all" (sickle's -M, SK_TRIM_PE_COMBO_ALL): an interleaved text in, every pair out in output 0, a mate
+        that is not kept as its name line and N / + / the lowest quality byte; every driver below takes it too.
         order=(threads, batch_len): the records in the order the reference writes them at -a threads with its reader's
         byte budget batch_len (sk_trim_fastq_ordered_device_async); counts then has the order counts under "order", and
         LongLineError may be raised.  A batch table that was too small shows in the count-only pass, which is then
@@ -891,7 +905,7 @@ class Context:
                                                                      mode=mode, max_read_len=max_read_len, stream=stream),
                                 self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[1]
         counts = run([FastqOutput() for _ in range(3)])
-        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        used = TRIM_OUTPUTS[mode]
         bufs, outs = [None] * 3, [FastqOutput() for _ in range(3)]
         for o in used:
             R, B = counts["records"][o], counts["bytes"][o]
@@ -942,8 +956,8 @@ class Context:
 
     def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
-        the current stream: the outputs are sized by the inputs (a trimmed text never exceeds them by more than one
-        newline each), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
+        the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
+        than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
         as bgzf's."""
@@ -964,8 +978,8 @@ class Context:
         else:
             ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
-        cap = sum(sizes) + 2
+        used = TRIM_OUTPUTS[mode]
+        cap = fastq_output_bound(sum(sizes), mode)
         bound = lib().sk_bgzf_bound(cap, SK_BGZF_EOF)
         zws_bytes = lib().sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
         outs, trimmed, images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
@@ -1182,8 +1196,8 @@ class Context:
         else:
             ws_bytes = L.sk_trim_fastq_ordered_workspace_bytes(sum(capacities), params.trunc_n, order.batch_capacity)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
-        cap = sum(capacities) + 2
+        used = TRIM_OUTPUTS[mode]
+        cap = fastq_output_bound(sum(capacities), mode)
         bound = L.sk_bgzf_bound(cap, SK_BGZF_EOF)
         zws_bytes = L.sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
         outs, trimmed, out_images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
@@ -1390,7 +1404,7 @@ class FastqStream:
         self.piece_bytes = int(piece_bytes)
         self.room = ((self.piece_bytes if room is None else int(room)) + 15) & ~15
         self.gz, self.search, self.max_read_len = gz, search, max_read_len
-        self.used = {"se": (0,), "pe_split": (0, 1, 2), "pe_interleaved": (0, 2)}[mode]
+        self.used = TRIM_OUTPUTS[mode]
         self.counts = {"records_in": [0, 0], "tail_lines": [0, 0], "dropped_unpaired": 0, "records": [0, 0, 0],
                        "bytes": [0, 0, 0]}
         self.pieces = 0
@@ -1414,7 +1428,7 @@ class FastqStream:
         else:
             self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
         self.ws = [alloc(self.ws_bytes) for _ in range(2)]
-        self.out_cap = n_in * cap_in + 2
+        self.out_cap = fastq_output_bound(n_in * cap_in, mode)
         self.out = [[alloc(self.out_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
         self.words = torch.zeros((n_in, 2, 4), dtype=torch.int64, device=dev)
         self.device_bytes += self.words.numel() * 8
@@ -1562,7 +1576,7 @@ class FastqStream:
             self._table_full = bool(counts["order_piece"]["table_full"])
             self._ended = bool(counts["order_piece"]["state"]["ended"])
         self._reads += counts["records_in"][0] * (2 if self.mode == "pe_split" else 1)
-        if not p["more"] and self.mode == "pe_interleaved":
+        if not p["more"] and self.mode in ("pe_interleaved", "pe_combo_all"):
             self._reads -= counts["dropped_unpaired"]
         self.pieces += 1
         carried = counts["piece"]["carried_bytes"]

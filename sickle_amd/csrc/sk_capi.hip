@@ -699,6 +699,8 @@ int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts,
     } while (0)
     if (!ctx) return SK_EINVAL;
     if (!batch || !out) SK_TRIM_BAD("sk_trim_device_async: batch and out are required");
+    // (packed reads have no name line to keep: the N records of SK_TRIM_PE_COMBO_ALL are the FASTQ text calls')
+    if (mode == SK_TRIM_PE_COMBO_ALL) SK_TRIM_BAD("trim: SK_TRIM_PE_COMBO_ALL is a mode of the FASTQ text calls only");
     if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_TRIM_BAD("trim mode %d is unknown", mode);
     const uint64_t n = batch->n_reads;
     if (batch->tiles) SK_TRIM_BAD("trim: segmented batches are not supported");
@@ -770,7 +772,8 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
     } while (0)
     if (!ctx) return SK_EINVAL;
     if (!params || !in || !out) SK_FQ_BAD("%s: params, in and out are required", who);
-    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_FQ_BAD("trim mode %d is unknown", mode);
+    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED && mode != SK_TRIM_PE_COMBO_ALL)
+        SK_FQ_BAD("trim mode %d is unknown", mode);
     const bool split = mode == SK_TRIM_PE_SPLIT;
     if (split && !in->text[1]) SK_FQ_BAD("fastq: SK_TRIM_PE_SPLIT needs text[1]");
     if (!split && (in->text[1] || in->bytes[1])) SK_FQ_BAD("fastq: text[1] is only for SK_TRIM_PE_SPLIT");
@@ -793,6 +796,14 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
 } // namespace
 
 namespace {
+// Q of an N record of SK_TRIM_PE_COMBO_ALL: the quality type's lowest quality byte (reference src/sickle.h:85-91).  (The
+// parameter checks of the scan have passed by the time this is called, so the type is known.)
+int fastq_fail_qual(const sk_params *params)
+{
+    const int32_t *k = sk_quality_constants(params->qualtype);
+    return k ? k[1] : 0;
+}
+
 // the device words of the chained and the piece calls
 int fastq_check_words(sk_ctx *ctx, const sk_fastq_lengths *lengths, const sk_fastq_piece *piece, int mode)
 {
@@ -860,8 +871,8 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
                                       stream, &packed, &cuts, &n_reads_dev));
     rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, out, workspace, d_err,
-                                     ctx->cu_count, stream));
+    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, fastq_fail_qual(params), out,
+                                     workspace, d_err, ctx->cu_count, stream));
     return SK_OK;
 }
 } // namespace
@@ -1177,8 +1188,8 @@ int sk_trim_fastq_ordered_piece_device_async(sk_ctx *ctx, const sk_params *param
                                                   d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev));
     rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_order_piece_emit(in, mode, params->trunc_n, counted, order, state_in, state_out, out, workspace,
-                                                 d_err, ctx->cu_count, stream));
+    SK_HIP(ctx, sk_launch_fastq_order_piece_emit(in, mode, params->trunc_n, counted, order, state_in, state_out,
+                                                 fastq_fail_qual(params), out, workspace, d_err, ctx->cu_count, stream));
     return SK_OK;
 }
 

@@ -167,7 +167,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 #define SK_FQ_H_FIT 13         // [3] produced, no error, within its capacities: the emission writes it
 #define SK_FQ_H_PRODUCED 16    // [3] out[o].text != NULL for an output of the mode
 #define SK_FQ_H_RANGE 19       // the stream's range-error word as the emission saw it
-#define SK_FQ_H_MODE 20        // the call's mode
+#define SK_FQ_H_MODE 20        // the call's framing mode (SK_TRIM_PE_INTERLEAVED for SK_TRIM_PE_COMBO_ALL)
 // Piece calls (sk_trim_fastq_piece_device_async with piece != NULL) use words 21..29, which are otherwise the ordered
 // calls' (sk_fastq_order.h); an ordered piece keeps these here and its order words in an extension block (below).
 #define SK_FQP_H_START 21      // [2] s_i: the window's first byte, offset in text[i]
@@ -210,6 +210,8 @@ static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * 
 // piece: NULL = the whole text; else (sk_trim_fastq_piece_device_async) text i starts at *piece->start_dev[i], with
 // piece->more only whole records (pairs) are taken, and errword is the stream's range-error word for the frame scan to
 // capture.  The emission takes the piece from the header.
+// mode: the call's; SK_TRIM_PE_COMBO_ALL frames, pairs and orders as SK_TRIM_PE_INTERLEAVED and differs in the emission
+// alone, which takes fail_qual, the Q of its N records (sk_fastq_record.h).
 // counted: the packed batch is for sk_scan_counted_device_async with *n_reads_dev (the header's SK_FQ_H_NREAL) -- packed->n_reads
 // stays the bound -- and the per-read steps of the pack and the emission stop at that word too; 0: everything walks the bound.
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
@@ -224,8 +226,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
                                                                                   const uint64_t **n_reads_dev);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  int counted, const sk_fastq_order *order,
-                                                                                 int piece, const sk_fastq_output *out,
-                                                                                 void *workspace,
+                                                                                 int piece, int fail_qual,
+                                                                                 const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);
 // Ordered pieces (sk_trim_fastq_ordered_piece_device_async): the header with the PIECE's words 21.. (SK_FQP_H_*), then an
@@ -239,8 +241,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_orde
     int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_emit(
     const sk_fastq_input *in, int mode, int trunc_n, int counted, const sk_fastq_order *order, const void *state_in,
-    void *state_out, const sk_fastq_output *out, void *workspace, const unsigned long long *errword, int cu_count,
-    hipStream_t stream);
+    void *state_out, int fail_qual, const sk_fastq_output *out, void *workspace, const unsigned long long *errword,
+    int cu_count, hipStream_t stream);
 // BGZF on the device (sk_bgzf.hip).  The caller's workspace (16-byte sections, sizes in bytes, NB = ceil(text bytes /
 // SK_BGZF_BLOCK) blocks, G = min(NB, SK_BGZF_GRID) workgroups of the block kernel):
 //   header    SK_BGZF_HDR_WORDS words

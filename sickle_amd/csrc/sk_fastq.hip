@@ -14,6 +14,9 @@
 //   (the scan: sk_scan_device_async on the packed batch, launched by sk_capi.hip)
 //   emit    9 count / 10 scan / 11 place  the pair rule over the cuts: output offset and read of every kept record
 //           12 gather the records' bytes: name line, seq[five:three], '\n', '+' line, qual[five:three], '\n'
+// SK_TRIM_PE_COMBO_ALL (sickle's -M) is SK_TRIM_PE_INTERLEAVED everywhere but in the emission: fq_route sends every read of
+// the call to out[0], a read that is not kept as an N record (sk_fastq_record.h), and step 12 runs as
+// sk_fq_gather_combo_kernel, the same gather instantiated with the N record's piece table.
 // Piece calls (sk_trim_fastq_piece_device_async): the three frame kernels start the text at a device word (fq_start), the
 // frame scan takes whole records (pairs) only when more text follows, and the emission's scan publishes what was consumed
 // and the ok word for the carry kernel of sk_fastq_piece.hip; everything else runs as it does for a whole text.
@@ -24,6 +27,7 @@
 
 #include "sk_device.h"
 #include "sk_fastq_order.h"
+#include "sk_fastq_record.h"
 
 namespace {
 
@@ -53,7 +57,9 @@ struct fq_args {
     const uint64_t *bytes_dev[2], *valid_dev[2];
     uint64_t n_chunks[2];
     uint64_t slots[2];
-    int32_t mode;
+    int32_t mode;      // the framing mode: SK_TRIM_PE_COMBO_ALL frames as SK_TRIM_PE_INTERLEAVED, with combo_all set
+    int32_t combo_all; // the routing of SK_TRIM_PE_COMBO_ALL: every read below NREAL to out[0], the not kept ones as N records
+    uint32_t fail_qual; // Q of an N record
     int32_t trunc_n;
     int32_t counted; // the per-read steps stop at SK_FQ_H_NREAL (fq_block_empty) and the scan takes its read count from it
     uint64_t n_pack, n_blocks;
@@ -483,28 +489,52 @@ struct fq_emit_read {
     uint64_t bytes;
 };
 
+// Destination and bytes of the FQ_PER_THREAD records of a lane from their cuts.  is_read: the rank holds a read of the call
+// (below NREAL, below the cuts, no verdict); only such a one is ever emitted, and its cut is {-1, -1} otherwise.  The pair
+// rule cannot tell "not kept" from "no read" and need not.  SK_TRIM_PE_COMBO_ALL must: the first is an N record in out[0],
+// the second nothing.  The flag is uniform and is looked at once, outside the loops, so that the other modes run the loop
+// they always ran.  record(j): the fq_rec of the lane's j-th read.
+template <class F>
+__device__ __forceinline__ void fq_route(const fq_args &a, const bool (&is_read)[FQ_PER_THREAD], const sk_cut_dev (&c)[FQ_PER_THREAD],
+                                         F record, fq_emit_read (&rd)[FQ_PER_THREAD])
+{
+    if (a.combo_all) {
+#pragma unroll
+        for (int j = 0; j < FQ_PER_THREAD; ++j) {
+            rd[j].dest = is_read[j] ? 0 : -1;
+            rd[j].bytes = 0;
+            if (is_read[j]) {
+                const fq_rec x = record(j);
+                rd[j].bytes = fqr_bytes({x.s0, x.e0, x.e1, x.e2, x.e3}, c[j].five, c[j].three);
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < FQ_PER_THREAD; ++j) {
+        rd[j].dest = fq_dest(a.mode, fqr_kept(c[j].three), fqr_kept(c[j ^ 1].three), j & 1);
+        rd[j].bytes = 0;
+        if (rd[j].dest >= 0) {
+            const fq_rec x = record(j);
+            rd[j].bytes = fqr_kept_bytes({x.s0, x.e0, x.e1, x.e2, x.e3}, c[j].five, c[j].three);
+        }
+    }
+}
+
 // the FQ_PER_THREAD reads of this lane (first even): destination and bytes of the emitted record
 __device__ __forceinline__ void fq_emit_load(const fq_args &a, uint64_t first, uint64_t n_real, bool bad,
                                              fq_emit_read (&rd)[FQ_PER_THREAD])
 {
-    bool kept[FQ_PER_THREAD];
+    bool is_read[FQ_PER_THREAD];
     sk_cut_dev c[FQ_PER_THREAD];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j) {
         const uint64_t r = first + j;
         c[j] = {-1, -1};
-        if (!bad && r < n_real) c[j] = a.cuts[r];
-        kept[j] = c[j].three >= 0; // src/trim_single.cpp:368, src/trim_paired.cpp:500,502
+        is_read[j] = !bad && r < n_real;
+        if (is_read[j]) c[j] = a.cuts[r];
     }
-#pragma unroll
-    for (int j = 0; j < FQ_PER_THREAD; ++j) {
-        rd[j].dest = fq_dest(a.mode, kept[j], kept[j ^ 1], j & 1);
-        rd[j].bytes = 0;
-        if (rd[j].dest >= 0) {
-            const fq_rec x = fq_record(a, first + j);
-            rd[j].bytes = (x.e0 - x.s0 + 1) + (x.e2 - x.e1) + 2 * (uint64_t)(c[j].three - c[j].five + 1);
-        }
-    }
+    fq_route(a, is_read, c, [&](int j) { return fq_record(a, first + j); }, rd);
 }
 
 __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_count_kernel(fq_args a)
@@ -676,14 +706,23 @@ __device__ __forceinline__ void fq_store_granule(uint8_t *dst, uint64_t g, fq_u1
     }
 }
 
-// one piece of a record: bytes [0, len) at src, or a '\n' (src == nullptr, len 1)
+// one piece of a record: bytes [0, len) at src, or (src == nullptr) the low len bytes of imm, for which nothing is loaded
 struct fq_piece {
     const uint8_t *src;
-    uint64_t len;
+    uint64_t len, imm;
 };
 
-// bytes [rel, rel + n) of a record made of np pieces to bytes [d, d + n) of acc
+// the table of sk_fastq_record.h over `text`
 template <int NP>
+__device__ __forceinline__ void fq_pieces_at(const uint8_t *text, const fqr_piece (&in)[NP], fq_piece (&pc)[NP])
+{
+#pragma unroll
+    for (int j = 0; j < NP; ++j) pc[j] = {in[j].at != FQR_IMM ? text + in[j].at : nullptr, in[j].len, in[j].imm};
+}
+
+// bytes [rel, rel + n) of a record made of NP pieces to bytes [d, d + n) of acc.  WIDE: an immediate may have more than one
+// byte (the N record's); else every immediate is one byte, a '\n'.
+template <int NP, bool WIDE>
 __device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, int d, int n, fq_u128 &acc)
 {
     uint64_t ps = 0;
@@ -694,8 +733,10 @@ __device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, 
             const int t = (int)min((uint64_t)n, pe - rel);
             if (pc[j].src)
                 fq_place(acc, fq_to_u128(fq_load_window(pc[j].src + (rel - ps), t)), d, t);
+            else if (WIDE)
+                fq_place(acc, (fq_u128)(pc[j].imm >> (8 * (rel - ps))), d, t);
             else
-                fq_place(acc, (fq_u128)'\n', d, 1);
+                fq_place(acc, (fq_u128)pc[j].imm, d, 1);
             rel += t;
             d += t;
             n -= t;
@@ -713,26 +754,31 @@ struct fq_job {
     int kind;
 };
 
-// bytes [rel, rel + n) of record k of the job to bytes [d, d + n) of acc
+// bytes [rel, rel + n) of record k of the job to bytes [d, d + n) of acc.  COMBO: the emission of SK_TRIM_PE_COMBO_ALL, whose
+// table also lists reads that are not kept (their N records); without it every listed read is kept and the table of
+// fqr_pieces has constant kinds, lengths and immediates where it always had them.
+template <bool COMBO>
 __device__ __forceinline__ void fq_record_bytes(const fq_args &a, const fq_job &j, uint64_t k, uint64_t rel, int d, int n,
                                                 fq_u128 &acc)
 {
     if (j.kind < 2) {
         const fq_rec x = fq_record(a, k);
-        const fq_piece pc[1] = {{x.text + (j.kind == 0 ? x.e2 : x.e0) + 1, x.e3 - x.e2 - 1}};
-        fq_fill<1>(pc, rel, d, n, acc);
+        const fq_piece pc[1] = {{x.text + (j.kind == 0 ? x.e2 : x.e0) + 1, x.e3 - x.e2 - 1, 0}};
+        fq_fill<1, false>(pc, rel, d, n, acc);
         return;
     }
     const uint64_t read = j.off[k * 2 + 1];
     const fq_rec x = fq_record(a, read);
     const sk_cut_dev c = a.cuts[read];
-    const uint64_t m = (uint64_t)(c.three - c.five);
-    const fq_piece pc[6] = {{x.text + x.s0, x.e0 - x.s0 + 1}, {x.text + x.e0 + 1 + c.five, m}, {nullptr, 1},
-                            {x.text + x.e1 + 1, x.e2 - x.e1}, {x.text + x.e2 + 1 + c.five, m}, {nullptr, 1}};
-    fq_fill<6>(pc, rel, d, n, acc);
+    fqr_piece rule[6];
+    fq_piece pc[6];
+    fqr_pieces({x.s0, x.e0, x.e1, x.e2, x.e3}, c.five, c.three, COMBO, a.fail_qual, rule);
+    fq_pieces_at<6>(x.text, rule, pc);
+    fq_fill<6, COMBO>(pc, rel, d, n, acc);
 }
 
-__global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int emit)
+template <bool COMBO>
+__device__ __forceinline__ void fq_gather(const fq_args &a, int emit)
 {
     __shared__ uint64_t s_off[FQ_WIN + 1];
     __shared__ uint64_t s_cur;
@@ -810,7 +856,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int
                         continue;
                     }
                     const uint64_t pe = min(e, end);
-                    fq_record_bytes(a, j, k, pos - b, (int)(pos - g), (int)(pe - pos), acc);
+                    fq_record_bytes<COMBO>(a, j, k, pos - b, (int)(pos - g), (int)(pe - pos), acc);
                     pos = pe;
                 }
                 fq_store_granule(j.dst, g, acc, (int)(end - g));
@@ -822,6 +868,19 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int
         }
         __syncthreads(); // s_cur / s_off are reused by the next job
     }
+}
+
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_kernel(fq_args a, int emit) { fq_gather<false>(a, emit); }
+
+// the emission's gather of SK_TRIM_PE_COMBO_ALL: a kernel of its own, so that the N record's variable immediate costs the
+// other modes' gather no register
+__global__ void __launch_bounds__(FQ_THREADS) sk_fq_gather_combo_kernel(fq_args a) { fq_gather<true>(a, 1); }
+
+void fq_launch_emit_gather(const fq_args &a, int cu_count, hipStream_t stream)
+{
+    const dim3 grid((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), threads(FQ_THREADS);
+    if (a.combo_all) hipLaunchKernelGGL(sk_fq_gather_combo_kernel, grid, threads, 0, stream, a);
+    else hipLaunchKernelGGL(sk_fq_gather_kernel, grid, threads, 0, stream, a, 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -968,23 +1027,15 @@ __device__ __forceinline__ void fq_order_reads(const fq_args &a, const fq_order 
 __device__ __forceinline__ void fq_order_emit_load(const fq_args &a, const uint64_t (&reads)[FQ_PER_THREAD], bool bad,
                                                    uint64_t n_cuts, fq_emit_read (&rd)[FQ_PER_THREAD])
 {
-    bool kept[FQ_PER_THREAD];
+    bool is_read[FQ_PER_THREAD];
     sk_cut_dev c[FQ_PER_THREAD];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j) {
         c[j] = {-1, -1};
-        if (!bad && reads[j] < n_cuts) c[j] = a.cuts[reads[j]];
-        kept[j] = c[j].three >= 0;
+        is_read[j] = !bad && reads[j] < n_cuts; // (a rank at or beyond NREAL has reads[j] = ~0)
+        if (is_read[j]) c[j] = a.cuts[reads[j]];
     }
-#pragma unroll
-    for (int j = 0; j < FQ_PER_THREAD; ++j) {
-        rd[j].dest = fq_dest(a.mode, kept[j], kept[j ^ 1], j & 1);
-        rd[j].bytes = 0;
-        if (rd[j].dest >= 0) {
-            const fq_rec x = fq_record(a, reads[j]);
-            rd[j].bytes = (x.e0 - x.s0 + 1) + (x.e2 - x.e1) + 2 * (uint64_t)(c[j].three - c[j].five + 1);
-        }
-    }
+    fq_route(a, is_read, c, [&](int j) { return fq_record(a, reads[j]); }, rd);
 }
 
 // nothing is trimmed after a format error, a line gzgets would split or a table that was too small
@@ -1272,10 +1323,14 @@ uint64_t fq_chunks_of(const uint8_t *text, uint64_t bytes)
 }
 
 // shift: bytes between the header and the sections (an ordered call's batch table lies there)
+// mode: the call's; SK_TRIM_PE_COMBO_ALL becomes the framing mode SK_TRIM_PE_INTERLEAVED with a.combo_all, so that every
+// kernel that frames, pairs or orders by a.mode takes it as that.  fail_qual: Q of its N records (emission only).
 void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted,
                   const sk_fastq_output *out, void *workspace, const unsigned long long *errword, fq_args &a,
-                  uint64_t shift = 0)
+                  uint64_t shift = 0, int fail_qual = 0)
 {
+    const bool combo_all = mode == SK_TRIM_PE_COMBO_ALL;
+    if (combo_all) mode = SK_TRIM_PE_INTERLEAVED;
     sk_fq_layout L;
     sk_fq_layout_of(in->bytes[0] + (mode == SK_TRIM_PE_SPLIT ? in->bytes[1] : 0), trunc_n, &L);
     uint8_t *ws = static_cast<uint8_t *>(workspace) + shift;
@@ -1289,6 +1344,8 @@ void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int
         a.slots[i] = i < n_in ? sk_fq_slots(a.bytes[i]) : 0;
     }
     a.mode = mode;
+    a.combo_all = combo_all ? 1 : 0;
+    a.fail_qual = (uint32_t)fail_qual & 0xffu;
     a.trunc_n = trunc_n ? 1 : 0;
     a.counted = counted ? 1 : 0;
     a.n_pack = sk_fq_pack_reads(a.bytes[0], a.bytes[1], mode);
@@ -1307,7 +1364,7 @@ void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int
     a.start_dev[0] = a.start_dev[1] = nullptr;
     a.piece = 0;
     for (int o = 0; o < 3; ++o) {
-        const bool used = o == 0 || (mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2);
+        const bool used = o == 0 || (!combo_all && ((mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2)));
         a.out[o] = used && out ? fq_out{out[o].text, out[o].capacity, out[o].record_index, out[o].record_capacity} : fq_out{};
     }
 }
@@ -1340,7 +1397,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
     fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, piece ? errword : nullptr, a,
                  order ? sk_fq_order_shift(order->batch_capacity) : 0);
     if (piece) {
-        for (int i = 0; i < (mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
+        for (int i = 0; i < (a.mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
         a.piece = piece->more ? 2 : 1;
     }
     const uint64_t nc = a.n_chunks[0] + a.n_chunks[1];
@@ -1371,14 +1428,15 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  int counted, const sk_fastq_order *order,
-                                                                                 int piece, const sk_fastq_output *out,
-                                                                                 void *workspace,
+                                                                                 int piece, int fail_qual,
+                                                                                 const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream)
 {
     fq_args a;
     // no emission kernel looks at a text's length: lines and records come from the descriptors and the header
-    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0);
+    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, order ? sk_fq_order_shift(order->batch_capacity) : 0,
+                 fail_qual);
     a.piece = piece ? 1 : 0; // the emission takes `more` and the window from the header
     const dim3 blocks((unsigned)a.n_blocks), threads(FQ_THREADS);
     if (order) {
@@ -1391,7 +1449,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
         hipLaunchKernelGGL(sk_fq_emit_scan_kernel, dim3(1), threads, 0, stream, a);
         if (a.n_blocks) hipLaunchKernelGGL(sk_fq_emit_place_kernel, blocks, threads, 0, stream, a);
     }
-    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
+    fq_launch_emit_gather(a, cu_count, stream);
     return hipGetLastError();
 }
 
@@ -1414,7 +1472,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_orde
 {
     fq_args a;
     fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity));
-    for (int i = 0; i < (mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
+    for (int i = 0; i < (a.mode == SK_TRIM_PE_SPLIT ? 2 : 1); ++i) a.start_dev[i] = piece->start_dev[i];
     a.piece = piece->more ? 2 : 1;
     fq_order o;
     fq_opiece p;
@@ -1442,11 +1500,12 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_orde
 
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_emit(
     const sk_fastq_input *in, int mode, int trunc_n, int counted, const sk_fastq_order *order, const void *state_in,
-    void *state_out, const sk_fastq_output *out, void *workspace, const unsigned long long *errword, int cu_count,
-    hipStream_t stream)
+    void *state_out, int fail_qual, const sk_fastq_output *out, void *workspace, const unsigned long long *errword,
+    int cu_count, hipStream_t stream)
 {
     fq_args a;
-    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity));
+    fq_make_args(in, nullptr, mode, trunc_n, counted, out, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity),
+                 fail_qual);
     a.piece = 1;
     fq_order o;
     fq_opiece p;
@@ -1455,6 +1514,6 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_orde
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_piece_emit_count_kernel, blocks, threads, 0, stream, a, o, p);
     hipLaunchKernelGGL(sk_fq_order_piece_emit_scan_kernel, dim3(1), threads, 0, stream, a, o, p);
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_order_piece_emit_place_kernel, blocks, threads, 0, stream, a, o, p);
-    hipLaunchKernelGGL(sk_fq_gather_kernel, dim3((unsigned)cu_count * SK_TRIM_GATHER_WG_PER_CU), dim3(FQ_THREADS), 0, stream, a, 1);
+    fq_launch_emit_gather(a, cu_count, stream);
     return hipGetLastError();
 }
