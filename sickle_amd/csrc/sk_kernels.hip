@@ -51,6 +51,11 @@
 #endif
 #define SK_STAGE_MIN 5  /* register-staged kernels exist for tiles of 5..20 KiB: row strides 72..320 */
 #define SK_STAGE_MAX 20
+// cache policy of the staged uniform kernels' cut stores (the aux operand of the buffer store builtin): 16 = sc1,
+// write-through -- the line does not stay dirty in the XCD's L2 (tools/probes/store_forms.hip)
+#ifndef SK_CUT_STORE_AUX
+#define SK_CUT_STORE_AUX 16
+#endif
 
 // MFMA = true (uniform-length batches; w <= 65, i.e. every uniform length the tiled kernel takes):
 // the window sums are taken off the vector ALU.  A box filter is a banded 0/1 matrix, so for 32 windows x 32 reads
@@ -71,6 +76,7 @@
 //
 // ABLATE (diagnostic launches of tools/ablate.py only; the product always runs 0):
 //   1 = DMA + cut store only (no scan), 2 = scan only (tile loaded once, then reused)
+//   staged kernel only: 3 = the whole kernel with the plain cut stores of every other family (A/B of the store form)
 //
 // SEG = segmented batches (mixed lengths, sorted by length on the host): every tile has its own
 // descriptor -- byte offset, row stride, read length, row count -- and is uniform inside, so it
@@ -244,6 +250,9 @@ sk_scan_tile_body(const uint8_t *__restrict__ qual, const uint8_t *__restrict__ 
             }
         }
     };
+    // WRITE_THROUGH (uniform staged batches: cuts in read order, no scatter): the cut pairs leave by write-through
+    // stores, see the store at the end of the turn.  ABLATE 3 keeps the plain store of every other family for A/B runs.
+    constexpr bool WRITE_THROUGH = STAGE != 0 && SEG == 0 && ABLATE != 3;
     if (!TABLE) set_length((int)a.read_len);
 
     const uint64_t batch_end = RAG ? rag_batch_end(offsets, lengths, a) : 0;
@@ -1148,7 +1157,17 @@ sk_scan_tile_body(const uint8_t *__restrict__ qual, const uint8_t *__restrict__ 
         // (staged kernels: no refill above, the next tile's pieces went out before the scan.  Tried and dropped: the cuts
         // stored a turn late, so that the next turn's wait for its pieces does not sit out this store -- 1-7 % slower)
         if (STAGE && scatter) index_settle(oidx);
-        if (active && (!WIDE || lane < (int)ROWS)) out[scatter ? (uint64_t)oidx : r] = sk_cut_dev{five, three};
+        if constexpr (WRITE_THROUGH) {
+            // uniform staged batches: the cuts of a tile are 8 * rows contiguous bytes in read order.  One 8-byte store per
+            // lane as everywhere else (any 8-byte aligned `out`), but write-through: a vector store through a descriptor of
+            // exactly this tile's rows (wave-uniform: scalar registers), the policy in the builtin's aux operand, so the
+            // compiler counts the store in its waits like any other.
+            typedef int sk_v2i __attribute__((ext_vector_type(2)));
+            const __amdgpu_buffer_rsrc_t cuts = __builtin_amdgcn_make_buffer_rsrc(out + (t << 6), 0, (int)(cur.rows * 8u), 0x00020000);
+            if (active) __builtin_amdgcn_raw_buffer_store_b64(sk_v2i{five, three}, cuts, lane * 8, 0, SK_CUT_STORE_AUX);
+        } else if (active && (!WIDE || lane < (int)ROWS)) {
+            out[scatter ? (uint64_t)oidx : r] = sk_cut_dev{five, three};
+        }
         // this trip's LDS reads are complete (their results were consumed) before the next
         // trip may overwrite the buffer they came from
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1557,6 +1576,7 @@ extern "C" hipError_t sk_launch_tile_ablate(int mode, const uint8_t *qual, sk_cu
     case 200: return SK_GO((sk_scan_tile_staged_kernel<10, 0>), 1);
     case 201: return SK_GO((sk_scan_tile_staged_kernel<10, 1>), 1);
     case 202: return SK_GO((sk_scan_tile_staged_kernel<10, 2>), 1);
+    case 203: return SK_GO((sk_scan_tile_staged_kernel<10, 3>), 1);
     default: return hipErrorInvalidValue;
     }
 #undef SK_GO

@@ -24,7 +24,8 @@ s = torch.cuda.Stream(dev)
 torch.cuda.synchronize()
 NAMES = {0: "2buf mfma full", 1: "2buf dma-only", 2: "2buf mfma scan-only", 10: "2buf valu full", 12: "2buf valu scan-only",
          100: "1buf mfma full", 101: "1buf dma-only", 102: "1buf mfma scan-only", 110: "1buf valu full",
-         200: "staged mfma full", 201: "staged load-only", 202: "staged scan-only"}
+         200: "staged mfma full", 201: "staged load-only", 202: "staged scan-only",
+         203: "staged, plain stores"}
 CONFIGS = [(8, (0, 1, 2, 10, 12)), (16, (100, 101, 102, 110)), (12, (100,)), (8, (100,)), (6, (0,))]
 if os.environ.get("SK_ABLATE_SHORT"):
     CONFIGS = [(16, (100, 101, 102)), (8, (0, 1))]
@@ -45,6 +46,40 @@ if os.environ.get("SK_ABLATE_STAGED"):
     print("ragged batch identical:", bool(torch.equal(ref, out)), flush=True)
 if os.environ.get("SK_ABLATE_AB"):
     CONFIGS = [(16, (100,)), (8, (0,)), (16, (100,)), (8, (0,)), (16, (100,)), (8, (0,)), (16, (101,)), (8, (1,)), (16, (102,)), (8, (2,))]
+if os.environ.get("SK_ABLATE_STORES"):
+    # the headline kernel (200: write-through cut stores) against itself with the plain stores it had before (203):
+    # SK_ABLATE_STORES rounds (at least five) of each, alternating, bench style -- 150 launches to settle, then 300
+    # queued back to back, one event pair each.  The last lines compare every round's mean, and the difference of the
+    # overall means against 203's own spread across its rounds (what two runs of identical code differ by).
+    rounds = max(5, int(os.environ["SK_ABLATE_STORES"]))
+    ref = torch.empty_like(out)
+    for mode, dst in ((203, ref), (200, out)):
+        assert lib.sk_launch_tile_ablate(mode, q.data_ptr(), dst.data_ptr(), err.data_ptr(), C.byref(a), 256, 1, 12, s.cuda_stream) == 0
+    s.synchronize()
+    print("cuts identical with both store forms:", bool(torch.equal(ref, out)), "error word", int(err.item()), flush=True)
+    means = {200: [], 203: []}
+    for rnd in range(rounds):
+        for mode in (203, 200):
+            for _ in range(150):
+                assert lib.sk_launch_tile_ablate(mode, q.data_ptr(), out.data_ptr(), err.data_ptr(), C.byref(a), 256, 1, 12, s.cuda_stream) == 0
+            s.synchronize()
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(300)]
+            for e0, e1 in evs:
+                e0.record(s)
+                lib.sk_launch_tile_ablate(mode, q.data_ptr(), out.data_ptr(), err.data_ptr(), C.byref(a), 256, 1, 12, s.cuda_stream)
+                e1.record(s)
+            s.synchronize()
+            ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
+            wall = evs[0][0].elapsed_time(evs[-1][1]) / len(evs)
+            means[mode].append(ms)
+            print("round %d mode %d (%-20s): events %.4f ms  first-to-last/launch %.4f ms" % (rnd, mode, NAMES[mode], ms, wall), flush=True)
+    avg = {m: sum(v) / len(v) for m, v in means.items()}
+    spread = max(means[203]) - min(means[203])
+    for m in (203, 200):
+        print("mode %d: mean %.4f ms [%.4f .. %.4f]" % (m, avg[m], min(means[m]), max(means[m])))
+    print("200 against 203: every round below every round of 203: %s; difference of the means %.4f ms against 203's spread %.4f ms: %s" %
+          (max(means[200]) < min(means[203]), avg[203] - avg[200], spread, "a gain" if avg[203] - avg[200] > spread else "inside the noise"))
+    sys.exit(0)
 B2B = bool(os.environ.get("SK_ABLATE_B2B"))  # bench style: 50 launches queued back to back, one event pair each
 for per_cu, modes in CONFIGS:
     for mode in modes:
