@@ -1035,6 +1035,90 @@ int sk_trim_fastq_ordered_piece_device_finish(sk_ctx *ctx, void *workspace, void
                                               sk_fastq_order_counts *order_counts, sk_fastq_piece_counts *piece_counts,
                                               sk_fastq_order_piece_counts *order_piece_counts);
 
+/*
+ * The trim report: what a run cut, on the device, over the workspace of a text call that has been enqueued on the same
+ * stream.  It gives sickle's closing summary (the kept / discarded lines), base counts and, optionally, length and
+ * per-position quality histograms.  It is exact integer arithmetic and accumulates in device memory, so a stream of pieces
+ * yields one report for the file with no host wait in between.  This comment is the normative text; the rule as code is
+ * sickle_amd/csrc/sk_fastq_report.h.  The host CLI does not use this call: it counts on the host, as it always did.
+ *
+ * The rule.  Read r of the call's packed batch has input length len = offsets[r + 1] - offsets[r] (its quality line) and
+ * the cut {five, three}; it is kept iff three >= 0, and then its output length is three - five.  Only the reads the call
+ * trimmed are reads (an interleaved text's odd last record, dropped_unpaired, and a piece's carry are in no count).  In
+ * the pair modes reads 2k and 2k + 1 are pair k.
+ *   calls, calls_failed   calls that added / that did not (below)
+ *   reads, kept, discarded
+ *   pairs[kept1 | kept2 << 1]   pairs by which mates are kept; all zero for SK_TRIM_SE.  The reference's numbers:
+ *       kept_p = 2 pairs[3]; kept_s1 = discard_s2 = pairs[1]; kept_s2 = discard_s1 = pairs[2]; discard_p = 2 pairs[0];
+ *       the N records of SK_TRIM_PE_COMBO_ALL are 2 pairs[0] + pairs[1] + pairs[2]
+ *   bases_in, bases_out   sum of len over all reads; of three - five over kept reads
+ *   bases_cut5, bases_cut3   of kept reads: five and len - three;  bases_discarded: len of the reads not kept
+ *   reads_cut5, reads_cut3   kept reads with five != 0, with three != len
+ *   max_len_in, max_len_out   the longest input; the longest output of a kept read
+ * Histograms (sk_fastq_report_hists, may be NULL, as may each array in it; device arrays of uint64_t that the caller owns
+ * and sizes): len_in[len_bins] and len_out[len_bins] count reads in bin min(length, len_bins - 1), len_out kept reads
+ * only by output length.  qsum_in / qcnt_in [pos_bins]: the sum of the RAW quality bytes and their number at position
+ * min(p, pos_bins - 1), p counted from the read's first base, over all reads; qsum_out / qcnt_out: the same over the
+ * three - five output bytes of kept reads, p counted from five.  Mean quality at a position is sum / cnt less
+ * sk_quality_constants(qualtype)[0]; that is left to the caller.  len_bins <= SK_FQ_REPORT_MAX_LEN_BINS and pos_bins <=
+ * SK_FQ_REPORT_MAX_POS_BINS: the tables are summed in LDS, 2 * 4 * 4096 = 32 KiB of 32-bit length counters and 2 * 8 *
+ * 2048 = 32 KiB of 64-bit position words, beside each other within the 64 KiB a workgroup may hold.
+ * Validity.  A call adds iff it has no format verdict and no range verdict, taken from its own workspace: SK_EFORMAT or
+ * SK_ERANGE of its finish (for the piece kinds also a range error inherited from the stream: a void piece adds nothing),
+ * and SK_ELONGLINE / a full batch table of sk_trim_fastq_ordered_device_async, after which nothing was written either.
+ * SK_ESPACE does not matter: a counting call, with every output NULL, reports in full.  A call that adds increments calls;
+ * one that does not increments calls_failed and touches nothing else, neither in the struct nor in the arrays.
+ * The source.  src->workspace is the text call's workspace and src->kind says which call wrote it:
+ *   SK_FQ_REPORT_PLAIN          sk_trim_fastq_device_async, the chained call without an order, the piece call with piece == NULL
+ *   SK_FQ_REPORT_PIECE          sk_trim_fastq_piece_device_async with a piece
+ *   SK_FQ_REPORT_ORDERED        sk_trim_fastq_ordered_device_async, the chained call with an order
+ *   SK_FQ_REPORT_ORDERED_PIECE  sk_trim_fastq_ordered_piece_device_async
+ * text_bytes, trunc_n and (ordered kinds) batch_capacity are what the call's workspace formula was called with: bytes[0] +
+ * bytes[1] of its input, params->trunc_n, order->batch_capacity.  They locate the sections; wrong ones read the wrong words.
+ * When.  The call must be enqueued on the text call's stream, after that call (its emission writes the range verdict the
+ * report goes by) and before the workspace is used again.  It only enqueues kernels: no copy, no allocation, no
+ * synchronisation, no host wait, and nothing is read from the texts.  flags: SK_FQ_REPORT_RESET zeroes *report_dev and the
+ * given arrays first (a kernel of its own); without it the call adds to what they hold.  report_dev is device memory; the
+ * caller copies it back after its own wait.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: ctx, src, src->workspace or report_dev NULL; a workspace that
+ * is not 16-byte aligned, a report or an array that is not 8-byte aligned; an unknown kind; flags other than
+ * SK_FQ_REPORT_RESET; src->reserved != 0; len_bins (pos_bins) of 0 with a length (position) array given, or above its limit.
+ */
+#define SK_FQ_REPORT_RESET 1
+#define SK_FQ_REPORT_MAX_LEN_BINS 4096u
+#define SK_FQ_REPORT_MAX_POS_BINS 2048u
+enum { SK_FQ_REPORT_PLAIN = 0, SK_FQ_REPORT_PIECE = 1, SK_FQ_REPORT_ORDERED = 2, SK_FQ_REPORT_ORDERED_PIECE = 3 };
+
+typedef struct {
+    uint64_t calls, calls_failed;
+    uint64_t reads, kept, discarded;
+    uint64_t pairs[4];
+    uint64_t bases_in, bases_out;
+    uint64_t bases_cut5, bases_cut3;
+    uint64_t bases_discarded;
+    uint64_t reads_cut5, reads_cut3;
+    uint64_t max_len_in, max_len_out;
+} sk_fastq_report; /* device memory, 8-byte aligned, 144 bytes */
+
+typedef struct {
+    const void *workspace;   /* device: the text call's workspace */
+    uint32_t kind;           /* SK_FQ_REPORT_* */
+    int32_t trunc_n;
+    uint64_t text_bytes;
+    uint64_t batch_capacity; /* ordered kinds; ignored by the others */
+    uint64_t reserved;       /* 0 */
+} sk_fastq_report_source;
+
+typedef struct {
+    uint64_t *len_in, *len_out; /* device, 8-byte aligned, or NULL */
+    uint64_t len_bins;
+    uint64_t *qsum_in, *qcnt_in, *qsum_out, *qcnt_out;
+    uint64_t pos_bins;
+} sk_fastq_report_hists;
+
+int sk_trim_fastq_report_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, sk_fastq_report *report_dev,
+                                      const sk_fastq_report_hists *hists, int flags, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

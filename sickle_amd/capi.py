@@ -50,7 +50,12 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async", "sk_gzip_inflate_piece_workspace_bytes",
            "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish",
            "sk_trim_fastq_ordered_piece_workspace_bytes", "sk_trim_fastq_ordered_piece_device_async",
-           "sk_trim_fastq_ordered_piece_device_finish")
+           "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async")
+# sk_trim_fastq_report_device_async (include/sickle_amd.h)
+SK_FQ_REPORT_RESET = 1
+SK_FQ_REPORT_MAX_LEN_BINS = 4096
+SK_FQ_REPORT_MAX_POS_BINS = 2048
+REPORT_KINDS = {"plain": 0, "piece": 1, "ordered": 2, "ordered_piece": 3}
 SK_GZIP_PIECE_STATE_BYTES = 128 + 32768
 SK_BGZF_EOF = 1
 SK_BGZF_SEARCH = 2
@@ -132,6 +137,92 @@ class FastqCounts(C.Structure):
                 "bytes": list(self.bytes), "format_error": int(self.format_error),
                 "format_input": int(self.format_input), "format_record": int(self.format_record),
                 "range": (int(self.range.read), int(self.range.pos), int(self.range.ch))}
+
+
+class FastqReport(C.Structure):
+    """sk_fastq_report: every member is a uint64_t"""
+    _fields_ = [("calls", C.c_uint64), ("calls_failed", C.c_uint64), ("reads", C.c_uint64), ("kept", C.c_uint64),
+                ("discarded", C.c_uint64), ("pairs", C.c_uint64 * 4), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64),
+                ("bases_cut5", C.c_uint64), ("bases_cut3", C.c_uint64), ("bases_discarded", C.c_uint64),
+                ("reads_cut5", C.c_uint64), ("reads_cut3", C.c_uint64), ("max_len_in", C.c_uint64),
+                ("max_len_out", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: (list(getattr(self, name)) if name == "pairs" else int(getattr(self, name))) for name, _ in self._fields_}
+
+
+REPORT_WORDS = C.sizeof(FastqReport) // 8
+HIST_ARRAYS = ("len_in", "len_out", "qsum_in", "qcnt_in", "qsum_out", "qcnt_out")
+
+
+class FastqReportSource(C.Structure):
+    _fields_ = [("workspace", C.c_void_p), ("kind", C.c_uint32), ("trunc_n", C.c_int32), ("text_bytes", C.c_uint64),
+                ("batch_capacity", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class FastqReportHists(C.Structure):
+    _fields_ = [("len_in", C.c_void_p), ("len_out", C.c_void_p), ("len_bins", C.c_uint64), ("qsum_in", C.c_void_p),
+                ("qcnt_in", C.c_void_p), ("qsum_out", C.c_void_p), ("qcnt_out", C.c_void_p), ("pos_bins", C.c_uint64)]
+
+
+def summary_text(report, mode):
+    """The kept / discarded lines the reference prints at the end of a run (reference src/trim_paired.cpp:468-475,
+    src/trim_single.cpp:347), byte for byte, from a report (a dict as the drivers return it, or a FastqReport).  mode
+    "se": "FastQ records kept: ..\nFastQ records discarded: ..\n\n".  The pair modes: from "\nFastQ paired records
+    kept" through the "single records discarded" line, in the interleaved wording when the input is one text
+    ("pe_interleaved", "pe_combo_all") and with "from PE1 / from PE2" for "pe_split".  The reference's "Total input
+    FastQ records" line is left out: it is not a property of the text."""
+    r = report.as_dict() if isinstance(report, FastqReport) else report
+    if mode == "se":
+        return "FastQ records kept: %d\nFastQ records discarded: %d\n\n" % (r["kept"], r["discarded"])
+    if mode not in TRIM_MODES:
+        raise ValueError("summary_text: unknown mode %r" % (mode,))
+    p = r["pairs"]
+    kept_p, discard_p, s1, s2 = 2 * p[3], 2 * p[0], p[1], p[2]  # kept_s1 = discard_s2 = pairs[1], kept_s2 = discard_s1 = pairs[2]
+    text = "\nFastQ paired records kept: %d (%d pairs)\n" % (kept_p, kept_p // 2)
+    if mode == "pe_split":
+        text += "FastQ single records kept: %d (from PE1: %d, from PE2: %d)\n" % (s1 + s2, s1, s2)
+    else:
+        text += "FastQ single records kept: %d\n" % (s1 + s2)
+    text += "FastQ paired records discarded: %d (%d pairs)\n" % (discard_p, discard_p // 2)
+    if mode == "pe_split":
+        text += "FastQ single records discarded: %d (from PE1: %d, from PE2: %d)\n\n" % (s1 + s2, s2, s1)
+    else:
+        text += "FastQ single records discarded: %d\n\n" % (s1 + s2)
+    return text
+
+
+class _ReportBuffers:
+    """The device words of one report= of a driver: the sk_fastq_report, then the histograms report=dict(len_bins=..,
+    pos_bins=..) asks for (all six arrays of the bins given), in one tensor."""
+
+    def __init__(self, report, dev):
+        import torch
+        opts = report if isinstance(report, dict) else {}
+        unknown = set(opts) - {"len_bins", "pos_bins"}
+        if unknown:
+            raise ValueError("report: unknown keys %r" % sorted(unknown))
+        self.len_bins, self.pos_bins = int(opts.get("len_bins", 0)), int(opts.get("pos_bins", 0))
+        self.buf = torch.empty(REPORT_WORDS + 2 * self.len_bins + 4 * self.pos_bins, dtype=torch.int64, device=dev)
+        self.ptr = self.buf.data_ptr()
+        self.hists = None
+        if self.len_bins or self.pos_bins:
+            at = lambda words: self.ptr + 8 * (REPORT_WORDS + words)
+            L, P = self.len_bins, self.pos_bins
+            self.hists = FastqReportHists(at(0) if L else None, at(L) if L else None, L,
+                                          *[at(2 * L + j * P) if P else None for j in range(4)], P)
+
+    def read(self):
+        """-> the report as a dict: sk_fastq_report's members, and a uint64 array per histogram asked for"""
+        w = self.buf.cpu().numpy().view(np.uint64)
+        rep = FastqReport.from_buffer_copy(w[:REPORT_WORDS].tobytes()).as_dict()
+        at, L, P = REPORT_WORDS, self.len_bins, self.pos_bins
+        for name in HIST_ARRAYS:
+            n = L if name.startswith("len") else P
+            if n:
+                rep[name] = w[at:at + n].copy()
+            at += n
+        return rep
 
 
 class FastqPiece(C.Structure):
@@ -446,6 +537,9 @@ def lib():
         L.sk_gzip_inflate_piece_device_finish.restype = C.c_int
         L.sk_gzip_inflate_piece_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GzipInflateCounts),
                                                           C.POINTER(GzipPieceCounts)]
+        L.sk_trim_fastq_report_device_async.restype = C.c_int
+        L.sk_trim_fastq_report_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.c_void_p,
+                                                        C.POINTER(FastqReportHists), C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -652,6 +746,17 @@ class Context:
         self._check(rc, c.range)
         return c.as_dict()
 
+    def trim_fastq_report_device_async(self, workspace_ptr, text_bytes, trunc_n, report_ptr, kind="plain", batch_capacity=0,
+                                       hists=None, reset=False, stream=None):
+        """sk_trim_fastq_report_device_async on raw device pointers: the report over the workspace of a text call already
+        enqueued on `stream`.  kind: "plain", "piece", "ordered" or "ordered_piece" (or SK_FQ_REPORT_*); text_bytes,
+        trunc_n, batch_capacity: what that call's workspace formula took; report_ptr: a sk_fastq_report in device memory;
+        hists: a FastqReportHists or None.  Only enqueues."""
+        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+        self._check(lib().sk_trim_fastq_report_device_async(self._h, C.byref(src), report_ptr,
+                                                            C.byref(hists) if hists is not None else None,
+                                                            SK_FQ_REPORT_RESET if reset else 0, stream))
+
     def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
                                         mode="se", max_read_len=0, stream=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
@@ -780,7 +885,7 @@ class Context:
                                                       stream))
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
-                          search=False, max_read_len=0, order=None, batch_capacity=None):
+                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -803,23 +908,26 @@ class Context:
         them ends in an EOF member, which readers step over).  .counts["order"] holds the summed order counts.  A piece
         must hold a batch: a batch_len that piece_bytes and room cannot hold, or lines that never use the budget up, end the
         stream with TrimError (SK_ESPACE) that names batch_len.  LongLineError counts its line within the piece.  When the
-        run ends before the text does (an empty batch, a split mismatch) the stream ends there, as the reference does."""
+        run ends before the text does (an empty batch, a split mismatch) the stream ends there, as the reference does.
+        report=True or dict(len_bins=.., pos_bins=..): sk_trim_fastq_report_device_async is enqueued behind every piece's
+        emission, zeroing the report in front of the first piece only; the report of the whole file (trim_fastq's dict)
+        is read back once, after the last piece's finish, into .report (None until then, and after a failure)."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0, order=None, batch_capacity=None):
+                       max_read_len=0, order=None, batch_capacity=None, report=False):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
-                         search=False, max_read_len=0, order=None, batch_capacity=None):
+                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -830,10 +938,10 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity: as in trim_fastq_stream."""
+        batch_capacity, report: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
-        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity)
+        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -866,7 +974,7 @@ class Context:
                 raise
         return call(second)
 
-    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None):
+    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -878,14 +986,18 @@ class Context:
         byte budget batch_len (sk_trim_fastq_ordered_device_async); counts then has the order counts under "order", and
         LongLineError may be raised.  A batch table that was too small shows in the count-only pass, which is then
         repeated once with the larger table; the writing pass runs once, with the table that fitted, so nothing is
-        written twice.  order=None: read order, the -a 1 order."""
+        written twice.  order=None: read order, the -a 1 order.
+        report=True or dict(len_bins=.., pos_bins=..): the trim report of the writing pass (sk_trim_fastq_report_device_async,
+        enqueued behind it) is returned as a third entry, a dict of sk_fastq_report's members and, for the bins given, the
+        histograms as uint64 arrays; summary_text(report, mode) gives the reference's closing lines.  report=False: the
+        call is what it was, to the launch."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
-                                                                                  record_index, o))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None)
+                                                                                  record_index, o, report))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report)
 
-    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order):
+    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -896,14 +1008,20 @@ class Context:
         else:
             ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        rep = _ReportBuffers(report, dev) if report else None
+        # the report goes behind the writing pass's emission and in front of its finish, which is the wait
+        tell = lambda final: final and rep and self.trim_fastq_report_device_async(
+            ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr, kind="plain" if order is None else "ordered",
+            batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream)
         if order is None:
-            run = lambda outs: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                             max_read_len=max_read_len, stream=stream),
-                                self.trim_fastq_device_finish(ws.data_ptr(), stream))[1]
+            run = lambda outs, final=False: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes,
+                                                                          mode=mode, max_read_len=max_read_len, stream=stream),
+                                             tell(final), self.trim_fastq_device_finish(ws.data_ptr(), stream))[2]
         else:
-            run = lambda outs: (self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes,
-                                                                     mode=mode, max_read_len=max_read_len, stream=stream),
-                                self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[1]
+            run = lambda outs, final=False: (self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(),
+                                                                                  ws_bytes, mode=mode, max_read_len=max_read_len,
+                                                                                  stream=stream),
+                                             tell(final), self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[2]
         counts = run([FastqOutput() for _ in range(3)])
         used = TRIM_OUTPUTS[mode]
         bufs, outs = [None] * 3, [FastqOutput() for _ in range(3)]
@@ -913,13 +1031,13 @@ class Context:
             idx = torch.empty(max(R, 1), dtype=torch.int64, device=dev) if record_index else None
             bufs[o] = (t, idx)
             outs[o] = FastqOutput(t.data_ptr(), B, idx.data_ptr() if record_index else None, R)
-        counts = run(outs)
+        counts = run(outs, True)
         res = [None] * 3
         for o in used:
             t, idx = bufs[o]
             R, B = counts["records"][o], counts["bytes"][o]
             res[o] = (t[:B], idx[:R]) if record_index else t[:B]
-        return tuple(res), counts
+        return (tuple(res), counts, rep.read()) if rep else (tuple(res), counts)
 
     # ---- BGZF on the device -------------------------------------------------------------------
     def bgzf_device_async(self, text_ptr, text_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, eof=True,
@@ -954,20 +1072,20 @@ class Context:
                                stream=stream, search=search)
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
-    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False):
+    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
         than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
-        as bgzf's."""
+        as bgzf's.  report: as trim_fastq's, a third entry."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
-            return self._with_batch_table(order, sizes,
-                                          lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o, search))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search)
+            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
+                                                                                     search, report))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report)
 
-    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False):
+    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -992,6 +1110,12 @@ class Context:
         else:
             self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
                                                  max_read_len=max_read_len, stream=stream)
+        rep = _ReportBuffers(report, dev) if report else None
+        if rep:
+            self.trim_fastq_report_device_async(ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr,
+                                                kind="plain" if order is None else "ordered",
+                                                batch_capacity=order.batch_capacity if order is not None else 0,
+                                                hists=rep.hists, reset=True, stream=stream)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1001,7 +1125,8 @@ class Context:
         sizes_out = [None if images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
                      for o in range(3)]
         counts = (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
-        return tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3)), counts
+        res = tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3))
+        return (res, counts, rep.read()) if rep else (res, counts)
 
     # ---- BGZF read on the device --------------------------------------------------------------
     def bgzf_inflate_device_async(self, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, stream=None):
@@ -1167,7 +1292,7 @@ class Context:
         head = bytes(image[:16].cpu().tolist())
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
-    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search):
+    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1207,6 +1332,12 @@ class Context:
         self.trim_fastq_chained_device_async(params, [t.data_ptr() for t in texts], capacities, outs, ws.data_ptr(), ws_bytes,
                                              bytes_dev_ptrs=nbytes, valid_dev_ptrs=valid, mode=mode, order=order,
                                              max_read_len=max_read_len, stream=stream)
+        rep = _ReportBuffers(report, dev) if report else None
+        if rep:
+            self.trim_fastq_report_device_async(ws.data_ptr(), sum(capacities), params.trunc_n, rep.ptr,
+                                                kind="plain" if order is None else "ordered",
+                                                batch_capacity=order.batch_capacity if order is not None else 0,
+                                                hists=rep.hists, reset=True, stream=stream)
         for o in used:
             out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1231,10 +1362,11 @@ class Context:
         sizes_out = [None if out_images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
                      for o in range(3)]
         counts = trim_finish(ws.data_ptr(), stream)
-        return tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3)), counts
+        res = tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3))
+        return (res, counts, rep.read()) if rep else (res, counts)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
-                kind=None):
+                kind=None, report=False):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
         trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
@@ -1250,7 +1382,8 @@ class Context:
         for a batch table that was too small is retried.  Every
         per-read step of the trim is sized by the capacity, so a tight bound is a fast call.  kind: "bgzf" or "gzip"
         names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
-        enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more."""
+        enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more.
+        report: as trim_fastq's, a third entry."""
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -1261,10 +1394,11 @@ class Context:
             if any(k not in ("bgzf", "gzip") for k in kinds):
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
-                                                                                       max_read_len, o, search))
+                                                                                       max_read_len, o, search, report))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
-        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search)
+        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
+                                  report=report)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -1394,7 +1528,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None):
+                 batch_capacity=None, report=False):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1442,6 +1576,8 @@ class FastqStream:
             self.comp = [[alloc(sources[0].group_cap) for _ in range(2)] for _ in range(n_in)]
             self.rws = [[alloc(self.rws_bytes) for _ in range(2)] for _ in range(n_in)]
         self.stream = torch.cuda.current_stream().cuda_stream
+        self.report = None
+        self._rep = _ReportBuffers(report, dev) if report else None  # (its few words are not in device_bytes)
         self._gen = self._run()
 
     def __iter__(self):
@@ -1516,6 +1652,12 @@ class FastqStream:
                                                     self.order, self.states[k & 1].data_ptr(),
                                                     self.states[(k + 1) & 1].data_ptr(), outs, self.ws[slot].data_ptr(),
                                                     self.ws_bytes, **words)
+        if self._rep:  # behind the piece's emission; the report is zeroed in front of the first piece only
+            # (the piece's sections lie where ITS bounds put them, which a short chunk makes less than the workspace's)
+            c.trim_fastq_report_device_async(self.ws[slot].data_ptr(), sum(bounds), self.params.trunc_n, self._rep.ptr,
+                                             kind="piece" if self.order is None else "ordered_piece",
+                                             batch_capacity=self.order.batch_capacity if self.order is not None else 0,
+                                             hists=self._rep.hists, reset=k == 0, stream=self.stream)
         if self.gz:
             for o in self.used:
                 b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
@@ -1606,6 +1748,11 @@ class FastqStream:
         return [max(c + t - u, 0) for c, t, u in zip(carried, last["taken"], consumed)]
 
     def _run(self):
+        yield from self._run_pieces()
+        if self._rep:  # every piece has been finished: the stream has been waited for
+            self.report = self._rep.read()
+
+    def _run_pieces(self):
         self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])
         self._table_full = self._ended = False  # ordered streams: the last finished piece's
         estimate, pending, k = [0, 0], None, 0

@@ -1314,6 +1314,42 @@ int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t
     return SK_OK;
 }
 
+// every check before the first HIP call: bad arguments enqueue nothing and need no device
+int sk_trim_fastq_report_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, sk_fastq_report *report_dev,
+                                      const sk_fastq_report_hists *hists, int flags, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+#define SK_FQR_BAD(...)               \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!src || !src->workspace || !report_dev) SK_FQR_BAD("report: src, src->workspace and report_dev are required");
+    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQR_BAD("report: src->workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(report_dev) & 7) SK_FQR_BAD("report: report_dev must be 8-byte aligned");
+    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQR_BAD("report: source kind %u is unknown", src->kind);
+    if (src->reserved != 0) SK_FQR_BAD("report: src->reserved must be 0");
+    if (flags & ~SK_FQ_REPORT_RESET) SK_FQR_BAD("report: flags %d are unknown", flags);
+    if (hists) {
+        const uintptr_t len = reinterpret_cast<uintptr_t>(hists->len_in) | reinterpret_cast<uintptr_t>(hists->len_out);
+        const uintptr_t pos = reinterpret_cast<uintptr_t>(hists->qsum_in) | reinterpret_cast<uintptr_t>(hists->qcnt_in) |
+                              reinterpret_cast<uintptr_t>(hists->qsum_out) | reinterpret_cast<uintptr_t>(hists->qcnt_out);
+        if ((len | pos) & 7) SK_FQR_BAD("report: the histogram arrays must be 8-byte aligned");
+        if (len && hists->len_bins == 0) SK_FQR_BAD("report: len_bins is 0 with a length array given");
+        if (pos && hists->pos_bins == 0) SK_FQR_BAD("report: pos_bins is 0 with a position array given");
+        if (hists->len_bins > SK_FQ_REPORT_MAX_LEN_BINS)
+            SK_FQR_BAD("report: len_bins %llu is above SK_FQ_REPORT_MAX_LEN_BINS = %u", (unsigned long long)hists->len_bins,
+                       SK_FQ_REPORT_MAX_LEN_BINS);
+        if (hists->pos_bins > SK_FQ_REPORT_MAX_POS_BINS)
+            SK_FQR_BAD("report: pos_bins %llu is above SK_FQ_REPORT_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
+                       SK_FQ_REPORT_MAX_POS_BINS);
+    }
+#undef SK_FQR_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_report(src, report_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
 uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags)
 {
     sk_bgzf_layout L;

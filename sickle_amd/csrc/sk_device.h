@@ -429,6 +429,12 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_carr
                                                                                   const sk_fastq_carry_words *prev_words,
                                                                                   const sk_fastq_carry_words *other_prev_words,
                                                                                   sk_fastq_carry_words *words, hipStream_t stream);
+// the trim report over a text call's workspace (sk_fastq_report.hip); the arguments have passed the checks of
+// sk_trim_fastq_report_device_async
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_report(const sk_fastq_report_source *src,
+                                                                                   sk_fastq_report *report_dev,
+                                                                                   const sk_fastq_report_hists *hists, int flags,
+                                                                                   hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
