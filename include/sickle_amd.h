@@ -1119,6 +1119,69 @@ typedef struct {
 int sk_trim_fastq_report_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, sk_fastq_report *report_dev,
                                       const sk_fastq_report_hists *hists, int flags, void *hip_stream);
 
+/*
+ * The audit: whether a paired run made sense, on the device, over the workspace AND the texts of a text call that has been
+ * enqueued on the same stream.  It compares the names of the two mates of every pair and gives the range of the quality
+ * bytes, the two mistakes (mates that are not mates, the wrong -t) that neither the reference nor a text call notices.
+ * Exact integers, accumulated in device memory like the report.  Nothing acts on the verdict: the caller decides.  This
+ * comment is the normative text; the rule as code is sickle_amd/csrc/sk_fastq_audit.h.  The host CLI does not use it.
+ *
+ * Key of a name line.  The name line is the record's first line without its '\n'; byte 0 is '@' in any call that adds.
+ * The key is bytes [1, e): e is the index of the first byte at or after index 1 that is ' ' (0x20), '\t' (0x09) or '\r'
+ * (0x0d), or the line's length if there is none.  Then, once: if the key has 2 bytes or more, its last but one is '/' and
+ * its last is '1' or '2', the tag is that digit and the key loses those two bytes; otherwise the tag is 0.  An empty key
+ * is a key.  ("@x/1/1" has the key "x/1" and the tag 1; "@x/3" the key "x/3"; "@/1" the empty key and the tag 1.)
+ * Pair k is reads 2k and 2k + 1 of the call's packed batch (SK_TRIM_PE_SPLIT, SK_TRIM_PE_INTERLEAVED and
+ * SK_TRIM_PE_COMBO_ALL, which frames as interleaved), only where both lie below the reads the call trimmed: a dropped odd
+ * record and a piece's carry are in no count (the report's rule).  The pair MATCHES iff the two keys have the same length
+ * and the same bytes; it is TAG-SWAPPED iff it matches, mate 1's tag is 2 and mate 2's tag is 1.  SK_TRIM_SE has no pairs.
+ * CASAVA 1.8 names match through the space rule, "/1" "/2" names through the tag rule, names with neither must be equal.
+ *   calls, calls_failed   calls that added / that did not (below)
+ *   pairs                 pairs whose names were compared
+ *   name_mismatch         of them: the keys differ
+ *   first_mismatch        the lowest such pair, pairs numbered over all ADDING calls since the reset, in call order; ~0: none.
+ *                         Over a stream of pieces that is the pair's number in the file; in the ordered kinds the number in
+ *                         read order, not in emission order
+ *   tags_swapped          matching pairs with the tags 2, 1
+ *   qual_bytes, qual_min, qual_max   number, lowest and highest of ALL bytes of the quality lines of the call's reads, taken
+ *                         as unsigned (the bytes of the packed batch; params->trunc_n plays no part, nor do the cuts);
+ *                         qual_min = ~0 and qual_max = 0 while qual_bytes == 0
+ *   reserved              the kernels' own words: a call's lowest mismatch and pair count before they are folded
+ * qual_hist_dev (device, uint64_t[256], 8-byte aligned, or NULL): qual_hist_dev[b] counts the quality bytes of value b.
+ * src is the report's source descriptor, with the same four kinds and the same meaning of text_bytes, trunc_n and
+ * batch_capacity: text_bytes is what THAT call's workspace formula took (a piece lays its sections out by its own bounds).
+ * in and mode are what the text call was given: the text pointers for the names, in->bytes as bounds of every load of a
+ * name byte (the descriptors count from text[i], also in a piece).  in == NULL: the names are not looked at and pairs,
+ * name_mismatch, first_mismatch and tags_swapped stay as they are; the same holds for SK_TRIM_SE.  The quality part needs no
+ * text.
+ * Validity is the report's, from the call's own workspace; and a mode whose framing mode (SK_TRIM_PE_COMBO_ALL ->
+ * SK_TRIM_PE_INTERLEAVED) differs from the one the text call recorded counts as failed too.  A call that does not add
+ * increments calls_failed and touches nothing else, neither in the struct nor in the histogram.
+ * When.  On the text call's stream, behind it, before the workspace AND THE TEXTS are reused (a stream driver's text
+ * buffers rotate).  It only enqueues kernels: no copy, no allocation, no wait.  A zeroed struct is not a valid start
+ * (first_mismatch and qual_min start at ~0): the first call on a struct carries SK_FQ_AUDIT_RESET, which sets the struct and
+ * zeroes the histogram by a kernel of its own in front.  Calls that add to one struct must be on one stream; the pair
+ * numbering is their order.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: ctx, src, src->workspace or audit_dev NULL; a workspace that is
+ * not 16-byte aligned, a struct or a histogram that is not 8-byte aligned; an unknown kind or mode; with in given:
+ * SK_TRIM_PE_SPLIT and text[1] NULL, another mode and text[1] not NULL, a pair mode and text[0] NULL with bytes[0] != 0;
+ * flags other than SK_FQ_AUDIT_RESET; src->reserved != 0.
+ */
+#define SK_FQ_AUDIT_RESET 1
+
+typedef struct {
+    uint64_t calls, calls_failed;
+    uint64_t pairs;
+    uint64_t name_mismatch;
+    uint64_t first_mismatch;
+    uint64_t tags_swapped;
+    uint64_t qual_bytes, qual_min, qual_max;
+    uint64_t reserved[7];
+} sk_fastq_audit; /* device memory, 8-byte aligned, 128 bytes */
+
+int sk_trim_fastq_audit_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                     sk_fastq_audit *audit_dev, uint64_t *qual_hist_dev, int flags, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,7 +50,10 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_piece_device_finish", "sk_fastq_carry_device_async", "sk_gzip_inflate_piece_workspace_bytes",
            "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish",
            "sk_trim_fastq_ordered_piece_workspace_bytes", "sk_trim_fastq_ordered_piece_device_async",
-           "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async")
+           "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async",
+           "sk_trim_fastq_audit_device_async")
+# sk_trim_fastq_audit_device_async (include/sickle_amd.h)
+SK_FQ_AUDIT_RESET = 1
 # sk_trim_fastq_report_device_async (include/sickle_amd.h)
 SK_FQ_REPORT_RESET = 1
 SK_FQ_REPORT_MAX_LEN_BINS = 4096
@@ -223,6 +226,55 @@ class _ReportBuffers:
                 rep[name] = w[at:at + n].copy()
             at += n
         return rep
+
+
+class FastqAudit(C.Structure):
+    """sk_fastq_audit: every member is a uint64_t"""
+    _fields_ = [("calls", C.c_uint64), ("calls_failed", C.c_uint64), ("pairs", C.c_uint64), ("name_mismatch", C.c_uint64),
+                ("first_mismatch", C.c_uint64), ("tags_swapped", C.c_uint64), ("qual_bytes", C.c_uint64),
+                ("qual_min", C.c_uint64), ("qual_max", C.c_uint64), ("reserved", C.c_uint64 * 7)]
+
+    def as_dict(self):
+        """the members but `reserved`, as ints"""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+AUDIT_WORDS = C.sizeof(FastqAudit) // 8
+AUDIT_NONE = (1 << 64) - 1  # first_mismatch without a mismatch, qual_min without a byte
+
+
+def qualtypes_consistent(audit):
+    """The names among "sanger", "solexa" and "illumina" whose quality range (sk_quality_constants: [min, max] as bytes)
+    contains the audit's [qual_min, qual_max]; all three when it saw no quality byte.  audit: a dict as the drivers
+    return it, or a FastqAudit.  Bytes that fit "illumina" in a run made with -t sanger are the sign of an offset-64
+    (CASAVA 1.3-1.7) file, which that run trimmed as if every quality were 31 higher."""
+    a = audit.as_dict() if isinstance(audit, FastqAudit) else audit
+    names = ("sanger", "solexa", "illumina")
+    if a["qual_bytes"] == 0:
+        return list(names)
+    out = []
+    for name in names:
+        k = lib().sk_quality_constants(QUALTYPES[name])  # {offset, min, max}
+        if k[1] <= a["qual_min"] and a["qual_max"] <= k[2]:
+            out.append(name)
+    return out
+
+
+class _AuditBuffers:
+    """The device words of one audit=True of a driver: the sk_fastq_audit, then the 256 histogram words, in one tensor."""
+
+    def __init__(self, dev):
+        import torch
+        self.buf = torch.empty(AUDIT_WORDS + 256, dtype=torch.int64, device=dev)
+        self.ptr = self.buf.data_ptr()
+        self.hist_ptr = self.ptr + 8 * AUDIT_WORDS
+
+    def read(self):
+        """-> the audit as a dict: sk_fastq_audit's members but `reserved`, and qual_hist as 256 ints"""
+        w = self.buf.cpu().numpy().view(np.uint64)
+        a = FastqAudit.from_buffer_copy(w[:AUDIT_WORDS].tobytes()).as_dict()
+        a["qual_hist"] = [int(x) for x in w[AUDIT_WORDS:]]
+        return a
 
 
 class FastqPiece(C.Structure):
@@ -540,6 +592,9 @@ def lib():
         L.sk_trim_fastq_report_device_async.restype = C.c_int
         L.sk_trim_fastq_report_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.c_void_p,
                                                         C.POINTER(FastqReportHists), C.c_int, C.c_void_p]
+        L.sk_trim_fastq_audit_device_async.restype = C.c_int
+        L.sk_trim_fastq_audit_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -757,6 +812,20 @@ class Context:
                                                             C.byref(hists) if hists is not None else None,
                                                             SK_FQ_REPORT_RESET if reset else 0, stream))
 
+    def trim_fastq_audit_device_async(self, workspace_ptr, text_bytes, trunc_n, audit_ptr, text_ptrs=None, text_bounds=None,
+                                      mode="se", kind="plain", batch_capacity=0, qual_hist_ptr=None, reset=False, stream=None):
+        """sk_trim_fastq_audit_device_async on raw device pointers: the audit over the workspace and the texts of a text
+        call already enqueued on `stream`.  kind, text_bytes, trunc_n, batch_capacity: as trim_fastq_report_device_async's;
+        text_ptrs, text_bounds: the text call's (None: in == NULL, the names are not looked at); mode: the text call's;
+        audit_ptr: a sk_fastq_audit in device memory; qual_hist_ptr: 256 uint64 in device memory or None.  Only enqueues."""
+        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+        inp = None
+        if text_ptrs is not None:
+            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
+            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        self._check(lib().sk_trim_fastq_audit_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode), audit_ptr,
+                                                           qual_hist_ptr, SK_FQ_AUDIT_RESET if reset else 0, stream))
+
     def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
                                         mode="se", max_read_len=0, stream=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
@@ -885,7 +954,7 @@ class Context:
                                                       stream))
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
-                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False):
+                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -911,23 +980,28 @@ class Context:
         run ends before the text does (an empty batch, a split mismatch) the stream ends there, as the reference does.
         report=True or dict(len_bins=.., pos_bins=..): sk_trim_fastq_report_device_async is enqueued behind every piece's
         emission, zeroing the report in front of the first piece only; the report of the whole file (trim_fastq's dict)
-        is read back once, after the last piece's finish, into .report (None until then, and after a failure)."""
+        is read back once, after the last piece's finish, into .report (None until then, and after a failure).
+        audit=True: sk_trim_fastq_audit_device_async likewise behind every piece, over the piece's workspace and its text
+        buffers, with the reset in front of the first piece only; the audit of the whole file (trim_fastq's
+        counts["audit"]) is read back once into .audit: first_mismatch is the pair's number in the file."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
+                           audit)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0, order=None, batch_capacity=None, report=False):
+                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity, report: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report, audit: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
+                           audit)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
-                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False):
+                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -938,10 +1012,11 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity, report: as in trim_fastq_stream."""
+        batch_capacity, report, audit: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
-        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report)
+        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
+                         audit)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -974,7 +1049,8 @@ class Context:
                 raise
         return call(second)
 
-    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False):
+    def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
+                   audit=False):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -990,14 +1066,28 @@ class Context:
         report=True or dict(len_bins=.., pos_bins=..): the trim report of the writing pass (sk_trim_fastq_report_device_async,
         enqueued behind it) is returned as a third entry, a dict of sk_fastq_report's members and, for the bins given, the
         histograms as uint64 arrays; summary_text(report, mode) gives the reference's closing lines.  report=False: the
-        call is what it was, to the launch."""
+        call is what it was, to the launch.
+        audit=True: the audit of the writing pass (sk_trim_fastq_audit_device_async, enqueued behind it, over its workspace
+        and the texts) is returned as counts["audit"]: sk_fastq_audit's members as ints (first_mismatch and qual_min are
+        AUDIT_NONE where there is none) and qual_hist, 256 ints; qualtypes_consistent(counts["audit"]) names the quality
+        types its bytes allow.  Nothing raises on a mismatch.  audit=False: the call is what it was, to the launch."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
-                                                                                  record_index, o, report))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report)
+                                                                                  record_index, o, report, audit))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit)
 
-    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False):
+    def _audit_behind(self, aud, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
+        """the audit of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has no
+        pointer and no records: the names are then not looked at)"""
+        if any(p is None for p in ptrs):
+            ptrs = None
+        self.trim_fastq_audit_device_async(ws_ptr, sum(bounds), trunc_n, aud.ptr, text_ptrs=ptrs, text_bounds=bounds, mode=mode,
+                                           kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
+                                           batch_capacity=order.batch_capacity if order is not None else 0,
+                                           qual_hist_ptr=aud.hist_ptr, reset=reset, stream=stream)
+
+    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1010,9 +1100,11 @@ class Context:
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         rep = _ReportBuffers(report, dev) if report else None
         # the report goes behind the writing pass's emission and in front of its finish, which is the wait
-        tell = lambda final: final and rep and self.trim_fastq_report_device_async(
+        aud = _AuditBuffers(dev) if audit else None
+        tell = lambda final: final and (rep and self.trim_fastq_report_device_async(
             ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr, kind="plain" if order is None else "ordered",
-            batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream)
+            batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream),
+            aud and self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream))
         if order is None:
             run = lambda outs, final=False: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes,
                                                                           mode=mode, max_read_len=max_read_len, stream=stream),
@@ -1037,6 +1129,8 @@ class Context:
             t, idx = bufs[o]
             R, B = counts["records"][o], counts["bytes"][o]
             res[o] = (t[:B], idx[:R]) if record_index else t[:B]
+        if aud:
+            counts["audit"] = aud.read()
         return (tuple(res), counts, rep.read()) if rep else (tuple(res), counts)
 
     # ---- BGZF on the device -------------------------------------------------------------------
@@ -1072,20 +1166,21 @@ class Context:
                                stream=stream, search=search)
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
-    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False):
+    def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False,
+                      audit=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
         than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
-        as bgzf's.  report: as trim_fastq's, a third entry."""
+        as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"]."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
-                                                                                     search, report))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report)
+                                                                                     search, report, audit))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit)
 
-    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False):
+    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1116,6 +1211,9 @@ class Context:
                                                 kind="plain" if order is None else "ordered",
                                                 batch_capacity=order.batch_capacity if order is not None else 0,
                                                 hists=rep.hists, reset=True, stream=stream)
+        aud = _AuditBuffers(dev) if audit else None
+        if aud:
+            self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1126,6 +1224,8 @@ class Context:
                      for o in range(3)]
         counts = (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
         res = tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3))
+        if aud:
+            counts["audit"] = aud.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     # ---- BGZF read on the device --------------------------------------------------------------
@@ -1292,7 +1392,7 @@ class Context:
         head = bytes(image[:16].cpu().tolist())
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
-    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False):
+    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1338,6 +1438,10 @@ class Context:
                                                 kind="plain" if order is None else "ordered",
                                                 batch_capacity=order.batch_capacity if order is not None else 0,
                                                 hists=rep.hists, reset=True, stream=stream)
+        aud = _AuditBuffers(dev) if audit else None
+        if aud:
+            self._audit_behind(aud, ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order,
+                               True, stream)
         for o in used:
             out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1363,10 +1467,12 @@ class Context:
                      for o in range(3)]
         counts = trim_finish(ws.data_ptr(), stream)
         res = tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3))
+        if aud:
+            counts["audit"] = aud.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
-                kind=None, report=False):
+                kind=None, report=False, audit=False):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
         trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
@@ -1383,7 +1489,7 @@ class Context:
         per-read step of the trim is sized by the capacity, so a tight bound is a fast call.  kind: "bgzf" or "gzip"
         names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
         enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more.
-        report: as trim_fastq's, a third entry."""
+        report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"]."""
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -1394,11 +1500,11 @@ class Context:
             if any(k not in ("bgzf", "gzip") for k in kinds):
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
-                                                                                       max_read_len, o, search, report))
+                                                                                       max_read_len, o, search, report, audit))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
-                                  report=report)
+                                  report=report, audit=audit)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -1528,7 +1634,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False):
+                 batch_capacity=None, report=False, audit=False):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1578,6 +1684,8 @@ class FastqStream:
         self.stream = torch.cuda.current_stream().cuda_stream
         self.report = None
         self._rep = _ReportBuffers(report, dev) if report else None  # (its few words are not in device_bytes)
+        self.audit = None
+        self._aud = _AuditBuffers(dev) if audit else None
         self._gen = self._run()
 
     def __iter__(self):
@@ -1658,6 +1766,9 @@ class FastqStream:
                                              kind="piece" if self.order is None else "ordered_piece",
                                              batch_capacity=self.order.batch_capacity if self.order is not None else 0,
                                              hists=self._rep.hists, reset=k == 0, stream=self.stream)
+        if self._aud:  # likewise; the piece's text buffers are the slot's, which piece k + 2 fills again behind this call
+            c._audit_behind(self._aud, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
+                            self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
         if self.gz:
             for o in self.used:
                 b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
@@ -1751,6 +1862,8 @@ class FastqStream:
         yield from self._run_pieces()
         if self._rep:  # every piece has been finished: the stream has been waited for
             self.report = self._rep.read()
+        if self._aud:
+            self.audit = self._aud.read()
 
     def _run_pieces(self):
         self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])

@@ -1350,6 +1350,35 @@ int sk_trim_fastq_report_device_async(sk_ctx *ctx, const sk_fastq_report_source 
     return SK_OK;
 }
 
+// every check before the first HIP call: bad arguments enqueue nothing and need no device
+int sk_trim_fastq_audit_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                     sk_fastq_audit *audit_dev, uint64_t *qual_hist_dev, int flags, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+#define SK_FQA_BAD(...)               \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!src || !src->workspace || !audit_dev) SK_FQA_BAD("audit: src, src->workspace and audit_dev are required");
+    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQA_BAD("audit: src->workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(audit_dev) & 7) SK_FQA_BAD("audit: audit_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(qual_hist_dev) & 7) SK_FQA_BAD("audit: qual_hist_dev must be 8-byte aligned");
+    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQA_BAD("audit: source kind %u is unknown", src->kind);
+    if (src->reserved != 0) SK_FQA_BAD("audit: src->reserved must be 0");
+    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQA_BAD("audit: mode %d is unknown", mode);
+    if (flags & ~SK_FQ_AUDIT_RESET) SK_FQA_BAD("audit: flags %d are unknown", flags);
+    if (in) {
+        if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQA_BAD("audit: SK_TRIM_PE_SPLIT needs text[1]");
+        if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQA_BAD("audit: text[1] is for SK_TRIM_PE_SPLIT only");
+        if (mode != SK_TRIM_SE && !in->text[0] && in->bytes[0]) SK_FQA_BAD("audit: text[0] is NULL with bytes[0] != 0");
+    }
+#undef SK_FQA_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_audit(src, in, mode, audit_dev, qual_hist_dev, flags, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
 uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags)
 {
     sk_bgzf_layout L;
