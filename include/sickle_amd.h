@@ -1182,6 +1182,75 @@ typedef struct {
 int sk_trim_fastq_audit_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
                                      sk_fastq_audit *audit_dev, uint64_t *qual_hist_dev, int flags, void *hip_stream);
 
+/*
+ * The bases: what the reads are made of, on the device, over the workspace AND the texts of a text call that has been
+ * enqueued on the same stream: base content and N content per position, the reads that hold an N at all, GC per read,
+ * each before and after the cut.  It is what tells whether params->trunc_n (-n) is worth passing and what it will cost.
+ * Exact integers, accumulated in device memory like the report and the audit.  Nothing acts on the result.  This comment
+ * is the normative text; the rule as code is sickle_amd/csrc/sk_fastq_bases.h.  The host CLI does not use it.
+ *
+ * Classes of a seq byte b: 0 'A' 'a'; 1 'C' 'c'; 2 'G' 'g'; 3 'T' 't'; 4 'N' 'n'; 5 everything else (IUPAC codes, '.',
+ * 'U', '\r', bytes >= 0x80).  A byte is LOWER iff it lies in 'a'..'z', whatever its class.
+ * Reads are the report's: read r of the call's packed batch counts only if it lies below the reads the call trimmed; its
+ * cut {five, three} is the workspace's; it is kept iff three >= 0, and then its output is bytes [five, three) of its seq
+ * line.  A dropped odd record and a piece's carry are in no count; the N records of SK_TRIM_PE_COMBO_ALL are not output
+ * bytes, so every `out` figure covers kept reads only.  In the ordered kinds the reads are in read order, which plays no
+ * part.
+ * The seq line of read r is found as the audit finds its name line: through the call's record descriptors, in text[0],
+ * or for SK_TRIM_PE_SPLIT in text[r & 1]; it is the bytes from behind the name line's '\n' to the seq line's '\n', counted
+ * from text[i], also in a piece.  In a call that adds its length is offsets[r + 1] - offsets[r], the quality line's.
+ * Position p counts from the line's first byte.  The bytes are always the text's, with params->trunc_n or without.
+ *   calls, calls_failed   calls that added / that did not (below)
+ *   reads, kept           as in the report
+ *   bases_in[c]           seq bytes of class c over all reads;  bases_out[c]: over the output bytes of kept reads
+ *   lower_in, lower_out   LOWER bytes likewise
+ *   reads_n_in            reads with at least one byte of class 4;  reads_n_out: kept reads whose output holds one
+ *   gc_none_in            reads with no byte of class 0-3;  gc_none_out: kept reads whose output has none (an empty output
+ *                         is one)
+ *   reserved              zero
+ * Arrays (sk_fastq_bases_hists, may be NULL, as may each array in it; device arrays of uint64_t that the caller owns):
+ * pos_in[6 * pos_bins] and pos_out[6 * pos_bins]: entry c * pos_bins + min(p, pos_bins - 1) counts the bytes of class c
+ * at position p; for pos_out over output bytes, p counted from five.  pos_bins <= SK_FQ_BASES_MAX_POS_BINS: the tables are
+ * summed in LDS, 2 * 6 * 1024 32-bit counters, 48 KiB.  gc_in[101] and gc_out[101]: a read whose bytes of class 0-3 number
+ * acgt > 0 counts in bin floor(100 * (C + G) / acgt), C and G its bytes of classes 1 and 2; gc_out: kept reads, over their
+ * output.  A read with acgt == 0 counts in gc_none_* instead.
+ * src is the report's source descriptor.  in and mode are what the text call was given; the texts are required, they are
+ * the data, and in->bytes bound every load of a seq byte.
+ * Validity is the audit's: the report's, from the call's own workspace, and a mode whose framing mode differs from the one
+ * the text call recorded counts as failed too.  A call that does not add increments calls_failed and touches nothing else,
+ * neither in the struct nor in the arrays.  SK_ESPACE does not matter: a counting call reports in full.
+ * When.  On the text call's stream, behind it, before the workspace AND THE TEXTS are reused.  It only enqueues kernels: no
+ * copy, no allocation, no wait.  SK_FQ_BASES_RESET zeroes the struct and the given arrays first, by a kernel of its own; a
+ * zeroed struct is a valid start.  Calls that add to one struct must be on one stream.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: ctx, src, src->workspace, bases_dev or in NULL; a workspace
+ * that is not 16-byte aligned, a struct or an array that is not 8-byte aligned; an unknown kind, mode or flags;
+ * src->reserved != 0; SK_TRIM_PE_SPLIT and text[1] NULL, another mode and text[1] not NULL; text[0] NULL with bytes[0] != 0;
+ * pos_bins of 0 with a position array given, or above its limit.
+ */
+#define SK_FQ_BASES_RESET 1
+#define SK_FQ_BASES_MAX_POS_BINS 1024u
+#define SK_FQ_BASES_GC_BINS 101u
+
+typedef struct {
+    uint64_t calls, calls_failed;
+    uint64_t reads, kept;
+    uint64_t bases_in[6], bases_out[6];
+    uint64_t lower_in, lower_out;
+    uint64_t reads_n_in, reads_n_out;
+    uint64_t gc_none_in, gc_none_out;
+    uint64_t reserved[2];
+} sk_fastq_bases; /* device memory, 8-byte aligned, 192 bytes */
+
+typedef struct {
+    uint64_t *pos_in, *pos_out; /* device, 8-byte aligned, [6 * pos_bins], or NULL */
+    uint64_t pos_bins;
+    uint64_t *gc_in, *gc_out;   /* device, 8-byte aligned, [SK_FQ_BASES_GC_BINS], or NULL */
+} sk_fastq_bases_hists;
+
+int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                     sk_fastq_bases *bases_dev, const sk_fastq_bases_hists *hists, int flags,
+                                     void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,12 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish",
            "sk_trim_fastq_ordered_piece_workspace_bytes", "sk_trim_fastq_ordered_piece_device_async",
            "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async",
-           "sk_trim_fastq_audit_device_async")
+           "sk_trim_fastq_audit_device_async", "sk_trim_fastq_bases_device_async")
+# sk_trim_fastq_bases_device_async (include/sickle_amd.h)
+SK_FQ_BASES_RESET = 1
+SK_FQ_BASES_MAX_POS_BINS = 1024
+SK_FQ_BASES_GC_BINS = 101
+BASES_CLASSES = ("A", "C", "G", "T", "N", "other")
 # sk_trim_fastq_audit_device_async (include/sickle_amd.h)
 SK_FQ_AUDIT_RESET = 1
 # sk_trim_fastq_report_device_async (include/sickle_amd.h)
@@ -275,6 +280,63 @@ class _AuditBuffers:
         a = FastqAudit.from_buffer_copy(w[:AUDIT_WORDS].tobytes()).as_dict()
         a["qual_hist"] = [int(x) for x in w[AUDIT_WORDS:]]
         return a
+
+
+class FastqBases(C.Structure):
+    """sk_fastq_bases: every member is a uint64_t"""
+    _fields_ = [("calls", C.c_uint64), ("calls_failed", C.c_uint64), ("reads", C.c_uint64), ("kept", C.c_uint64),
+                ("bases_in", C.c_uint64 * 6), ("bases_out", C.c_uint64 * 6), ("lower_in", C.c_uint64),
+                ("lower_out", C.c_uint64), ("reads_n_in", C.c_uint64), ("reads_n_out", C.c_uint64),
+                ("gc_none_in", C.c_uint64), ("gc_none_out", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        """the members but `reserved`, as ints; bases_in and bases_out as lists of six, in the order of BASES_CLASSES"""
+        return {name: (list(getattr(self, name)) if name.startswith("bases") else int(getattr(self, name)))
+                for name, _ in self._fields_ if name != "reserved"}
+
+
+BASES_WORDS = C.sizeof(FastqBases) // 8
+
+
+class FastqBasesHists(C.Structure):
+    _fields_ = [("pos_in", C.c_void_p), ("pos_out", C.c_void_p), ("pos_bins", C.c_uint64), ("gc_in", C.c_void_p),
+                ("gc_out", C.c_void_p)]
+
+
+class _BasesBuffers:
+    """The device words of one bases= of a driver: the sk_fastq_bases, then the arrays bases=dict(pos_bins=.., gc=True)
+    asks for (both position tables of the bins given, both GC histograms), in one tensor."""
+
+    def __init__(self, bases, dev):
+        import torch
+        opts = bases if isinstance(bases, dict) else {}
+        unknown = set(opts) - {"pos_bins", "gc"}
+        if unknown:
+            raise ValueError("bases: unknown keys %r" % sorted(unknown))
+        self.pos_bins, self.gc = int(opts.get("pos_bins", 0)), bool(opts.get("gc", False))
+        G = SK_FQ_BASES_GC_BINS if self.gc else 0
+        self.buf = torch.empty(BASES_WORDS + 12 * self.pos_bins + 2 * G, dtype=torch.int64, device=dev)
+        self.ptr = self.buf.data_ptr()
+        self.hists = None
+        if self.pos_bins or G:
+            at = lambda words: self.ptr + 8 * (BASES_WORDS + words)
+            P = self.pos_bins
+            self.hists = FastqBasesHists(at(0) if P else None, at(6 * P) if P else None, P, at(12 * P) if G else None,
+                                         at(12 * P + G) if G else None)
+
+    def read(self):
+        """-> the bases as a dict: sk_fastq_bases's members but `reserved`; pos_in and pos_out as uint64 arrays of shape
+        (6, pos_bins), gc_in and gc_out of 101, where asked for"""
+        w = self.buf.cpu().numpy().view(np.uint64)
+        b = FastqBases.from_buffer_copy(w[:BASES_WORDS].tobytes()).as_dict()
+        at, P = BASES_WORDS, self.pos_bins
+        if P:
+            b["pos_in"], b["pos_out"] = w[at:at + 6 * P].reshape(6, P).copy(), w[at + 6 * P:at + 12 * P].reshape(6, P).copy()
+        at += 12 * P
+        if self.gc:
+            G = SK_FQ_BASES_GC_BINS
+            b["gc_in"], b["gc_out"] = w[at:at + G].copy(), w[at + G:at + 2 * G].copy()
+        return b
 
 
 class FastqPiece(C.Structure):
@@ -592,6 +654,9 @@ def lib():
         L.sk_trim_fastq_report_device_async.restype = C.c_int
         L.sk_trim_fastq_report_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.c_void_p,
                                                         C.POINTER(FastqReportHists), C.c_int, C.c_void_p]
+        L.sk_trim_fastq_bases_device_async.restype = C.c_int
+        L.sk_trim_fastq_bases_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
+                                                       C.c_int, C.c_void_p, C.POINTER(FastqBasesHists), C.c_int, C.c_void_p]
         L.sk_trim_fastq_audit_device_async.restype = C.c_int
         L.sk_trim_fastq_audit_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -826,6 +891,21 @@ class Context:
         self._check(lib().sk_trim_fastq_audit_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode), audit_ptr,
                                                            qual_hist_ptr, SK_FQ_AUDIT_RESET if reset else 0, stream))
 
+    def trim_fastq_bases_device_async(self, workspace_ptr, text_bytes, trunc_n, bases_ptr, text_ptrs, text_bounds, mode="se",
+                                      kind="plain", batch_capacity=0, hists=None, reset=False, stream=None):
+        """sk_trim_fastq_bases_device_async on raw device pointers: the bases over the workspace and the texts of a text
+        call already enqueued on `stream`.  kind, text_bytes, trunc_n, batch_capacity: as trim_fastq_report_device_async's;
+        text_ptrs, text_bounds, mode: the text call's (text_ptrs None: in == NULL, which is refused: the texts are the
+        data); bases_ptr: a sk_fastq_bases in device memory; hists: a FastqBasesHists or None.  Only enqueues."""
+        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+        inp = None
+        if text_ptrs is not None:
+            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
+            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        self._check(lib().sk_trim_fastq_bases_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode), bases_ptr,
+                                                           C.byref(hists) if hists is not None else None,
+                                                           SK_FQ_BASES_RESET if reset else 0, stream))
+
     def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
                                         mode="se", max_read_len=0, stream=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
@@ -954,7 +1034,7 @@ class Context:
                                                       stream))
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
-                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
+                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -983,25 +1063,28 @@ class Context:
         is read back once, after the last piece's finish, into .report (None until then, and after a failure).
         audit=True: sk_trim_fastq_audit_device_async likewise behind every piece, over the piece's workspace and its text
         buffers, with the reset in front of the first piece only; the audit of the whole file (trim_fastq's
-        counts["audit"]) is read back once into .audit: first_mismatch is the pair's number in the file."""
+        counts["audit"]) is read back once into .audit: first_mismatch is the pair's number in the file.
+        bases=True or dict(pos_bins=.., gc=True): sk_trim_fastq_bases_device_async likewise behind every piece, over the
+        piece's workspace and its text buffers, with the reset in front of the first piece only; the bases of the whole
+        file (trim_fastq's counts["bases"]) are read back once into .bases (None until then, and after a failure)."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit)
+                           audit, bases)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
+                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity, report, audit: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report, audit, bases: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit)
+                           audit, bases)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
-                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False):
+                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -1012,11 +1095,11 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity, report, audit: as in trim_fastq_stream."""
+        batch_capacity, report, audit, bases: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
         st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                         audit)
+                         audit, bases)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1050,7 +1133,7 @@ class Context:
         return call(second)
 
     def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
-                   audit=False):
+                   audit=False, bases=False):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -1070,12 +1153,16 @@ class Context:
         audit=True: the audit of the writing pass (sk_trim_fastq_audit_device_async, enqueued behind it, over its workspace
         and the texts) is returned as counts["audit"]: sk_fastq_audit's members as ints (first_mismatch and qual_min are
         AUDIT_NONE where there is none) and qual_hist, 256 ints; qualtypes_consistent(counts["audit"]) names the quality
-        types its bytes allow.  Nothing raises on a mismatch.  audit=False: the call is what it was, to the launch."""
+        types its bytes allow.  Nothing raises on a mismatch.  audit=False: the call is what it was, to the launch.
+        bases=True or dict(pos_bins=.., gc=True): the bases of the writing pass (sk_trim_fastq_bases_device_async, enqueued
+        behind it, over its workspace and the texts) are returned as counts["bases"]: sk_fastq_bases's members as ints
+        (bases_in and bases_out: six, in the order of BASES_CLASSES) and, where asked for, pos_in and pos_out as uint64
+        arrays of shape (6, pos_bins) and gc_in and gc_out of 101.  bases=False: the call is what it was, to the launch."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
-                                                                                  record_index, o, report, audit))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit)
+                                                                                  record_index, o, report, audit, bases))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases)
 
     def _audit_behind(self, aud, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
         """the audit of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has no
@@ -1087,7 +1174,18 @@ class Context:
                                            batch_capacity=order.batch_capacity if order is not None else 0,
                                            qual_hist_ptr=aud.hist_ptr, reset=reset, stream=stream)
 
-    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False):
+    def _bases_behind(self, bas, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
+        """the bases of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has
+        no pointer: it gets the struct's own address with the bound 0, of which no byte is loaded)"""
+        total = sum(bounds)
+        bounds = [0 if p is None else b for p, b in zip(ptrs, bounds)]
+        ptrs = [bas.ptr if p is None else p for p in ptrs]
+        self.trim_fastq_bases_device_async(ws_ptr, total, trunc_n, bas.ptr, ptrs, bounds, mode=mode,
+                                           kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
+                                           batch_capacity=order.batch_capacity if order is not None else 0,
+                                           hists=bas.hists, reset=reset, stream=stream)
+
+    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1101,10 +1199,12 @@ class Context:
         rep = _ReportBuffers(report, dev) if report else None
         # the report goes behind the writing pass's emission and in front of its finish, which is the wait
         aud = _AuditBuffers(dev) if audit else None
+        bas = _BasesBuffers(bases, dev) if bases else None
         tell = lambda final: final and (rep and self.trim_fastq_report_device_async(
             ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr, kind="plain" if order is None else "ordered",
             batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream),
-            aud and self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream))
+            aud and self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream),
+            bas and self._bases_behind(bas, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream))
         if order is None:
             run = lambda outs, final=False: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes,
                                                                           mode=mode, max_read_len=max_read_len, stream=stream),
@@ -1131,6 +1231,8 @@ class Context:
             res[o] = (t[:B], idx[:R]) if record_index else t[:B]
         if aud:
             counts["audit"] = aud.read()
+        if bas:
+            counts["bases"] = bas.read()
         return (tuple(res), counts, rep.read()) if rep else (tuple(res), counts)
 
     # ---- BGZF on the device -------------------------------------------------------------------
@@ -1167,20 +1269,22 @@ class Context:
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
     def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False,
-                      audit=False):
+                      audit=False, bases=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
         than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
-        as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"]."""
+        as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as
+        trim_fastq's, counts["bases"]."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
-                                                                                     search, report, audit))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit)
+                                                                                     search, report, audit, bases))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases)
 
-    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False):
+    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False,
+                       bases=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1214,6 +1318,9 @@ class Context:
         aud = _AuditBuffers(dev) if audit else None
         if aud:
             self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream)
+        bas = _BasesBuffers(bases, dev) if bases else None
+        if bas:
+            self._bases_behind(bas, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1226,6 +1333,8 @@ class Context:
         res = tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3))
         if aud:
             counts["audit"] = aud.read()
+        if bas:
+            counts["bases"] = bas.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     # ---- BGZF read on the device --------------------------------------------------------------
@@ -1392,7 +1501,8 @@ class Context:
         head = bytes(image[:16].cpu().tolist())
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
-    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False):
+    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False,
+                         bases=False):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1442,6 +1552,10 @@ class Context:
         if aud:
             self._audit_behind(aud, ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order,
                                True, stream)
+        bas = _BasesBuffers(bases, dev) if bases else None
+        if bas:
+            self._bases_behind(bas, ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order,
+                               True, stream)
         for o in used:
             out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1469,10 +1583,12 @@ class Context:
         res = tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3))
         if aud:
             counts["audit"] = aud.read()
+        if bas:
+            counts["bases"] = bas.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
-                kind=None, report=False, audit=False):
+                kind=None, report=False, audit=False, bases=False):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
         trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
@@ -1489,7 +1605,8 @@ class Context:
         per-read step of the trim is sized by the capacity, so a tight bound is a fast call.  kind: "bgzf" or "gzip"
         names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
         enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more.
-        report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"]."""
+        report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as trim_fastq's,
+        counts["bases"]."""
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -1500,11 +1617,12 @@ class Context:
             if any(k not in ("bgzf", "gzip") for k in kinds):
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
-                                                                                       max_read_len, o, search, report, audit))
+                                                                                       max_read_len, o, search, report, audit,
+                                                                                       bases))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
-                                  report=report, audit=audit)
+                                  report=report, audit=audit, bases=bases)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -1634,7 +1752,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False, audit=False):
+                 batch_capacity=None, report=False, audit=False, bases=False):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1686,6 +1804,8 @@ class FastqStream:
         self._rep = _ReportBuffers(report, dev) if report else None  # (its few words are not in device_bytes)
         self.audit = None
         self._aud = _AuditBuffers(dev) if audit else None
+        self.bases = None
+        self._bas = _BasesBuffers(bases, dev) if bases else None
         self._gen = self._run()
 
     def __iter__(self):
@@ -1768,6 +1888,9 @@ class FastqStream:
                                              hists=self._rep.hists, reset=k == 0, stream=self.stream)
         if self._aud:  # likewise; the piece's text buffers are the slot's, which piece k + 2 fills again behind this call
             c._audit_behind(self._aud, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
+                            self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
+        if self._bas:  # likewise
+            c._bases_behind(self._bas, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
                             self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
         if self.gz:
             for o in self.used:
@@ -1864,6 +1987,8 @@ class FastqStream:
             self.report = self._rep.read()
         if self._aud:
             self.audit = self._aud.read()
+        if self._bas:
+            self.bases = self._bas.read()
 
     def _run_pieces(self):
         self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])

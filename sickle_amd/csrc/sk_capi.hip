@@ -1379,6 +1379,41 @@ int sk_trim_fastq_audit_device_async(sk_ctx *ctx, const sk_fastq_report_source *
     return SK_OK;
 }
 
+// every check before the first HIP call: bad arguments enqueue nothing and need no device
+int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                     sk_fastq_bases *bases_dev, const sk_fastq_bases_hists *hists, int flags, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+#define SK_FQB_BAD(...)               \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!src || !src->workspace || !bases_dev || !in) SK_FQB_BAD("bases: src, src->workspace, bases_dev and in are required");
+    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQB_BAD("bases: src->workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(bases_dev) & 7) SK_FQB_BAD("bases: bases_dev must be 8-byte aligned");
+    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQB_BAD("bases: source kind %u is unknown", src->kind);
+    if (src->reserved != 0) SK_FQB_BAD("bases: src->reserved must be 0");
+    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQB_BAD("bases: mode %d is unknown", mode);
+    if (flags & ~SK_FQ_BASES_RESET) SK_FQB_BAD("bases: flags %d are unknown", flags);
+    if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQB_BAD("bases: SK_TRIM_PE_SPLIT needs text[1]");
+    if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQB_BAD("bases: text[1] is for SK_TRIM_PE_SPLIT only");
+    if (!in->text[0] && in->bytes[0]) SK_FQB_BAD("bases: text[0] is NULL with bytes[0] != 0");
+    if (hists) {
+        const uintptr_t pos = reinterpret_cast<uintptr_t>(hists->pos_in) | reinterpret_cast<uintptr_t>(hists->pos_out);
+        const uintptr_t gc = reinterpret_cast<uintptr_t>(hists->gc_in) | reinterpret_cast<uintptr_t>(hists->gc_out);
+        if ((pos | gc) & 7) SK_FQB_BAD("bases: the arrays must be 8-byte aligned");
+        if (pos && hists->pos_bins == 0) SK_FQB_BAD("bases: pos_bins is 0 with a position array given");
+        if (hists->pos_bins > SK_FQ_BASES_MAX_POS_BINS)
+            SK_FQB_BAD("bases: pos_bins %llu is above SK_FQ_BASES_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
+                       SK_FQ_BASES_MAX_POS_BINS);
+    }
+#undef SK_FQB_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_bases(src, in, mode, bases_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
 uint64_t sk_bgzf_bound(uint64_t text_bytes, int flags)
 {
     sk_bgzf_layout L;

@@ -442,6 +442,13 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_audi
                                                                                   sk_fastq_audit *audit_dev,
                                                                                   uint64_t *qual_hist_dev, int flags,
                                                                                   hipStream_t stream);
+// the bases over a text call's workspace and texts (sk_fastq_bases.hip); the arguments have passed the checks of
+// sk_trim_fastq_bases_device_async
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_bases(const sk_fastq_report_source *src,
+                                                                                  const sk_fastq_input *in, int mode,
+                                                                                  sk_fastq_bases *bases_dev,
+                                                                                  const sk_fastq_bases_hists *hists, int flags,
+                                                                                  hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
