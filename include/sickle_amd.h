@@ -277,6 +277,7 @@ int sk_count_pairs_device_finish(sk_ctx *ctx, void *hip_stream, sk_pair_counts *
  * sk_trim_workspace_bytes(n_reads) bytes: 128 + 64 * ceil(n_reads / 2048) + 8 * n_reads, i.e. below
  * 8.04 bytes per read + 192 bytes).  sk_trim_device_finish is the only call that waits: it reads the counts out of the
  * workspace after the stream's work.  Two trims in flight at once need two workspaces.
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  */
 typedef struct {
     uint8_t *qual;            /* device, 16-byte aligned, or NULL (then no bytes are written) */
@@ -361,12 +362,15 @@ int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_tri
  * sk_trim_fastq_device_async only enqueues kernels on hip_stream: no copy, no synchronisation, no allocation beyond the
  * one sk_scan_device_async makes on its own (the regrouping scratch of a context's first big mixed batch).  All scratch
  * lives in `workspace` (device, 16-byte aligned), sized without a look at the text by the most records and qual bytes a
- * valid text of T = bytes[0] + bytes[1] bytes can hold.  With H = floor((T + 2) / 16):
- *   sk_trim_fastq_workspace_bytes(T, trunc_n) = 544 + 144 H + 16 floor(T / 65536) + 64 ceil((H + 1) / 1024)
+ * valid text of T = bytes[0] + bytes[1] bytes can hold, and by the most lines any text of T bytes can hold (a descriptor
+ * slot for every four lines: the ordered calls count lines of malformed texts too).  With H = floor((T + 2) / 16) and
+ * G = floor((T + 7) / 8):
+ *   sk_trim_fastq_workspace_bytes(T, trunc_n) = 464 + 80 G + 64 H + 16 floor(T / 65536) + 64 ceil((H + 1) / 1024)
  *                                               + (trunc_n ? 2 : 1) * 16 ceil(T / 32)
- * i.e. about 9.5 bytes per text byte (10 with trunc_n).  It holds for any text, malformed ones included.  finish is the
+ * i.e. about 14.5 bytes per text byte (15 with trunc_n).  It holds for any text, malformed ones included.  finish is the
  * only call that waits: it reads the counts out of the workspace and reads and clears the stream's range-error word (a
  * later sk_scan_device_finish on that stream does not report it again).  Two calls in flight need two workspaces.
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  */
 enum { SK_FQ_OK = 0, SK_FQ_ID_SHORT = 1, SK_FQ_ID_NO_AT = 2, SK_FQ_SEQ_EMPTY = 3, SK_FQ_QUAL_EMPTY = 4, SK_FQ_LENGTHS = 5,
        SK_FQ_TOO_LONG = 6, SK_FQ_PAIR_COUNT = 7 };
@@ -442,7 +446,8 @@ int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, 
  * ends at the end of the text, as above (the reference's reader drops its last character).
  *
  * The workspace: sk_trim_fastq_ordered_workspace_bytes(text_bytes, trunc_n, batch_capacity), with text_bytes = bytes[0] +
- * bytes[1], is sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + 8 (batch_capacity + 1) rounded up to 16.  The number
+ * bytes[1], is sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + 8 (batch_capacity + 1) rounded up to 16.  Its contents
+ * on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.  The number
  * of batches depends on the text: a batch usually holds about batch_len bytes, fewer when long carried lines use the
  * budget up.  A caller starts at, say, batch_capacity = text_bytes / batch_len + 16 and calls again with a larger table
  * when it was too small: finish then returns SK_ESPACE with batches = batch_capacity + 1 ("more than") and nothing
@@ -522,6 +527,7 @@ const char *sk_bgzf_last_error(void);
  * bytes_out = the need.  sk_bgzf_bound(bytes, flags) = bytes + 31 ceil(bytes / 65280) + (SK_BGZF_EOF ? 28 : 0) always
  * suffices (a stored member is its text + 5 + 26 bytes).
  *
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  * sk_bgzf_device_async only enqueues three kernels on hip_stream: no allocation, no copy, no synchronisation, no lock.  All
  * scratch and the counts live in `workspace` (device, 16-byte aligned).  With NB = ceil(text_bytes / 65280):
  *   sk_bgzf_workspace_bytes(text_bytes) = 128 + 16 NB + 261152 min(NB, 1280) + 65536 NB
@@ -611,6 +617,7 @@ int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t
  * where and why), SK_ESPACE, SK_OK.  After SK_EDATA out[0, min(bytes_out, capacity)) is undefined; no byte at or beyond
  * capacity is ever written, and a member writes inside its own ISIZE span only.  A corrupt image is never read outside
  * [image, image + image_bytes).  `image` has any alignment, `out` and `workspace` are 16-byte aligned.
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  *
  * sk_bgzf_inflate_device_async only enqueues kernels on hip_stream (with R = ceil(log2(floor(n / 26) + 1)): 6 + R when
  * counting, 8 + R otherwise, the last one a single lane that writes the word of sk_bgzf_inflate_output_words): no allocation,
@@ -671,6 +678,7 @@ int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream
  * precedence, SK_EDATA, SK_ESPACE, SK_OK.  After SK_EDATA out[0, min(bytes_out, capacity)) is undefined.  No byte at or
  * beyond capacity is ever written, none outside [image, image + image_bytes) is ever read.  `image` has any alignment,
  * `out` and `workspace` are 16-byte aligned.
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  *
  * sk_gzip_inflate_device_async only enqueues kernels on hip_stream (3 when counting, 9 otherwise): no allocation, no copy,
  * no synchronisation.  All scratch and the counts live in `workspace`.  With n = image_bytes, A(x) = 16 ceil(x / 16),
@@ -747,6 +755,7 @@ int sk_gzip_inflate_output_words(void *workspace, const uint64_t **bytes_dev, co
  * sk_gzip_inflate_output_words works on a piece's workspace: the piece's text length and its written word, which feed
  * sk_fastq_carry_device_async as the BGZF reader's do.
  *
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  * sk_gzip_inflate_piece_device_async only enqueues kernels (10) on hip_stream: no allocation, no copy, no wait.  Two pieces
  * in flight need two workspaces and alternate two states.  With w = window_bytes, chunk and S taken on w as
  * sk_gzip_inflate_workspace_bytes takes them on n (SK_GZIP_CHUNK applies likewise):
@@ -845,8 +854,8 @@ int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_
  * pieces is sk_trim_fastq_ordered_piece_device_async (below).  This comment is the normative text.
  *
  * sk_trim_fastq_piece_device_async is sk_trim_fastq_chained_device_async(.., order = NULL, ..), and everything said there
- * holds (the workspace is sk_trim_fastq_workspace_bytes(bytes[0] + bytes[1], trunc_n), everything sized on the host is a
- * function of in->bytes), with what follows.  piece == NULL is that call bit for bit: the same launches, nothing more
+ * holds (the workspace is sk_trim_fastq_workspace_bytes(bytes[0] + bytes[1], trunc_n), its contents on entry are arbitrary
+ * and nothing outside it is written, everything sized on the host is a function of in->bytes), with what follows.  piece == NULL is that call bit for bit: the same launches, nothing more
  * loaded, finished by sk_trim_fastq_device_finish.  A call with a piece is finished by sk_trim_fastq_piece_device_finish.
  * Window.  n_i is text i's length as the chained call defines it (in->bytes, bytes_dev, valid_dev).  s_i = min(*start_dev[i],
  * n_i), or 0 for a NULL word.  Text i of the call is text[i][s_i, n_i): the first line starts at s_i, no 16-byte block
@@ -862,8 +871,8 @@ int sk_scan_counted_device_async(sk_ctx *ctx, const sk_params *params, const sk_
  * piece's first record).  Everything behind them is the carry: not checked, not scanned, no format or range error comes
  * from it; SK_FQ_PAIR_COUNT never occurs and dropped_unpaired is 0.  records_in[i] = u; tail_lines[i] = the complete lines
  * carried, lines_i - 4u, which may exceed 3.  consumed_i = s_i when u == 0, else one past the '\n' of line 4u - 1.  A text
- * with more records than the call has descriptor slots ends in SK_EFORMAT, as in the whole-text call (a malformed record
- * lies among the consumed ones).
+ * with more records than the packed batch has reads, (b + 1) / 8, ends in SK_EFORMAT, as in the whole-text call (a
+ * malformed record lies among the consumed ones).
  * The stream's range-error word.  The frame scan captures the word as it is when the piece begins.  If it is set -- an
  * earlier call on the stream met a range error that no finish has cleared yet -- the piece is void: it takes no record
  * (u = 0, nothing checked, scanned or emitted, so the earlier error stays as it is), ok = 0, and its finish returns
@@ -998,6 +1007,7 @@ int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int inp
  * the batch table:
  *   sk_trim_fastq_ordered_piece_workspace_bytes(text_bytes, trunc_n, batch_capacity)
  *       = sk_trim_fastq_ordered_workspace_bytes(text_bytes, trunc_n, batch_capacity) + 256
+ * The workspace's contents on entry are arbitrary, and nothing outside [workspace, workspace + bytes) is written.
  * A batch usually holds about batch_len bytes, so batch_capacity = text_bytes / batch_len + 16 is a good guess, and a wrong
  * one costs nothing but shorter pieces.  The walk's serial loop is bounded by batch_capacity + 1 steps.
  * Same discipline: only kernels are enqueued, finish is the only call that waits.  SK_EINVAL, nothing enqueued: the bad

@@ -140,10 +140,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
                                                                            const sk_trim_output *out, void *workspace,
                                                                            int cu_count, hipStream_t stream);
 // FASTQ text on the device (sk_fastq.hip).  The caller's workspace (16-byte sections, sizes in bytes, T = text bytes of all
-// inputs, H = (T + 2) / 16):
+// inputs, H = (T + 2) / 16, G = (T + 7) / 8):
 //   header    SK_FQ_HDR_WORDS words
 //   chunks    16 per framing chunk of SK_FQ_CHUNK_BYTES (T / 65536 + 3 chunks at most over both inputs): '\n' count, last '\n'
-//   desc      40 per record slot, 2H + 4 slots: name start and the end of each of the four lines of record k
+//   desc      40 per record slot, 2G + 2 slots: name start and the end of each of the four lines of record k
 //   offsets   8 * (N + 2), N = 2H + 2: the packed batch's offsets (n_pack + 1 of them)
 //   cuts      8 * N
 //   blocks    64 per block of SK_FQ_BLOCK_READS packed reads (the pack's, then the emission's block table)
@@ -151,8 +151,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 //   qual, seq 16 * ceil(T / 32) each (seq only with trunc_n): the packed batch
 // Sizing by the worst case, without a look at the text: a valid record is at least 8 bytes ("@a\nA\n+\nI\n"; 7 for an
 // unterminated last one), so text i of b bytes holds at most (b + 1) / 8 valid records and at most b / 2 bytes of qual.
-// It gets (b + 1) / 8 + 1 slots: the first slots records cannot all be valid in a text with more, so a record that gets
-// no slot is never the lowest malformed one, and a text with more records than the packed batch holds is SK_EFORMAT.
+// The packed batch is sized by that; a text with more records than it holds is SK_EFORMAT.  The descriptors are sized by
+// the lines of any text, valid or not: b bytes hold at most b lines, so b / 4 + 1 slots take every line of text i, and
+// the ordered calls, whose batches and counts are a matter of lines alone, see all of them (with (b + 1) / 8 + 1 slots
+// they stopped at the last slot of a text of empty lines).  The clamps at the slot count in the kernels never bite.
 #define SK_FQ_CHUNK_BYTES 65536u
 #define SK_FQ_BLOCK_READS 2048u
 #define SK_FQ_BLOCK_WORDS 8u
@@ -179,7 +181,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 struct sk_fq_layout {
     uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
 };
-static inline uint64_t sk_fq_slots(uint64_t bytes) { return (bytes + 1) / 8 + 1; }
+static inline uint64_t sk_fq_slots(uint64_t bytes) { return bytes / 4 + 1; }
 // reads of the packed batch: the most valid records the text(s) can hold
 static inline uint64_t sk_fq_pack_reads(uint64_t bytes0, uint64_t bytes1, int mode)
 {
@@ -188,7 +190,7 @@ static inline uint64_t sk_fq_pack_reads(uint64_t bytes0, uint64_t bytes1, int mo
 }
 static inline void sk_fq_layout_of(uint64_t text_bytes, int trunc_n, sk_fq_layout *L)
 {
-    const uint64_t H = (text_bytes + 2) / 16, S = 2 * H + 4, N = 2 * H + 2;
+    const uint64_t H = (text_bytes + 2) / 16, S = 2 * ((text_bytes + 7) / 8) + 2, N = 2 * H + 2; // S >= b0 / 4 + b1 / 4 + 2
     const uint64_t NC = text_bytes / SK_FQ_CHUNK_BYTES + 3, NB = (N + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
     const uint64_t Q = 16 * ((text_bytes + 31) / 32);
     L->chunks = 8 * SK_FQ_HDR_WORDS;

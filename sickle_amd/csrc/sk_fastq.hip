@@ -206,7 +206,7 @@ __device__ __forceinline__ void fq_block_scan(uint64_t (&v)[N], uint64_t (&total
 __device__ __forceinline__ void fq_put_line(const fq_args &a, int i, uint64_t ln, uint64_t start, uint64_t end)
 {
     const uint64_t r = ln >> 2;
-    if (r >= a.slots[i]) return; // only in a text with a malformed record below this one (sk_device.h)
+    if (r >= a.slots[i]) return; // never: b bytes hold at most b lines (sk_device.h)
     uint64_t *d = a.desc[i] + 5 * r;
     if ((ln & 3) == 0) d[0] = start;
     d[1 + (ln & 3)] = end;
@@ -366,6 +366,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_frame_lines_kernel(fq_args a
 __global__ void __launch_bounds__(FQ_THREADS) sk_fq_check_kernel(fq_args a)
 {
     const uint64_t *h = a.hdr;
+    // the clamps never bite: every record with a line has a slot (sk_device.h)
     const uint64_t n0 = min(h[SK_FQ_H_RECORDS], a.slots[0]), n1 = min(h[SK_FQ_H_RECORDS + 1], a.slots[1]);
     uint64_t best = ~0ull;
     for (uint64_t g = (uint64_t)blockIdx.x * FQ_THREADS + threadIdx.x; g < n0 + n1; g += (uint64_t)gridDim.x * FQ_THREADS) {
@@ -601,7 +602,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_scan_kernel(fq_args a)
         const uint64_t u = a.hdr[SK_FQ_H_RECORDS + i], end = a.hdr[SK_FQP_H_END + i];
         uint64_t consumed = a.hdr[SK_FQP_H_START + i];
         if (!a.hdr[SK_FQP_H_MORE] || i >= (a.mode == SK_TRIM_PE_SPLIT ? 2 : 1)) consumed = end; // the stream ends here
-        else if (u > a.slots[i]) consumed = end; // only in a text with a malformed record among the consumed ones
+        else if (u > a.slots[i]) consumed = end; // never: every record with a line has a slot (sk_device.h)
         else if (u) consumed = a.desc[i][5 * (u - 1) + 4] + 1;
         a.hdr[SK_FQP_H_CONSUMED + i] = consumed;
     }
@@ -897,8 +898,7 @@ struct fq_order {
     uint32_t threads;
 };
 
-// lines of text i the descriptor table holds (all of them, but for a text with a malformed record among its first
-// slots[i] records: sk_device.h)
+// lines of text i the descriptor table holds: all of them (sk_device.h: a slot for every four lines of any text)
 __device__ __forceinline__ uint64_t fq_order_lines(const fq_args &a, int i)
 {
     return min(a.hdr[SK_FQ_H_LINES + i], 4 * a.slots[i]);

@@ -15,9 +15,16 @@ def torch_mod():
     return torch
 
 
-def upload(text, shift=0):
-    """text (bytes) on the device at an address that is `shift` bytes past a 16-byte boundary."""
+HOSTILE_TEXT = b"\n@x\nACGT\n+\nIIII\n"  # records that an over-read would find around a text
+
+
+def upload(text, shift=0, surround=None):
+    """text (bytes) on the device at an address that is `shift` bytes past a 16-byte boundary.  surround: None = zeros
+    around the text, else bytes repeated in the 256 bytes before and the 4096 bytes behind it (bgzf_raw.surrounded)."""
     torch = torch_mod()
+    if surround is not None:
+        import bgzf_raw
+        return bgzf_raw.surrounded(text, shift, 0, surround)
     buf = torch.zeros(len(text) + shift + 16, dtype=torch.uint8, device="cuda")
     if len(text):
         buf[shift:shift + len(text)] = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
@@ -25,11 +32,12 @@ def upload(text, shift=0):
 
 
 def raw(ctx, params, texts, mode, caps=None, rec_caps=None, shift=0, max_read_len=0, index=True, ws=None, stream=None,
-        finish=True, room=0):
+        finish=True, room=0, surround=None):
     """One async + finish on raw pointers, every output pre-filled with SENTINEL.  caps / rec_caps: per output (None =
-    what the model says plus a little); room: sentinel bytes / entries behind every output's capacity.  -> (rc, counts, [bytes or None], [index arrays or None])."""
+    what the model says plus a little); room: sentinel bytes / entries behind every output's capacity; surround: what
+    lies around the texts (upload).  -> (rc, counts, [bytes or None], [index arrays or None])."""
     torch = torch_mod()
-    bufs = [upload(t, shift) for t in texts]
+    bufs = [upload(t, shift, surround) for t in texts]
     T = sum(len(t) for t in texts)
     ws_bytes = capi.lib().sk_trim_fastq_workspace_bytes(T, params.trunc_n)
     if ws is None:

@@ -21,12 +21,12 @@ pytestmark = pytest.mark.gpu
 GUARD = 64
 
 
-def inflate(ctx, image, shift=0, capacity=None, count_only=False, ws=None):
+def inflate(ctx, image, shift=0, capacity=None, count_only=False, ws=None, surround=None):
     """One async + finish on raw pointers; `out` is capacity + GUARD bytes of SENTINEL, and the guard is checked here, in
     every test.  capacity None: what the model says the text needs.  -> (rc, counts, out tensor narrowed to capacity)"""
     torch = torch_mod()
     L = capi.lib()
-    keep, ptr = upload(image, shift)
+    keep, ptr = upload(image, shift, surround=surround)  # surround: what lies around the image (bgzf_raw.upload)
     need = L.sk_bgzf_inflate_workspace_bytes(len(image))
     if ws is None:
         ws = torch.empty(need, dtype=torch.uint8, device="cuda")

@@ -26,13 +26,13 @@ def host(tmp_path_factory):
     return {name: (data, st.host_image(data, d, name, "eof")) for name, data in texts.items()}
 
 
-def raw(ctx, text, flags=SEARCH, shift=0, bound=None, dev_len=None, valid=None, capacity=None, ws=None):
+def raw(ctx, text, flags=SEARCH, shift=0, bound=None, dev_len=None, valid=None, capacity=None, ws=None, surround=None):
     """One async + finish on raw pointers, `out` pre-filled with SENTINEL (bgzf_raw.raw with flags and a workspace that
     can be handed in) -> (rc of the async call or of finish, counts, out tensor)."""
     torch = torch_mod()
     L = capi.lib()
     nbytes = len(text) if bound is None else bound
-    keep, ptr = upload(text, shift, room=nbytes - len(text))
+    keep, ptr = upload(text, shift, room=nbytes - len(text), surround=surround)
     cap = L.sk_bgzf_bound(nbytes, flags) if capacity is None else capacity
     out = torch.full((cap + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
     if ws is None:

@@ -59,10 +59,11 @@ def word(value):
     return torch.tensor([value], dtype=torch.int64, device="cuda")
 
 
-def chained(ctx, ptuple, ptrs, bounds, mode, ns=(), valids=(), order=None, no_lengths=False, index=True):
+def chained(ctx, ptuple, ptrs, bounds, mode, ns=(), valids=(), order=None, no_lengths=False, index=True, ws=None):
     """One sk_trim_fastq_chained_device_async + finish on raw pointers, every output pre-filled with SENTINEL and GUARD
     more bytes / entries behind its capacity.  ptrs / bounds: the texts' addresses and in->bytes; ns / valids: the values of
-    the device words (None = no such word).  -> (rc, counts (with "order" in ordered calls), keep, batch table or None)"""
+    the device words (None = no such word).  ws: the workspace tensor, used as it is (the byte count handed to the library
+    stays the formula's).  -> (rc, counts (with "order" in ordered calls), keep, batch table or None)"""
     torch = torch_mod()
     L = capi.lib()
     params = capi.make_params(*ptuple)
@@ -71,7 +72,8 @@ def chained(ctx, ptuple, ptrs, bounds, mode, ns=(), valids=(), order=None, no_le
         ws_bytes = L.sk_trim_fastq_workspace_bytes(T, params.trunc_n)
     else:
         ws_bytes = L.sk_trim_fastq_ordered_workspace_bytes(T, params.trunc_n, order.batch_capacity)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     cap, rcap = T + 64, T // 4 + 4
     outs, keep = [], []
     for o in range(3):

@@ -25,17 +25,19 @@ def to_dev(text):
     return torch_mod().from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
 
 
-def raw(ctx, params, texts, mode, threads, batch_len, capacity=None, limit=0, caps=None, shift=0):
-    """One ordered async + finish on raw pointers, every output pre-filled with SENTINEL.
+def raw(ctx, params, texts, mode, threads, batch_len, capacity=None, limit=0, caps=None, shift=0, ws=None, surround=None):
+    """One ordered async + finish on raw pointers, every output pre-filled with SENTINEL.  ws: the workspace tensor, used
+    as it is (the byte count handed to the library stays the formula's); surround: what lies around the texts.
     -> (rc, counts with "order", keep, table of first units)"""
     torch = torch_mod()
-    bufs = [upload(t, shift) for t in texts]
+    bufs = [upload(t, shift, surround) for t in texts]
     T = sum(len(t) for t in texts)
     capacity = capacity or T // batch_len + 16
     L = capi.lib()
     ws_bytes = L.sk_trim_fastq_ordered_workspace_bytes(T, params.trunc_n, capacity)
     assert ws_bytes == L.sk_trim_fastq_workspace_bytes(T, params.trunc_n) + (8 * (capacity + 1) + 15) // 16 * 16
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    if ws is None:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
     caps = caps or [T + 64] * 3
     outs, keep = [], []
     for o in range(3):

@@ -19,7 +19,7 @@ import fastq_order_model as om
 import fastq_order_piece_model as opm
 import fastq_util as fu
 import trim_model as tm
-from bgzf_raw import to_device
+from bgzf_raw import surrounded, to_device
 from fastq_raw import SENTINEL, torch_mod
 from sickle_amd import capi
 from test_fastq_api import golden_texts
@@ -56,18 +56,24 @@ def model_sequence(ptuple, texts, mode, threads, batch_len, capacity, steps, lim
     return want
 
 
-def run_sequence(ctx, ptuple, texts, mode, threads, batch_len, capacity, steps, limit=0, short=None, shift=3):
+def run_sequence(ctx, ptuple, texts, mode, threads, batch_len, capacity, steps, limit=0, short=None, shift=3, ws=None,
+                 seen=None, surround=None):
     """steps: [(n per input, more)]: piece j's window is [what piece j - 1 did not consume, n) of each text: its start is
     the consumed word piece j - 1 published, its end a device word, so the windows are the stream's (the carry and the
     next chunk).  Piece j reads state j and writes state j + 1.  Every piece is enqueued before the first finish.  short:
     {piece: output} whose capacity is one byte less than it needs.  Each piece is compared with opm.piece on the
-    model's own windows; -> the model's pieces."""
+    model's own windows.  ws: one workspace tensor per step, each used as it is (the byte count handed to the library stays
+    the formula's); seen: a list that takes, per piece, (rc, counts, the state it wrote, the words it published, every
+    output tensor as bytes).  -> the model's pieces."""
     torch = torch_mod()
     L = capi.lib()
     params = capi.make_params(*ptuple)
     n_in = len(texts)
     want = model_sequence(ptuple, texts, mode, threads, batch_len, capacity, steps, limit, short)  # also: what a short output needs
-    bufs = [place(t, shift + 5 * i) for i, t in enumerate(texts)]
+    if surround is None:
+        bufs = [place(t, shift + 5 * i) for i, t in enumerate(texts)]
+    else:  # what lies around the texts (bgzf_raw.surrounded)
+        bufs = [surrounded(t, (shift + 5 * i) % 16, 0, surround) for i, t in enumerate(texts)]
     order = capi.FastqOrder(threads, 0, batch_len, capacity, limit)
     states = torch.zeros((len(steps) + 1, 8), dtype=torch.int64, device="cuda")
     ends = torch.tensor([list(ns) + [0] * (2 - n_in) for ns, _ in steps], dtype=torch.int64, device="cuda")
@@ -75,7 +81,7 @@ def run_sequence(ctx, ptuple, texts, mode, threads, batch_len, capacity, steps, 
     for j, (ns, more) in enumerate(steps):
         T = sum(ns)
         ws_bytes = L.sk_trim_fastq_ordered_piece_workspace_bytes(T, params.trunc_n, capacity)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        step_ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda") if ws is None else ws[j]
         cap, rcap = T + 64, T // 4 + 4
         outs, keep, caps = [], [], []
         for o in range(3):
@@ -90,10 +96,10 @@ def run_sequence(ctx, ptuple, texts, mode, threads, batch_len, capacity, steps, 
         prev = calls[-1]["ws"].data_ptr() if calls else None
         starts = [capi.Context.trim_fastq_piece_words(prev, i)[0] if prev else None for i in range(n_in)]
         ctx.trim_fastq_ordered_piece_device_async(params, [b[1] for b in bufs], list(ns), order, states[j].data_ptr(),
-                                                  states[j + 1].data_ptr(), outs, ws.data_ptr(), ws_bytes,
+                                                  states[j + 1].data_ptr(), outs, step_ws.data_ptr(), ws_bytes,
                                                   bytes_dev_ptrs=[ends[j, i:].data_ptr() for i in range(n_in)],
                                                   start_dev_ptrs=starts, more=more, mode=mode)
-        calls.append({"ws": ws, "keep": keep, "caps": caps, "cap": cap, "rcap": rcap})
+        calls.append({"ws": step_ws, "keep": keep, "caps": caps, "cap": cap, "rcap": rcap})
     host_states = None
     for j, (call, p) in enumerate(zip(calls, want)):
         rc, _, counts = ctx._ordered_piece_finish(call["ws"].data_ptr(), None)
@@ -127,11 +133,16 @@ def run_sequence(ctx, ptuple, texts, mode, threads, batch_len, capacity, steps, 
         assert opc["state"] == p["state"], tag
         dev_state = capi.FastqOrderState.from_buffer_copy(host_states[j + 1].tobytes()).as_dict()
         assert dev_state == p["state"], tag  # what the next piece started from
+        published = []
         for i in range(n_in):  # the words a carry would go by
             words = capi.Context.trim_fastq_piece_words(call["ws"].data_ptr(), i)
             hdr = call["ws"][:256].cpu().numpy().view(np.uint64)
             got = [int(hdr[(w - call["ws"].data_ptr()) // 8]) for w in words]
             assert got == [p["base"][i] + p["consumed"][i], p["ns"][i], p["ok"]], tag
+            published.append(got)
+        if seen is not None:
+            seen.append((rc, counts, host_states[j + 1].tobytes(), published,
+                         [(t.cpu().numpy().tobytes(), ix.cpu().numpy().tobytes()) for t, ix in call["keep"]]))
         if p["long_line"] is not None and not p["inherited_range"] and not p["inherited_failure"]:
             assert (oc["long_line_input"], oc["long_line"]) == p["long_line"], tag
         if rc == capi.SK_EFORMAT:

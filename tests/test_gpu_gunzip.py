@@ -26,9 +26,11 @@ GUARD = 64
 KEYS = ("error", "error_member", "error_offset")
 
 
-def inflate(ctx, image, shift=0, capacity=None, count_only=False, chunk=0, monkeypatch=None):
+def inflate(ctx, image, shift=0, capacity=None, count_only=False, chunk=0, monkeypatch=None, ws=None, surround=None):
     """One async + finish on raw pointers; `out` is capacity + GUARD bytes of SENTINEL, and the guard is checked here, in
-    every test.  capacity None: the model's bytes_out.  chunk: SK_GZIP_CHUNK for the call.  -> (rc, counts, out[:capacity])"""
+    every test.  capacity None: the model's bytes_out.  chunk: SK_GZIP_CHUNK for the call.  ws: the workspace tensor, used
+    as it is (the byte count handed to the library stays the formula's).  surround: what lies around the image on the
+    device (bgzf_raw.upload).  -> (rc, counts, out[:capacity])"""
     torch = torch_mod()
     L = capi.lib()
     if monkeypatch is not None:
@@ -36,13 +38,14 @@ def inflate(ctx, image, shift=0, capacity=None, count_only=False, chunk=0, monke
             monkeypatch.setenv("SK_GZIP_CHUNK", str(chunk))
         else:
             monkeypatch.delenv("SK_GZIP_CHUNK", raising=False)
-    keep, ptr = upload(image, shift)
+    keep, ptr = upload(image, shift, surround=surround)
     cap = gm.gunzip(image)["bytes_out"] if capacity is None else capacity
     need = L.sk_gzip_inflate_workspace_bytes(len(image), 0 if count_only else cap)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
     out = torch.full((cap + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
     rc = L.sk_gzip_inflate_device_async(ctx._h, ptr if len(image) else None, len(image), None if count_only else out.data_ptr(),
-                                        0 if count_only else cap, ws.data_ptr(), ws.numel(), None)
+                                        0 if count_only else cap, ws.data_ptr(), need, None)
     assert rc == capi.SK_OK, L.sk_last_error(ctx._h)
     c = capi.GzipInflateCounts()
     rc = L.sk_gzip_inflate_device_finish(ctx._h, ws.data_ptr(), None, C.byref(c))

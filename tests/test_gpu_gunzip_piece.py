@@ -40,21 +40,23 @@ class Pieces:
     """Pieces on raw pointers, enqueued by add() and read by finish(): piece i goes from states[i] to states[i + 1] unless
     told otherwise, into a text buffer of capacity + GUARD bytes of SENTINEL whose guard finish() checks."""
 
-    def __init__(self, ctx, image, slots, shift=0, start=None):
+    def __init__(self, ctx, image, slots, shift=0, start=None, surround=None):
         torch = torch_mod()
         self.ctx, self.L, self.image = ctx, capi.lib(), image
-        self.keep, self.ptr = upload(image, shift)
+        self.keep, self.ptr = upload(image, shift, surround=surround)
         self.states = torch.zeros((slots + 1, STATE), dtype=torch.uint8, device="cuda")
         if start is not None:
             self.states[0] = to_device(start)
         self.calls = []
 
-    def add(self, window, capacity, src, dst, last=1, lo=0, hi=None):
-        """image[lo:hi] is handed in, with image_offset = lo"""
+    def add(self, window, capacity, src, dst, last=1, lo=0, hi=None, ws=None):
+        """image[lo:hi] is handed in, with image_offset = lo.  ws: the workspace tensor, used as it is (the byte count
+        handed to the library stays the formula's)"""
         torch = torch_mod()
         hi = len(self.image) if hi is None else hi
         ws_bytes = self.L.sk_gzip_inflate_piece_workspace_bytes(window, capacity)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        if ws is None:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
         out = torch.full((capacity + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda")
         piece = capi.GzipPiece(lo, window, last, 0)
         rc = self.L.sk_gzip_inflate_piece_device_async(self.ctx._h, self.ptr + lo if hi > lo else None, hi - lo, C.byref(piece),
