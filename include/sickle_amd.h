@@ -1261,6 +1261,78 @@ int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *
                                      sk_fastq_bases *bases_dev, const sk_fastq_bases_hists *hists, int flags,
                                      void *hip_stream);
 
+/*
+ * The rejects: the records of the reads a text call did NOT keep, as FASTQ text in device memory, over the workspace AND
+ * the texts of a text call that has been enqueued on the same stream.  It is fastp's --failed_out and cutadapt's
+ * --too-short-output: the records to look at, or to trim again with other settings.  The reference has no counterpart (it
+ * drops them); what ties this to it is conservation: what the text call wrote plus the rejects is what it read.  This
+ * comment is the normative text; the rule as code is sickle_amd/csrc/sk_fastq_rejects.h.  The host CLI does not use it.
+ *
+ * Reads are the report's: read r of the text call's packed batch with r < the reads the call trimmed (the header's
+ * SK_FQ_H_NREAL).  A dropped odd record, a piece's carry and the records behind an ordered call's last batch are not reads.
+ * A read is kept iff its cut has three >= 0.  In the pair framings reads 2k and 2k + 1 are pair k.
+ * Selection.  flags == 0: every read that is not kept.  SK_FQ_REJECTS_PAIRS: both mates of every pair of which at least one
+ * mate is not kept, kept mates included; the rejects text is then a valid interleaved text that can be trimmed again.
+ * SK_FQ_REJECTS_PAIRS with SK_TRIM_SE is SK_EINVAL.  SK_TRIM_PE_COMBO_ALL selects as SK_TRIM_PE_INTERLEAVED does; the N
+ * records it emitted are no part of this.
+ * Record.  A record is the input's own four lines, uncut: bytes [s0, e3) of the record's text (SK_TRIM_PE_SPLIT: text[r & 1]),
+ * s0 the name line's first byte and e3 the end of the quality line, then one '\n': e3 - s0 + 1 bytes.  The closing '\n' is
+ * always synthesized and never loaded, so an unterminated last line gains it (in the chained forms the byte at e3 lies
+ * beyond the text).  A '\r' belongs to its line and is copied.
+ * Order.  Read order, in every kind: the ordered kinds do not reorder the rejects (the audit numbers its pairs the same way).
+ * Index.  out->record_index gets the read number of each record, in the text call's numbering.
+ * Validity is the audit's, taken from the text call's own workspace: no format verdict, no range verdict (for the piece
+ * kinds also none inherited: a void piece), not SK_ELONGLINE nor a full batch table; and a mode whose framing mode
+ * (SK_TRIM_PE_COMBO_ALL -> SK_TRIM_PE_INTERLEAVED) differs from the one the text call recorded makes the call void too.  A void
+ * call writes nothing to `out`; its counts are records = bytes = reads = 0 and valid = 0, its words are *bytes_dev = 0 and
+ * *written_dev = 0, and its finish returns SK_OK.  SK_ESPACE of the text call does not matter: a counting text call can be
+ * followed by a counting rejects call.
+ * Capacity.  out == NULL or out->text == NULL: the call only counts (its words are 0).  Bytes beyond out->capacity, or
+ * records beyond out->record_capacity with a record_index given: nothing is written to either buffer, finish returns
+ * SK_ESPACE with the needs in counts, and the words are 0.  A text buffer of sk_trim_fastq_rejects_bound(T) = T + 2 bytes
+ * always fits, T = the text call's bytes[0] + bytes[1]: the records' spans are disjoint parts of the texts, and every
+ * record's '\n' but an unterminated last line's (one per text) is a text byte outside every span.
+ * Counts.  records, bytes: the selected records and their bytes, exact: bytes is the sum of e3 - s0 + 1 over them.  reads
+ * is the reads the text call trimmed.  valid: 1, or 0 for a void call.  flags: the call's.
+ * Words.  sk_trim_fastq_rejects_output_words gives two device words of the workspace with the meaning
+ * sk_bgzf_input's bytes_dev and valid_dev take: the bytes written, and 1 iff they were written.  sk_bgzf_device_async chains
+ * behind the rejects with no host wait; after a void call, a counting call or one that did not fit, its image is the EOF
+ * member alone.
+ * Workspace.  sk_trim_fastq_rejects_workspace_bytes(T) is a pure function of src->text_bytes:
+ *   128 + 16 ceil(N / 2048) + 16 N,  N = 2 floor((T + 2) / 16) + 2
+ * a header, a table of blocks and an output offset and a read number per read the packed batch can hold, the emission's
+ * cost.  Its contents on entry are arbitrary.  Nothing outside the workspace, out->text[0, capacity) and
+ * out->record_index[0, record_capacity) is ever written.  Every load of a descriptor is bounded by the slots of the text
+ * call's section, every load of a text byte by in->bytes[i]: a source that names the wrong layout or the wrong texts
+ * gives wrong bytes, never a load outside the workspaces and the texts (but for the rest of an aligned 16-byte block that
+ * holds a wanted byte, as in the text call), and never an unbounded walk.
+ * When.  On the text call's stream, behind it, before its workspace AND ITS TEXTS are reused.  sk_trim_fastq_rejects_device_async
+ * only enqueues kernels: no copy, no allocation, no wait; all scratch and counts live in `workspace`.  finish is the only
+ * call that waits.  Two rejects calls in flight need two workspaces.  src is the report's source descriptor; in and mode
+ * are what the text call was given.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: ctx, src, src->workspace, in or workspace NULL; src->workspace,
+ * workspace or out->text not 16-byte aligned, out->record_index not 8-byte aligned; an unknown kind, mode or flag;
+ * SK_FQ_REJECTS_PAIRS with SK_TRIM_SE; src->reserved != 0; SK_TRIM_PE_SPLIT and text[1] NULL, another mode and text[1] not
+ * NULL; a text NULL with bytes != 0; workspace_bytes below sk_trim_fastq_rejects_workspace_bytes(src->text_bytes).
+ */
+#define SK_FQ_REJECTS_PAIRS 1
+
+typedef struct {
+    uint64_t records, bytes; /* the selected records and their bytes: what the buffers need */
+    uint64_t reads;          /* the reads the text call trimmed */
+    uint32_t valid;          /* 0: a void call */
+    uint32_t flags;
+} sk_fastq_rejects_counts;
+
+size_t sk_trim_fastq_rejects_workspace_bytes(uint64_t text_bytes); /* pure, no device */
+uint64_t sk_trim_fastq_rejects_bound(uint64_t text_bytes);         /* pure: a text buffer that always fits */
+int sk_trim_fastq_rejects_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                       const sk_fastq_output *out, int flags, void *workspace, size_t workspace_bytes,
+                                       void *hip_stream);
+/* Waits for hip_stream and fills *counts: SK_OK, or SK_ESPACE with the needs. */
+int sk_trim_fastq_rejects_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_rejects_counts *counts);
+int sk_trim_fastq_rejects_output_words(void *rejects_workspace, const uint64_t **bytes_dev, const uint64_t **written_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,11 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_gzip_inflate_piece_device_async", "sk_gzip_inflate_piece_device_finish",
            "sk_trim_fastq_ordered_piece_workspace_bytes", "sk_trim_fastq_ordered_piece_device_async",
            "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async",
-           "sk_trim_fastq_audit_device_async", "sk_trim_fastq_bases_device_async")
+           "sk_trim_fastq_audit_device_async", "sk_trim_fastq_bases_device_async",
+           "sk_trim_fastq_rejects_workspace_bytes", "sk_trim_fastq_rejects_bound", "sk_trim_fastq_rejects_device_async",
+           "sk_trim_fastq_rejects_device_finish", "sk_trim_fastq_rejects_output_words")
+# sk_trim_fastq_rejects_device_async (include/sickle_amd.h)
+SK_FQ_REJECTS_PAIRS = 1
 # sk_trim_fastq_bases_device_async (include/sickle_amd.h)
 SK_FQ_BASES_RESET = 1
 SK_FQ_BASES_MAX_POS_BINS = 1024
@@ -337,6 +341,26 @@ class _BasesBuffers:
             G = SK_FQ_BASES_GC_BINS
             b["gc_in"], b["gc_out"] = w[at:at + G].copy(), w[at + G:at + 2 * G].copy()
         return b
+
+
+class FastqRejectsCounts(C.Structure):
+    """sk_fastq_rejects_counts"""
+    _fields_ = [("records", C.c_uint64), ("bytes", C.c_uint64), ("reads", C.c_uint64), ("valid", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def _rejects_flags(rejects):
+    """rejects=True | "pairs" (or the flags themselves) -> the flags of sk_trim_fastq_rejects_device_async"""
+    if rejects is True:
+        return 0
+    if rejects == "pairs":
+        return SK_FQ_REJECTS_PAIRS
+    if isinstance(rejects, int) and not isinstance(rejects, bool):
+        return rejects
+    raise ValueError("rejects: False, True or \"pairs\", not %r" % (rejects,))
 
 
 class FastqPiece(C.Structure):
@@ -660,6 +684,18 @@ def lib():
         L.sk_trim_fastq_audit_device_async.restype = C.c_int
         L.sk_trim_fastq_audit_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.sk_trim_fastq_rejects_workspace_bytes.restype = C.c_size_t
+        L.sk_trim_fastq_rejects_workspace_bytes.argtypes = [C.c_uint64]
+        L.sk_trim_fastq_rejects_bound.restype = C.c_uint64
+        L.sk_trim_fastq_rejects_bound.argtypes = [C.c_uint64]
+        L.sk_trim_fastq_rejects_device_async.restype = C.c_int
+        L.sk_trim_fastq_rejects_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
+                                                         C.c_int, C.POINTER(FastqOutput), C.c_int, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p]
+        L.sk_trim_fastq_rejects_device_finish.restype = C.c_int
+        L.sk_trim_fastq_rejects_device_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FastqRejectsCounts)]
+        L.sk_trim_fastq_rejects_output_words.restype = C.c_int
+        L.sk_trim_fastq_rejects_output_words.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         _lib = L
     return _lib
 
@@ -906,6 +942,43 @@ class Context:
                                                            C.byref(hists) if hists is not None else None,
                                                            SK_FQ_BASES_RESET if reset else 0, stream))
 
+    def trim_fastq_rejects_device_async(self, src_workspace_ptr, text_bytes, trunc_n, text_ptrs, text_bounds, out, workspace_ptr,
+                                        workspace_bytes, mode="se", kind="plain", batch_capacity=0, pairs=False, stream=None):
+        """sk_trim_fastq_rejects_device_async on raw device pointers: the records of the reads that were not kept, over
+        the workspace and the texts of a text call already enqueued on `stream`.  kind, text_bytes, trunc_n,
+        batch_capacity: as trim_fastq_report_device_async's; text_ptrs, text_bounds, mode: the text call's; out: a
+        FastqOutput or None (the call only counts); workspace_ptr, workspace_bytes: the rejects call's own workspace
+        (sk_trim_fastq_rejects_workspace_bytes(text_bytes)); pairs: SK_FQ_REJECTS_PAIRS (or the flags as an int).
+        Only enqueues."""
+        src = FastqReportSource(src_workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+        inp = None
+        if text_ptrs is not None:
+            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
+            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        flags = pairs if isinstance(pairs, int) and not isinstance(pairs, bool) else (SK_FQ_REJECTS_PAIRS if pairs else 0)
+        self._check(lib().sk_trim_fastq_rejects_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode),
+                                                             C.byref(out) if out is not None else None, flags, workspace_ptr,
+                                                             workspace_bytes, stream))
+
+    def trim_fastq_rejects_device_finish(self, workspace_ptr, stream=None):
+        """sk_trim_fastq_rejects_device_finish -> counts (dict); raises TrimError (with .counts, the needs) on SK_ESPACE."""
+        c = FastqRejectsCounts()
+        rc = lib().sk_trim_fastq_rejects_device_finish(self._h, workspace_ptr, stream, C.byref(c))
+        if rc == SK_ESPACE:
+            raise TrimError("fastq rejects failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
+        self._check(rc)
+        return c.as_dict()
+
+    @staticmethod
+    def trim_fastq_rejects_output_words(rejects_workspace_ptr):
+        """sk_trim_fastq_rejects_output_words -> (bytes_dev, written_dev), device addresses for bgzf_device_async's
+        bytes_dev_ptr and valid_dev_ptr"""
+        b, w = C.c_void_p(), C.c_void_p()
+        rc = lib().sk_trim_fastq_rejects_output_words(rejects_workspace_ptr, C.byref(b), C.byref(w))
+        if rc != SK_OK:
+            raise SickleError("sk_trim_fastq_rejects_output_words failed (%d)" % rc)
+        return b.value, w.value
+
     def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
                                         mode="se", max_read_len=0, stream=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
@@ -1034,7 +1107,8 @@ class Context:
                                                       stream))
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
-                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
+                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
+                          rejects=False):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -1066,25 +1140,33 @@ class Context:
         counts["audit"]) is read back once into .audit: first_mismatch is the pair's number in the file.
         bases=True or dict(pos_bins=.., gc=True): sk_trim_fastq_bases_device_async likewise behind every piece, over the
         piece's workspace and its text buffers, with the reset in front of the first piece only; the bases of the whole
-        file (trim_fastq's counts["bases"]) are read back once into .bases (None until then, and after a failure)."""
+        file (trim_fastq's counts["bases"]) are read back once into .bases (None until then, and after a failure).
+        rejects=True or "pairs": sk_trim_fastq_rejects_device_async behind every piece, over the piece's workspace and its
+        text buffers before they rotate, into two more output buffers (and, with gz=True, images and writer workspaces)
+        that .device_bytes includes.  Every yielded tuple gains a fourth entry, the piece's rejects as bytes: the records
+        of the reads the piece did not keep ("pairs": both mates of every pair with such a mate), the input's own four
+        lines, in read order also with order=; with gz=True BGZF members written through the call's output words, of which
+        only the last piece's carry the EOF member.  The entries concatenated are the rejects of the whole file.  .rejects
+        holds the summed records and bytes after the last piece (None until then, and after a failure)."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases)
+                           audit, bases, rejects)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
+                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False, rejects=False):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity, report, audit, bases: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report, audit, bases, rejects: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases)
+                           audit, bases, rejects)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
-                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False):
+                         search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
+                         rejects=False):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -1095,11 +1177,11 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity, report, audit, bases: as in trim_fastq_stream."""
+        batch_capacity, report, audit, bases, rejects: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
         st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                         audit, bases)
+                         audit, bases, rejects)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1133,7 +1215,7 @@ class Context:
         return call(second)
 
     def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
-                   audit=False, bases=False):
+                   audit=False, bases=False, rejects=False):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -1157,12 +1239,18 @@ class Context:
         bases=True or dict(pos_bins=.., gc=True): the bases of the writing pass (sk_trim_fastq_bases_device_async, enqueued
         behind it, over its workspace and the texts) are returned as counts["bases"]: sk_fastq_bases's members as ints
         (bases_in and bases_out: six, in the order of BASES_CLASSES) and, where asked for, pos_in and pos_out as uint64
-        arrays of shape (6, pos_bins) and gc_in and gc_out of 101.  bases=False: the call is what it was, to the launch."""
+        arrays of shape (6, pos_bins) and gc_in and gc_out of 101.  bases=False: the call is what it was, to the launch.
+        rejects=True or "pairs": the records of the reads that were not kept (sk_trim_fastq_rejects_device_async; "pairs":
+        both mates of every pair with such a mate, SK_FQ_REJECTS_PAIRS), the input's own four lines, in read order.  A
+        counting rejects call behind the counting pass sizes the buffer, the writing one goes behind the writing pass and
+        in front of its finish.  counts["rejects"] = {"text": uint8 tensor, "index": int64 tensor of read numbers (None
+        without record_index=True), "records", "bytes", "reads"}.  rejects=False: the call is what it was, to the launch."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
-                                                                                  record_index, o, report, audit, bases))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases)
+                                                                                  record_index, o, report, audit, bases,
+                                                                                  rejects))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects)
 
     def _audit_behind(self, aud, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
         """the audit of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has no
@@ -1185,7 +1273,20 @@ class Context:
                                            batch_capacity=order.batch_capacity if order is not None else 0,
                                            hists=bas.hists, reset=reset, stream=stream)
 
-    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False):
+    def _rejects_behind(self, rws, out, flags, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, stream):
+        """the rejects of a driver's text call: behind it on its stream, over its workspace and its texts, into the
+        workspace rws (an empty text has no pointer: it gets rws's own address with the bound 0, of which no byte is
+        loaded)"""
+        total = sum(bounds)
+        bounds = [0 if p is None else b for p, b in zip(ptrs, bounds)]
+        ptrs = [rws.data_ptr() if p is None else p for p in ptrs]
+        self.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, ptrs, bounds, out, rws.data_ptr(), rws.numel(), mode=mode,
+                                             kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
+                                             batch_capacity=order.batch_capacity if order is not None else 0, pairs=flags,
+                                             stream=stream)
+
+    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False,
+                    rejects=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1205,16 +1306,31 @@ class Context:
             batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream),
             aud and self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream),
             bas and self._bases_behind(bas, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream))
+        # the rejects: a counting call behind the counting pass, the writing one behind the writing pass
+        rej_out = [None]
+        if rejects:
+            rej_flags = _rejects_flags(rejects)
+            rws = torch.empty(lib().sk_trim_fastq_rejects_workspace_bytes(sum(sizes)), dtype=torch.uint8, device=dev)
+            spill = lambda: self._rejects_behind(rws, rej_out[0], rej_flags, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode,
+                                                 "plain", order, stream)
+        else:
+            spill = lambda: None
         if order is None:
             run = lambda outs, final=False: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes,
                                                                           mode=mode, max_read_len=max_read_len, stream=stream),
-                                             tell(final), self.trim_fastq_device_finish(ws.data_ptr(), stream))[2]
+                                             tell(final), spill(), self.trim_fastq_device_finish(ws.data_ptr(), stream))[3]
         else:
             run = lambda outs, final=False: (self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(),
                                                                                   ws_bytes, mode=mode, max_read_len=max_read_len,
                                                                                   stream=stream),
-                                             tell(final), self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[2]
+                                             tell(final), spill(), self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[3]
         counts = run([FastqOutput() for _ in range(3)])
+        if rejects:
+            need = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
+            rej_text = torch.empty(max(need["bytes"], 16), dtype=torch.uint8, device=dev)
+            rej_idx = torch.empty(max(need["records"], 1), dtype=torch.int64, device=dev) if record_index else None
+            rej_out[0] = FastqOutput(rej_text.data_ptr(), need["bytes"], rej_idx.data_ptr() if record_index else None,
+                                     need["records"])
         used = TRIM_OUTPUTS[mode]
         bufs, outs = [None] * 3, [FastqOutput() for _ in range(3)]
         for o in used:
@@ -1233,6 +1349,10 @@ class Context:
             counts["audit"] = aud.read()
         if bas:
             counts["bases"] = bas.read()
+        if rejects:
+            got = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
+            counts["rejects"] = {"text": rej_text[:got["bytes"]], "index": rej_idx[:got["records"]] if record_index else None,
+                                 "records": got["records"], "bytes": got["bytes"], "reads": got["reads"]}
         return (tuple(res), counts, rep.read()) if rep else (tuple(res), counts)
 
     # ---- BGZF on the device -------------------------------------------------------------------
@@ -1752,7 +1872,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False, audit=False, bases=False):
+                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1806,6 +1926,21 @@ class FastqStream:
         self._aud = _AuditBuffers(dev) if audit else None
         self.bases = None
         self._bas = _BasesBuffers(bases, dev) if bases else None
+        self.rejects = None
+        self._rej = bool(rejects)
+        if rejects:  # a workspace and a text buffer (an image, a writer workspace) per slot, sized by the slot's text buffers
+            self._rej_flags = _rejects_flags(rejects)
+            if self._rej_flags & SK_FQ_REJECTS_PAIRS and mode == "se":
+                raise ValueError("rejects=\"pairs\" needs a pair mode")
+            self._rej_sum = {"records": 0, "bytes": 0}
+            self.jws = [alloc(L.sk_trim_fastq_rejects_workspace_bytes(n_in * cap_in)) for _ in range(2)]
+            self.jcap = L.sk_trim_fastq_rejects_bound(n_in * cap_in)
+            self.jout = [alloc(self.jcap) for _ in range(2)]
+            if gz:
+                self.jimg_cap = L.sk_bgzf_bound(self.jcap, SK_BGZF_EOF)
+                self.jzws_bytes = L.sk_bgzf_workspace_bytes_flags(self.jcap, SK_BGZF_SEARCH if search else 0)
+                self.jimg = [alloc(self.jimg_cap) for _ in range(2)]
+                self.jzws = [alloc(self.jzws_bytes) for _ in range(2)]
         self._gen = self._run()
 
     def __iter__(self):
@@ -1892,6 +2027,15 @@ class FastqStream:
         if self._bas:  # likewise
             c._bases_behind(self._bas, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
                             self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
+        if self._rej:  # likewise, into the slot's own workspace and text buffer (and through its words into the writer)
+            c._rejects_behind(self.jws[slot], FastqOutput(self.jout[slot].data_ptr(), self.jcap, None, 0), self._rej_flags,
+                              self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
+                              self.params.trunc_n, self.mode, "piece", self.order, self.stream)
+            if self.gz:
+                b, w = c.trim_fastq_rejects_output_words(self.jws[slot].data_ptr())
+                c.bgzf_device_async(self.jout[slot].data_ptr(), self.jcap, self.jimg[slot].data_ptr(), self.jimg_cap,
+                                    self.jzws[slot].data_ptr(), self.jzws_bytes, eof=not more, bytes_dev_ptr=b,
+                                    valid_dev_ptr=w, stream=self.stream, search=self.search)
         if self.gz:
             for o in self.used:
                 b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
@@ -1959,6 +2103,15 @@ class FastqStream:
         # what the piece consumed of each input: what it was handed (the carry before it and its chunk) less what it carried
         self._known = (p["k"], carried, [a + b - c for a, b, c in zip(self._carried_in, p["taken"], carried)])
         self._carried_in = carried
+        if self._rej:
+            got = c.trim_fastq_rejects_device_finish(self.jws[slot].data_ptr(), self.stream)
+            if self.gz:
+                n = c.bgzf_device_finish(self.jzws[slot].data_ptr(), self.stream)["bytes_out"]
+                res.append(self.jimg[slot][:n].cpu().numpy().tobytes())
+            else:
+                res.append(self.jout[slot][:got["bytes"]].cpu().numpy().tobytes())
+            self._rej_sum["records"] += got["records"]
+            self._rej_sum["bytes"] += got["bytes"]
         return tuple(res)
 
     def _raw_finish(self, slot):
@@ -1970,7 +2123,7 @@ class FastqStream:
         """what closes the outputs when the run ended in a piece that was not a closing one"""
         if not self.gz or not last["more"]:
             return []
-        return [tuple(BGZF_EOF_MEMBER if o in self.used else None for o in range(3))]
+        return [tuple(BGZF_EOF_MEMBER if o in self.used else None for o in range(3)) + ((BGZF_EOF_MEMBER,) if self._rej else ())]
 
     def _estimate(self, last):
         """bytes each input carries into the piece behind piece `last` (enqueued): what the last finished piece carried,
@@ -1989,6 +2142,8 @@ class FastqStream:
             self.audit = self._aud.read()
         if self._bas:
             self.bases = self._bas.read()
+        if self._rej:
+            self.rejects = dict(self._rej_sum)
 
     def _run_pieces(self):
         self._reads, self._bounds, self._carried_in, self._known = 0, [0, 0], [0, 0], (-1, [0, 0], [0, 0])

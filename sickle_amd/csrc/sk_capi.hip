@@ -15,6 +15,7 @@
 #include "sickle_amd.h"
 #include "sk_device.h"
 #include "sk_fastq_order.h"
+#include "sk_fastq_rejects.h"
 
 static_assert(sizeof(sk_tile) == sizeof(sk_tile_dev) && sizeof(sk_tile) == 24, "sk_tile layout");
 
@@ -1411,6 +1412,76 @@ int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *
 #undef SK_FQB_BAD
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_bases(src, in, mode, bases_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+size_t sk_trim_fastq_rejects_workspace_bytes(uint64_t text_bytes) { return (size_t)fqj_workspace_bytes(text_bytes); }
+
+uint64_t sk_trim_fastq_rejects_bound(uint64_t text_bytes) { return fqj_bound(text_bytes); }
+
+// every check before the first HIP call: bad arguments enqueue nothing and need no device
+int sk_trim_fastq_rejects_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                       const sk_fastq_output *out, int flags, void *workspace, size_t workspace_bytes,
+                                       void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+#define SK_FQJ_BAD(...)               \
+    do {                              \
+        set_error(ctx, __VA_ARGS__); \
+        return SK_EINVAL;             \
+    } while (0)
+    if (!src || !src->workspace || !in || !workspace) SK_FQJ_BAD("rejects: src, src->workspace, in and workspace are required");
+    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQJ_BAD("rejects: src->workspace must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) SK_FQJ_BAD("rejects: workspace must be 16-byte aligned");
+    if (out && (reinterpret_cast<uintptr_t>(out->text) & 15)) SK_FQJ_BAD("rejects: out->text must be 16-byte aligned");
+    if (out && (reinterpret_cast<uintptr_t>(out->record_index) & 7)) SK_FQJ_BAD("rejects: out->record_index must be 8-byte aligned");
+    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQJ_BAD("rejects: source kind %u is unknown", src->kind);
+    if (src->reserved != 0) SK_FQJ_BAD("rejects: src->reserved must be 0");
+    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQJ_BAD("rejects: mode %d is unknown", mode);
+    if (flags & ~SK_FQ_REJECTS_PAIRS) SK_FQJ_BAD("rejects: flags %d are unknown", flags);
+    if ((flags & SK_FQ_REJECTS_PAIRS) && mode == SK_TRIM_SE) SK_FQJ_BAD("rejects: SK_FQ_REJECTS_PAIRS needs a pair mode");
+    if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQJ_BAD("rejects: SK_TRIM_PE_SPLIT needs text[1]");
+    if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQJ_BAD("rejects: text[1] is for SK_TRIM_PE_SPLIT only");
+    if (!in->text[0] && in->bytes[0]) SK_FQJ_BAD("rejects: text[0] is NULL with bytes[0] != 0");
+    if (!in->text[1] && in->bytes[1]) SK_FQJ_BAD("rejects: text[1] is NULL with bytes[1] != 0");
+    if (src->text_bytes > (1ull << 35)) SK_FQJ_BAD("rejects: %llu bytes of text is beyond what a text call takes", (unsigned long long)src->text_bytes);
+    const size_t need = sk_trim_fastq_rejects_workspace_bytes(src->text_bytes);
+    if (workspace_bytes < need)
+        SK_FQJ_BAD("rejects: workspace must hold sk_trim_fastq_rejects_workspace_bytes(%llu) = %zu bytes",
+                   (unsigned long long)src->text_bytes, need);
+#undef SK_FQJ_BAD
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_rejects(src, in, mode, out, flags, workspace, ctx->cu_count, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+int sk_trim_fastq_rejects_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_rejects_counts *counts)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t h[FQJ_HDR_WORDS];
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    counts->records = h[FQJ_H_RECORDS];
+    counts->bytes = h[FQJ_H_BYTES];
+    counts->reads = h[FQJ_H_READS];
+    counts->valid = (uint32_t)h[FQJ_H_VALID];
+    counts->flags = (uint32_t)h[FQJ_H_FLAGS];
+    if (h[FQJ_H_VALID] && h[FQJ_H_PRODUCED] && !h[FQJ_H_WRITTEN]) {
+        set_error(ctx, "rejects: the text needs %llu bytes and %llu records, more than a capacity",
+                  (unsigned long long)counts->bytes, (unsigned long long)counts->records);
+        return SK_ESPACE;
+    }
+    return SK_OK;
+}
+
+int sk_trim_fastq_rejects_output_words(void *rejects_workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)
+{
+    if (!rejects_workspace || !bytes_dev || !written_dev) return SK_EINVAL;
+    const uint64_t *hdr = static_cast<const uint64_t *>(rejects_workspace);
+    *bytes_dev = hdr + FQJ_H_OUT_BYTES;
+    *written_dev = hdr + FQJ_H_WRITTEN;
     return SK_OK;
 }
 

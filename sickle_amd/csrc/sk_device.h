@@ -451,6 +451,13 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_base
                                                                                   sk_fastq_bases *bases_dev,
                                                                                   const sk_fastq_bases_hists *hists, int flags,
                                                                                   hipStream_t stream);
+// the rejects text over a text call's workspace and texts (sk_fastq_rejects.hip); the arguments have passed the checks of
+// sk_trim_fastq_rejects_device_async
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_rejects(const sk_fastq_report_source *src,
+                                                                                    const sk_fastq_input *in, int mode,
+                                                                                    const sk_fastq_output *out, int flags,
+                                                                                    void *workspace, int cu_count,
+                                                                                    hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif
