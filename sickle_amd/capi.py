@@ -709,6 +709,46 @@ def _np_ptr(a):
     return None if a is None else a.ctypes.data
 
 
+# ---- the structs of the FASTQ text calls, from the one or two entries per input the wrappers take --------------------------
+def _two(xs, fill):
+    return list(xs) + [fill] * (2 - len(xs))
+
+
+def _fastq_input(text_ptrs, text_bytes, max_read_len=0):
+    return FastqInput((C.c_void_p * 2)(*_two(text_ptrs, None)), (C.c_uint64 * 2)(*_two(text_bytes, 0)), max_read_len)
+
+
+def _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs):
+    return FastqLengths((C.c_void_p * 2)(*_two(bytes_dev_ptrs, None)), (C.c_void_p * 2)(*_two(valid_dev_ptrs, None)))
+
+
+def _fastq_piece(start_dev_ptrs, more):
+    return FastqPiece((C.c_void_p * 2)(*_two(start_dev_ptrs, None)), 1 if more else 0, 0)
+
+
+def _fastq_outputs(outs):
+    return (FastqOutput * 3)(*list(outs)[:3])
+
+
+def _report_source(workspace_ptr, kind, trunc_n, text_bytes, batch_capacity):
+    return FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+
+
+def _source_kind(kind, order):
+    """kind ("plain" or "piece") and order (a FastqOrder or None) of a driver's text call -> the kind and batch_capacity
+    of the sk_fastq_report_source over its workspace"""
+    if order is None:
+        return kind, 0
+    return {"plain": "ordered", "piece": "ordered_piece"}[kind], order.batch_capacity
+
+
+def _fastq_ws_bytes(sizes, trunc_n, order):
+    """the workspace of a whole-text call on texts of these sizes; order: a FastqOrder or None"""
+    if order is None:
+        return lib().sk_trim_fastq_workspace_bytes(sum(sizes), trunc_n)
+    return lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), trunc_n, order.batch_capacity)
+
+
 class Context:
     """One sk_ctx.  Raises SickleError when no gfx950 device is usable."""
 
@@ -736,6 +776,20 @@ class Context:
         if rc == SK_ERANGE:
             raise RangeError(err.read, err.pos, err.ch)
         raise SickleError("libsickle_amd call failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()))
+
+    def _check_fastq(self, rc, c, counts, record_base=0, read_base=0):
+        """the rc of a text call's finish: LongLineError, FormatError, RangeError, TrimError (SK_ESPACE) or _check's.  c: its
+        FastqCounts; counts: the dict the exception carries; record_base, read_base: what makes a piece's record and read
+        numbers the stream's"""
+        if rc == SK_ELONGLINE:
+            raise LongLineError(counts["order"]["long_line_input"], counts["order"]["long_line"], counts)
+        if rc == SK_EFORMAT:
+            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record) + record_base, counts)
+        if rc == SK_ERANGE:
+            raise RangeError(int(c.range.read) + read_base, int(c.range.pos), int(c.range.ch))
+        if rc == SK_ESPACE:
+            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
+        self._check(rc)
 
     # ---- host buffers (numpy) -------------------------------------------------------------
     def trim_segmented(self, params, qual, tiles, out_index, max_stride, seq=None, slot_order=False):
@@ -885,22 +939,17 @@ class Context:
                                 max_read_len=0, stream=None):
         """sk_trim_fastq_device_async on raw device pointers; text_ptrs / text_bytes: one or two entries, outs: up to
         three FastqOutput (missing ones are not produced)."""
-        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bytes) + [0] * (2 - len(text_bytes))
-        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
-        arr = (FastqOutput * 3)(*list(outs)[:3])
+        inp = _fastq_input(text_ptrs, text_bytes, max_read_len)
         self._check(lib().sk_trim_fastq_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
-                                                     arr, workspace_ptr, workspace_bytes, stream))
+                                                     _fastq_outputs(outs), workspace_ptr, workspace_bytes, stream))
 
     def trim_fastq_device_finish(self, workspace_ptr, stream=None):
         """sk_trim_fastq_device_finish -> counts (dict); raises FormatError, RangeError or TrimError (SK_ESPACE)."""
         c = FastqCounts()
         rc = lib().sk_trim_fastq_device_finish(self._h, workspace_ptr, stream, C.byref(c))
-        if rc == SK_EFORMAT:
-            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), c.as_dict())
-        if rc == SK_ESPACE:
-            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, c.as_dict())
-        self._check(rc, c.range)
-        return c.as_dict()
+        counts = c.as_dict()
+        self._check_fastq(rc, c, counts)
+        return counts
 
     def trim_fastq_report_device_async(self, workspace_ptr, text_bytes, trunc_n, report_ptr, kind="plain", batch_capacity=0,
                                        hists=None, reset=False, stream=None):
@@ -908,7 +957,7 @@ class Context:
         enqueued on `stream`.  kind: "plain", "piece", "ordered" or "ordered_piece" (or SK_FQ_REPORT_*); text_bytes,
         trunc_n, batch_capacity: what that call's workspace formula took; report_ptr: a sk_fastq_report in device memory;
         hists: a FastqReportHists or None.  Only enqueues."""
-        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
+        src = _report_source(workspace_ptr, kind, trunc_n, text_bytes, batch_capacity)
         self._check(lib().sk_trim_fastq_report_device_async(self._h, C.byref(src), report_ptr,
                                                             C.byref(hists) if hists is not None else None,
                                                             SK_FQ_REPORT_RESET if reset else 0, stream))
@@ -919,11 +968,8 @@ class Context:
         call already enqueued on `stream`.  kind, text_bytes, trunc_n, batch_capacity: as trim_fastq_report_device_async's;
         text_ptrs, text_bounds: the text call's (None: in == NULL, the names are not looked at); mode: the text call's;
         audit_ptr: a sk_fastq_audit in device memory; qual_hist_ptr: 256 uint64 in device memory or None.  Only enqueues."""
-        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
-        inp = None
-        if text_ptrs is not None:
-            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
-            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        src = _report_source(workspace_ptr, kind, trunc_n, text_bytes, batch_capacity)
+        inp = None if text_ptrs is None else C.byref(_fastq_input(text_ptrs, text_bounds))
         self._check(lib().sk_trim_fastq_audit_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode), audit_ptr,
                                                            qual_hist_ptr, SK_FQ_AUDIT_RESET if reset else 0, stream))
 
@@ -933,11 +979,8 @@ class Context:
         call already enqueued on `stream`.  kind, text_bytes, trunc_n, batch_capacity: as trim_fastq_report_device_async's;
         text_ptrs, text_bounds, mode: the text call's (text_ptrs None: in == NULL, which is refused: the texts are the
         data); bases_ptr: a sk_fastq_bases in device memory; hists: a FastqBasesHists or None.  Only enqueues."""
-        src = FastqReportSource(workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
-        inp = None
-        if text_ptrs is not None:
-            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
-            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        src = _report_source(workspace_ptr, kind, trunc_n, text_bytes, batch_capacity)
+        inp = None if text_ptrs is None else C.byref(_fastq_input(text_ptrs, text_bounds))
         self._check(lib().sk_trim_fastq_bases_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode), bases_ptr,
                                                            C.byref(hists) if hists is not None else None,
                                                            SK_FQ_BASES_RESET if reset else 0, stream))
@@ -950,11 +993,8 @@ class Context:
         FastqOutput or None (the call only counts); workspace_ptr, workspace_bytes: the rejects call's own workspace
         (sk_trim_fastq_rejects_workspace_bytes(text_bytes)); pairs: SK_FQ_REJECTS_PAIRS (or the flags as an int).
         Only enqueues."""
-        src = FastqReportSource(src_workspace_ptr, REPORT_KINDS.get(kind, kind), int(trunc_n), text_bytes, batch_capacity, 0)
-        inp = None
-        if text_ptrs is not None:
-            pad = lambda v, fill: (list(v) + [fill, fill])[:2]
-            inp = C.byref(FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), 0))
+        src = _report_source(src_workspace_ptr, kind, trunc_n, text_bytes, batch_capacity)
+        inp = None if text_ptrs is None else C.byref(_fastq_input(text_ptrs, text_bounds))
         flags = pairs if isinstance(pairs, int) and not isinstance(pairs, bool) else (SK_FQ_REJECTS_PAIRS if pairs else 0)
         self._check(lib().sk_trim_fastq_rejects_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode),
                                                              C.byref(out) if out is not None else None, flags, workspace_ptr,
@@ -983,11 +1023,10 @@ class Context:
                                         mode="se", max_read_len=0, stream=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
         trim_fastq_device_async."""
-        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bytes) + [0] * (2 - len(text_bytes))
-        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
-        arr = (FastqOutput * 3)(*list(outs)[:3])
+        inp = _fastq_input(text_ptrs, text_bytes, max_read_len)
         self._check(lib().sk_trim_fastq_ordered_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
-                                                             C.byref(order), arr, workspace_ptr, workspace_bytes, stream))
+                                                             C.byref(order), _fastq_outputs(outs), workspace_ptr,
+                                                             workspace_bytes, stream))
 
     def trim_fastq_ordered_device_finish(self, workspace_ptr, stream=None):
         """sk_trim_fastq_ordered_device_finish -> counts (dict, with the order counts under "order"); raises
@@ -996,13 +1035,7 @@ class Context:
         c, oc = FastqCounts(), FastqOrderCounts()
         rc = lib().sk_trim_fastq_ordered_device_finish(self._h, workspace_ptr, stream, C.byref(c), C.byref(oc))
         counts = dict(c.as_dict(), order=oc.as_dict())
-        if rc == SK_ELONGLINE:
-            raise LongLineError(int(oc.long_line_input), int(oc.long_line), counts)
-        if rc == SK_EFORMAT:
-            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
-        if rc == SK_ESPACE:
-            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
-        self._check(rc, c.range)
+        self._check_fastq(rc, c, counts)
         return counts
 
     def trim_fastq_chained_device_async(self, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes,
@@ -1012,14 +1045,10 @@ class Context:
         bytes_dev_ptrs / valid_dev_ptrs (up to two entries each, None = not given) the device words that hold the lengths
         and their validity, e.g. those of bgzf_inflate_output_words.  order: a FastqOrder or None (read order); the
         workspace and the finish are those of trim_fastq_ordered_device_async / trim_fastq_device_async accordingly."""
-        tp, tb = list(text_ptrs) + [None] * (2 - len(text_ptrs)), list(text_bounds) + [0] * (2 - len(text_bounds))
-        bd, vd = list(bytes_dev_ptrs) + [None] * (2 - len(bytes_dev_ptrs)), list(valid_dev_ptrs) + [None] * (2 - len(valid_dev_ptrs))
-        inp = FastqInput((C.c_void_p * 2)(*tp), (C.c_uint64 * 2)(*tb), max_read_len)
-        lengths = FastqLengths((C.c_void_p * 2)(*bd), (C.c_void_p * 2)(*vd))
-        arr = (FastqOutput * 3)(*list(outs)[:3])
+        inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
         self._check(lib().sk_trim_fastq_chained_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
                                                              TRIM_MODES.get(mode, mode),
-                                                             None if order is None else C.byref(order), arr,
+                                                             None if order is None else C.byref(order), _fastq_outputs(outs),
                                                              workspace_ptr, workspace_bytes, stream))
 
     # ---- FASTQ text in pieces ------------------------------------------------------------------
@@ -1029,14 +1058,11 @@ class Context:
         """sk_trim_fastq_piece_device_async on raw device pointers: trim_fastq_chained_device_async (read order) on the
         window that starts at the device words start_dev_ptrs (None = 0); more: more text follows, so only whole records
         (pairs) are taken and the rest is the carry.  piece=False passes piece == NULL: the chained call itself."""
-        pad = lambda xs, fill: list(xs) + [fill] * (2 - len(xs))
-        inp = FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), max_read_len)
-        lengths = FastqLengths((C.c_void_p * 2)(*pad(bytes_dev_ptrs, None)), (C.c_void_p * 2)(*pad(valid_dev_ptrs, None)))
-        pc = FastqPiece((C.c_void_p * 2)(*pad(start_dev_ptrs, None)), 1 if more else 0, 0)
-        arr = (FastqOutput * 3)(*list(outs)[:3])
+        inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
+        pc = _fastq_piece(start_dev_ptrs, more)
         self._check(lib().sk_trim_fastq_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
-                                                           C.byref(pc) if piece else None, TRIM_MODES.get(mode, mode), arr,
-                                                           workspace_ptr, workspace_bytes, stream))
+                                                           C.byref(pc) if piece else None, TRIM_MODES.get(mode, mode),
+                                                           _fastq_outputs(outs), workspace_ptr, workspace_bytes, stream))
 
     def _piece_finish(self, workspace_ptr, stream):
         c, pc = FastqCounts(), FastqPieceCounts()
@@ -1047,11 +1073,7 @@ class Context:
         """sk_trim_fastq_piece_device_finish -> counts (dict, with the piece counts under "piece"); raises FormatError,
         RangeError (an inherited one too: counts["piece"]["inherited_range"] is not seen then) or TrimError (SK_ESPACE)."""
         rc, c, counts = self._piece_finish(workspace_ptr, stream)
-        if rc == SK_EFORMAT:
-            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
-        if rc == SK_ESPACE:
-            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
-        self._check(rc, c.range)
+        self._check_fastq(rc, c, counts)
         return counts
 
     def trim_fastq_ordered_piece_device_async(self, params, text_ptrs, text_bounds, order, state_in_ptr, state_out_ptr, outs,
@@ -1060,15 +1082,12 @@ class Context:
         """sk_trim_fastq_ordered_piece_device_async on raw device pointers: trim_fastq_piece_device_async whose records are
         the batches the piece can commit, in the -a T order.  order: a FastqOrder; state_in_ptr (None: the start of a
         stream) and state_out_ptr: FastqOrderState in device memory."""
-        pad = lambda xs, fill: list(xs) + [fill] * (2 - len(xs))
-        inp = FastqInput((C.c_void_p * 2)(*pad(text_ptrs, None)), (C.c_uint64 * 2)(*pad(text_bounds, 0)), max_read_len)
-        lengths = FastqLengths((C.c_void_p * 2)(*pad(bytes_dev_ptrs, None)), (C.c_void_p * 2)(*pad(valid_dev_ptrs, None)))
-        pc = FastqPiece((C.c_void_p * 2)(*pad(start_dev_ptrs, None)), 1 if more else 0, 0)
-        arr = (FastqOutput * 3)(*list(outs)[:3])
+        inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
+        pc = _fastq_piece(start_dev_ptrs, more)
         self._check(lib().sk_trim_fastq_ordered_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
                                                                    C.byref(pc), C.byref(order), state_in_ptr, state_out_ptr,
-                                                                   TRIM_MODES.get(mode, mode), arr, workspace_ptr,
-                                                                   workspace_bytes, stream))
+                                                                   TRIM_MODES.get(mode, mode), _fastq_outputs(outs),
+                                                                   workspace_ptr, workspace_bytes, stream))
 
     def _ordered_piece_finish(self, workspace_ptr, stream):
         c, oc, pc, opc = FastqCounts(), FastqOrderCounts(), FastqPieceCounts(), FastqOrderPieceCounts()
@@ -1080,13 +1099,7 @@ class Context:
         """sk_trim_fastq_ordered_piece_device_finish -> counts (dict, with "order", "piece" and "order_piece"); raises
         LongLineError, FormatError, RangeError (an inherited one too) or TrimError (SK_ESPACE: an output)."""
         rc, c, counts = self._ordered_piece_finish(workspace_ptr, stream)
-        if rc == SK_ELONGLINE:
-            raise LongLineError(counts["order"]["long_line_input"], counts["order"]["long_line"], counts)
-        if rc == SK_EFORMAT:
-            raise FormatError(int(c.format_error), int(c.format_input), int(c.format_record), counts)
-        if rc == SK_ESPACE:
-            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(self._h).decode()), rc, counts)
-        self._check(rc, c.range)
+        self._check_fastq(rc, c, counts)
         return counts
 
     @staticmethod
@@ -1252,38 +1265,34 @@ class Context:
                                                                                   rejects))
         return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects)
 
-    def _audit_behind(self, aud, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
-        """the audit of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has no
-        pointer and no records: the names are then not looked at)"""
-        if any(p is None for p in ptrs):
-            ptrs = None
-        self.trim_fastq_audit_device_async(ws_ptr, sum(bounds), trunc_n, aud.ptr, text_ptrs=ptrs, text_bounds=bounds, mode=mode,
-                                           kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
-                                           batch_capacity=order.batch_capacity if order is not None else 0,
-                                           qual_hist_ptr=aud.hist_ptr, reset=reset, stream=stream)
-
-    def _bases_behind(self, bas, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream):
-        """the bases of a driver's text call: behind it on its stream, over its workspace and its texts (an empty text has
-        no pointer: it gets the struct's own address with the bound 0, of which no byte is loaded)"""
+    def _enqueue_behind(self, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream, rep=None, aud=None, bas=None,
+                        rej=None):
+        """What follows a driver's text call on its stream, over its workspace and its texts: the report, the audit, the
+        bases, then the rejects, each where its buffers are given (rep, aud, bas: the drivers' buffer objects; rej: the
+        rejects call's workspace tensor, its FastqOutput or None, its flags).  kind: "plain" or "piece"; order: the text
+        call's FastqOrder or None; reset: zero what accumulates (not the rejects, which do not).  The audit does without the
+        names when a text is empty (no pointer); the bases and the rejects, which need `in`, give an empty text their own
+        buffer's address with the bound 0, of which no byte is loaded."""
+        kind, cap = _source_kind(kind, order)
         total = sum(bounds)
-        bounds = [0 if p is None else b for p, b in zip(ptrs, bounds)]
-        ptrs = [bas.ptr if p is None else p for p in ptrs]
-        self.trim_fastq_bases_device_async(ws_ptr, total, trunc_n, bas.ptr, ptrs, bounds, mode=mode,
-                                           kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
-                                           batch_capacity=order.batch_capacity if order is not None else 0,
-                                           hists=bas.hists, reset=reset, stream=stream)
-
-    def _rejects_behind(self, rws, out, flags, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, stream):
-        """the rejects of a driver's text call: behind it on its stream, over its workspace and its texts, into the
-        workspace rws (an empty text has no pointer: it gets rws's own address with the bound 0, of which no byte is
-        loaded)"""
-        total = sum(bounds)
-        bounds = [0 if p is None else b for p, b in zip(ptrs, bounds)]
-        ptrs = [rws.data_ptr() if p is None else p for p in ptrs]
-        self.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, ptrs, bounds, out, rws.data_ptr(), rws.numel(), mode=mode,
-                                             kind=kind if order is None else {"plain": "ordered", "piece": "ordered_piece"}[kind],
-                                             batch_capacity=order.batch_capacity if order is not None else 0, pairs=flags,
-                                             stream=stream)
+        own = lambda ptr: ([ptr if p is None else p for p in ptrs], [0 if p is None else b for p, b in zip(ptrs, bounds)])
+        if rep:
+            self.trim_fastq_report_device_async(ws_ptr, total, trunc_n, rep.ptr, kind=kind, batch_capacity=cap, hists=rep.hists,
+                                                reset=reset, stream=stream)
+        if aud:
+            self.trim_fastq_audit_device_async(ws_ptr, total, trunc_n, aud.ptr,
+                                               text_ptrs=None if any(p is None for p in ptrs) else ptrs, text_bounds=bounds,
+                                               mode=mode, kind=kind, batch_capacity=cap, qual_hist_ptr=aud.hist_ptr, reset=reset,
+                                               stream=stream)
+        if bas:
+            p, b = own(bas.ptr)
+            self.trim_fastq_bases_device_async(ws_ptr, total, trunc_n, bas.ptr, p, b, mode=mode, kind=kind, batch_capacity=cap,
+                                               hists=bas.hists, reset=reset, stream=stream)
+        if rej:
+            rws, out, flags = rej
+            p, b = own(rws.data_ptr())
+            self.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, p, b, out, rws.data_ptr(), rws.numel(), mode=mode,
+                                                 kind=kind, batch_capacity=cap, pairs=flags, stream=stream)
 
     def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False,
                     rejects=False):
@@ -1292,38 +1301,29 @@ class Context:
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if order is None:
-            ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
-        else:
-            ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         rep = _ReportBuffers(report, dev) if report else None
-        # the report goes behind the writing pass's emission and in front of its finish, which is the wait
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
-        tell = lambda final: final and (rep and self.trim_fastq_report_device_async(
-            ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr, kind="plain" if order is None else "ordered",
-            batch_capacity=order.batch_capacity if order is not None else 0, hists=rep.hists, reset=True, stream=stream),
-            aud and self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream),
-            bas and self._bases_behind(bas, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream))
-        # the rejects: a counting call behind the counting pass, the writing one behind the writing pass
         rej_out = [None]
         if rejects:
             rej_flags = _rejects_flags(rejects)
             rws = torch.empty(lib().sk_trim_fastq_rejects_workspace_bytes(sum(sizes)), dtype=torch.uint8, device=dev)
-            spill = lambda: self._rejects_behind(rws, rej_out[0], rej_flags, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode,
-                                                 "plain", order, stream)
-        else:
-            spill = lambda: None
-        if order is None:
-            run = lambda outs, final=False: (self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes,
-                                                                          mode=mode, max_read_len=max_read_len, stream=stream),
-                                             tell(final), spill(), self.trim_fastq_device_finish(ws.data_ptr(), stream))[3]
-        else:
-            run = lambda outs, final=False: (self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(),
-                                                                                  ws_bytes, mode=mode, max_read_len=max_read_len,
-                                                                                  stream=stream),
-                                             tell(final), spill(), self.trim_fastq_ordered_device_finish(ws.data_ptr(), stream))[3]
+
+        def run(outs, final=False):
+            if order is None:
+                self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                             max_read_len=max_read_len, stream=stream)
+            else:
+                self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
+                                                     max_read_len=max_read_len, stream=stream)
+            # the report, the audit and the bases go behind the writing pass's emission and in front of its finish, which
+            # is the wait; the rejects: a counting call behind the counting pass, the writing one behind the writing pass
+            self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream,
+                                 rep=final and rep, aud=final and aud, bas=final and bas,
+                                 rej=(rws, rej_out[0], rej_flags) if rejects else None)
+            return (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
         counts = run([FastqOutput() for _ in range(3)])
         if rejects:
             need = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
@@ -1410,10 +1410,7 @@ class Context:
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if order is None:
-            ws_bytes = lib().sk_trim_fastq_workspace_bytes(sum(sizes), params.trunc_n)
-        else:
-            ws_bytes = lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), params.trunc_n, order.batch_capacity)
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = TRIM_OUTPUTS[mode]
         cap = fastq_output_bound(sum(sizes), mode)
@@ -1430,17 +1427,9 @@ class Context:
             self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
                                                  max_read_len=max_read_len, stream=stream)
         rep = _ReportBuffers(report, dev) if report else None
-        if rep:
-            self.trim_fastq_report_device_async(ws.data_ptr(), sum(sizes), params.trunc_n, rep.ptr,
-                                                kind="plain" if order is None else "ordered",
-                                                batch_capacity=order.batch_capacity if order is not None else 0,
-                                                hists=rep.hists, reset=True, stream=stream)
         aud = _AuditBuffers(dev) if audit else None
-        if aud:
-            self._audit_behind(aud, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream)
         bas = _BasesBuffers(bases, dev) if bases else None
-        if bas:
-            self._bases_behind(bas, ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream)
+        self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream, rep, aud, bas)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1646,10 +1635,7 @@ class Context:
             readers.append((fin, rws))
             nbytes.append(b)
             valid.append(w)
-        if order is None:
-            ws_bytes = L.sk_trim_fastq_workspace_bytes(sum(capacities), params.trunc_n)
-        else:
-            ws_bytes = L.sk_trim_fastq_ordered_workspace_bytes(sum(capacities), params.trunc_n, order.batch_capacity)
+        ws_bytes = _fastq_ws_bytes(capacities, params.trunc_n, order)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = TRIM_OUTPUTS[mode]
         cap = fastq_output_bound(sum(capacities), mode)
@@ -1663,19 +1649,10 @@ class Context:
                                              bytes_dev_ptrs=nbytes, valid_dev_ptrs=valid, mode=mode, order=order,
                                              max_read_len=max_read_len, stream=stream)
         rep = _ReportBuffers(report, dev) if report else None
-        if rep:
-            self.trim_fastq_report_device_async(ws.data_ptr(), sum(capacities), params.trunc_n, rep.ptr,
-                                                kind="plain" if order is None else "ordered",
-                                                batch_capacity=order.batch_capacity if order is not None else 0,
-                                                hists=rep.hists, reset=True, stream=stream)
         aud = _AuditBuffers(dev) if audit else None
-        if aud:
-            self._audit_behind(aud, ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order,
-                               True, stream)
         bas = _BasesBuffers(bases, dev) if bases else None
-        if bas:
-            self._bases_behind(bas, ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order,
-                               True, stream)
+        self._enqueue_behind(ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order, True,
+                             stream, rep, aud, bas)
         for o in used:
             out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -2015,27 +1992,19 @@ class FastqStream:
                                                     self.order, self.states[k & 1].data_ptr(),
                                                     self.states[(k + 1) & 1].data_ptr(), outs, self.ws[slot].data_ptr(),
                                                     self.ws_bytes, **words)
-        if self._rep:  # behind the piece's emission; the report is zeroed in front of the first piece only
-            # (the piece's sections lie where ITS bounds put them, which a short chunk makes less than the workspace's)
-            c.trim_fastq_report_device_async(self.ws[slot].data_ptr(), sum(bounds), self.params.trunc_n, self._rep.ptr,
-                                             kind="piece" if self.order is None else "ordered_piece",
-                                             batch_capacity=self.order.batch_capacity if self.order is not None else 0,
-                                             hists=self._rep.hists, reset=k == 0, stream=self.stream)
-        if self._aud:  # likewise; the piece's text buffers are the slot's, which piece k + 2 fills again behind this call
-            c._audit_behind(self._aud, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
-                            self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
-        if self._bas:  # likewise
-            c._bases_behind(self._bas, self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
-                            self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream)
-        if self._rej:  # likewise, into the slot's own workspace and text buffer (and through its words into the writer)
-            c._rejects_behind(self.jws[slot], FastqOutput(self.jout[slot].data_ptr(), self.jcap, None, 0), self._rej_flags,
-                              self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
-                              self.params.trunc_n, self.mode, "piece", self.order, self.stream)
-            if self.gz:
-                b, w = c.trim_fastq_rejects_output_words(self.jws[slot].data_ptr())
-                c.bgzf_device_async(self.jout[slot].data_ptr(), self.jcap, self.jimg[slot].data_ptr(), self.jimg_cap,
-                                    self.jzws[slot].data_ptr(), self.jzws_bytes, eof=not more, bytes_dev_ptr=b,
-                                    valid_dev_ptr=w, stream=self.stream, search=self.search)
+        # Behind the piece's emission, over its workspace (whose sections lie where ITS bounds put them, which a short chunk
+        # makes less than the workspace's) and the slot's text buffers, which piece k + 2 fills again behind these calls.
+        # What accumulates is zeroed in front of the first piece only; the rejects go into the slot's own workspace and text
+        # buffer (and through its words into the writer).
+        rej = (self.jws[slot], FastqOutput(self.jout[slot].data_ptr(), self.jcap, None, 0), self._rej_flags) if self._rej else None
+        c._enqueue_behind(self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
+                          self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream, self._rep, self._aud,
+                          self._bas, rej)
+        if self._rej and self.gz:
+            b, w = c.trim_fastq_rejects_output_words(self.jws[slot].data_ptr())
+            c.bgzf_device_async(self.jout[slot].data_ptr(), self.jcap, self.jimg[slot].data_ptr(), self.jimg_cap,
+                                self.jzws[slot].data_ptr(), self.jzws_bytes, eof=not more, bytes_dev_ptr=b, valid_dev_ptr=w,
+                                stream=self.stream, search=self.search)
         if self.gz:
             for o in self.used:
                 b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
@@ -2065,16 +2034,8 @@ class FastqStream:
                             SK_ESPACE, counts)
         base_reads = self._reads
         per_input = base_reads // 2 if self.mode == "pe_split" else base_reads
-        if rc == SK_ELONGLINE:
-            raise LongLineError(counts["order"]["long_line_input"], counts["order"]["long_line"], counts)
-        if rc == SK_EFORMAT:
-            raise FormatError(int(raw.format_error), int(raw.format_input), int(raw.format_record) + per_input, counts)
-        if rc == SK_ERANGE:
-            raise RangeError(int(raw.range.read) + (0 if counts["piece"]["inherited_range"] else base_reads),
-                             int(raw.range.pos), int(raw.range.ch))
-        if rc == SK_ESPACE:
-            raise TrimError("fastq trim failed (%d): %s" % (rc, lib().sk_last_error(c._h).decode()), rc, counts)
-        c._check(rc)
+        # stream-wide numbers: the records and reads before the piece (an inherited range error keeps its call's read number)
+        c._check_fastq(rc, raw, counts, record_base=per_input, read_base=0 if counts["piece"]["inherited_range"] else base_reads)
         if any(status):
             raise SickleError("fastq stream: piece %d follows a failed carry (status %r)" % (p["k"], status))
         res = [None] * 3

@@ -14,8 +14,9 @@
 
 #include "sickle_amd.h"
 #include "sk_device.h"
-#include "sk_fastq_order.h"
 #include "sk_fastq_rejects.h"
+#include "sk_fastq_verdict.h"
+#include "sk_gunzip_block.h"
 
 static_assert(sizeof(sk_tile) == sizeof(sk_tile_dev) && sizeof(sk_tile) == 24, "sk_tile layout");
 
@@ -120,6 +121,22 @@ void set_error(sk_ctx *ctx, const char *fmt, ...)
             return SK_EHIP;                                                                    \
         }                                                                                      \
     } while (0)
+
+// the message and SK_EINVAL: a bad argument (nothing is enqueued behind it), or a finish that found one on the device
+#define SK_BAD(ctx, ...)               \
+    do {                               \
+        set_error((ctx), __VA_ARGS__); \
+        return SK_EINVAL;              \
+    } while (0)
+
+               // how the finishes that take everything from a workspace's header begin: its first `words` words, waited for
+               int read_header(sk_ctx *ctx, const void *workspace, uint64_t *h, size_t words, hipStream_t stream)
+               {
+               SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, words * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    return SK_OK;
+}
 
 bool tile_eligible(const sk_batch *b);
 
@@ -380,17 +397,6 @@ int reset_error_word(sk_ctx *ctx, unsigned long long *d_err, hipStream_t stream)
 {
     SK_HIP(ctx, hipMemsetAsync(d_err, 0xff, sizeof(unsigned long long), stream));
     return SK_OK;
-}
-
-int decode_error(unsigned long long word, sk_err *err)
-{
-    if (word == kNoError) return SK_OK;
-    if (err) {
-        err->read = (uint32_t)(word >> 32);
-        err->pos = (uint32_t)((word >> 8) & 0xffffffu);
-        err->ch = (int32_t)(int8_t)(word & 0xff);
-    }
-    return SK_ERANGE;
 }
 
 size_t batch_bytes(const sk_batch *b)
@@ -693,38 +699,32 @@ size_t sk_trim_workspace_bytes(uint64_t n_reads)
 int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts, int mode, const sk_trim_output out[3],
                          void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-#define SK_TRIM_BAD(...)              \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!batch || !out) SK_TRIM_BAD("sk_trim_device_async: batch and out are required");
+    if (!batch || !out) SK_BAD(ctx, "sk_trim_device_async: batch and out are required");
     // (packed reads have no name line to keep: the N records of SK_TRIM_PE_COMBO_ALL are the FASTQ text calls')
-    if (mode == SK_TRIM_PE_COMBO_ALL) SK_TRIM_BAD("trim: SK_TRIM_PE_COMBO_ALL is a mode of the FASTQ text calls only");
-    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_TRIM_BAD("trim mode %d is unknown", mode);
+    if (mode == SK_TRIM_PE_COMBO_ALL) SK_BAD(ctx, "trim: SK_TRIM_PE_COMBO_ALL is a mode of the FASTQ text calls only");
+    if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED) SK_BAD(ctx, "trim mode %d is unknown", mode);
     const uint64_t n = batch->n_reads;
-    if (batch->tiles) SK_TRIM_BAD("trim: segmented batches are not supported");
-    if (mode != SK_TRIM_SE && (n & 1)) SK_TRIM_BAD("trim: a paired mode needs an even number of reads, not %llu", (unsigned long long)n);
-    if (n && (!batch->qual || !cuts)) SK_TRIM_BAD("trim: qual and cuts are required");
-    if (reinterpret_cast<uintptr_t>(cuts) & 7) SK_TRIM_BAD("trim: cuts must be 8-byte aligned");
+    if (batch->tiles) SK_BAD(ctx, "trim: segmented batches are not supported");
+    if (mode != SK_TRIM_SE && (n & 1)) SK_BAD(ctx, "trim: a paired mode needs an even number of reads, not %llu", (unsigned long long)n);
+    if (n && (!batch->qual || !cuts)) SK_BAD(ctx, "trim: qual and cuts are required");
+    if (reinterpret_cast<uintptr_t>(cuts) & 7) SK_BAD(ctx, "trim: cuts must be 8-byte aligned");
     if (!batch->offsets) {
         if (batch->stride == 0 || (!batch->lengths && (batch->read_len > batch->stride || batch->read_len > SK_MAX_READ_LEN)))
-            SK_TRIM_BAD("trim: fixed-stride batch: need stride >= read_len (<= %u), or lengths", SK_MAX_READ_LEN);
+            SK_BAD(ctx, "trim: fixed-stride batch: need stride >= read_len (<= %u), or lengths", SK_MAX_READ_LEN);
     }
     for (int o = 0; o < 3; ++o) {
         const bool used = o == 0 || (mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2);
         if (!used || !out[o].offsets) continue;
         if ((reinterpret_cast<uintptr_t>(out[o].qual) | reinterpret_cast<uintptr_t>(out[o].seq)) & 15)
-            SK_TRIM_BAD("trim: out[%d].qual and out[%d].seq must be 16-byte aligned", o, o);
+            SK_BAD(ctx, "trim: out[%d].qual and out[%d].seq must be 16-byte aligned", o, o);
         if ((reinterpret_cast<uintptr_t>(out[o].offsets) | reinterpret_cast<uintptr_t>(out[o].read_index)) & 7)
-            SK_TRIM_BAD("trim: out[%d].offsets and out[%d].read_index must be 8-byte aligned", o, o);
-        if (n && out[o].seq && !batch->seq) SK_TRIM_BAD("trim: out[%d].seq needs batch->seq", o);
+            SK_BAD(ctx, "trim: out[%d].offsets and out[%d].read_index must be 8-byte aligned", o, o);
+        if (n && out[o].seq && !batch->seq) SK_BAD(ctx, "trim: out[%d].seq needs batch->seq", o);
     }
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < sk_trim_workspace_bytes(n))
-        SK_TRIM_BAD("trim: workspace must be 16-byte aligned and hold sk_trim_workspace_bytes(%llu) = %zu bytes",
-                    (unsigned long long)n, sk_trim_workspace_bytes(n));
-#undef SK_TRIM_BAD
+        SK_BAD(ctx, "trim: workspace must be 16-byte aligned and hold sk_trim_workspace_bytes(%llu) = %zu bytes",
+               (unsigned long long)n, sk_trim_workspace_bytes(n));
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_trim(batch, reinterpret_cast<const sk_cut_dev *>(cuts), mode, out, workspace, ctx->cu_count,
                                static_cast<hipStream_t>(hip_stream)));
@@ -734,22 +734,16 @@ int sk_trim_device_async(sk_ctx *ctx, const sk_batch *batch, const sk_cut *cuts,
 int sk_trim_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_trim_counts *counts)
 {
     if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[SK_TRIM_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    int rc = SK_OK;
+    int rc = read_header(ctx, workspace, h, SK_TRIM_HDR_WORDS, static_cast<hipStream_t>(hip_stream));
+    if (rc != SK_OK) return rc;
     for (int o = 0; o < 3; ++o) {
         counts->records[o] = h[SK_TRIM_H_RECORDS + o];
         counts->bytes[o] = h[SK_TRIM_H_BYTES + o];
         if (h[SK_TRIM_H_PRODUCED + o] && !h[SK_TRIM_H_FIT + o]) rc = SK_ESPACE;
     }
     counts->bad_read = h[SK_TRIM_H_BAD];
-    if (counts->bad_read != UINT64_MAX) {
-        set_error(ctx, "trim: read %llu has an invalid kept cut", (unsigned long long)counts->bad_read);
-        return SK_EINVAL;
-    }
+    if (counts->bad_read != UINT64_MAX) SK_BAD(ctx, "trim: read %llu has an invalid kept cut", (unsigned long long)counts->bad_read);
     if (rc == SK_ESPACE) set_error(ctx, "trim: an output's buffers are too small for what it needs");
     return rc;
 }
@@ -762,41 +756,34 @@ size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n)
 }
 
 namespace {
-// the argument checks of both FASTQ calls; extra = what an ordered call's batch table adds to the workspace
+// the argument checks of every FASTQ text call; extra = what an ordered call's batch table (and an ordered piece's block)
+// adds to the workspace
 int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in, int mode,
                      const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, size_t extra)
 {
-#define SK_FQ_BAD(...)                \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!params || !in || !out) SK_FQ_BAD("%s: params, in and out are required", who);
+    if (!params || !in || !out) SK_BAD(ctx, "%s: params, in and out are required", who);
     if (mode != SK_TRIM_SE && mode != SK_TRIM_PE_SPLIT && mode != SK_TRIM_PE_INTERLEAVED && mode != SK_TRIM_PE_COMBO_ALL)
-        SK_FQ_BAD("trim mode %d is unknown", mode);
+        SK_BAD(ctx, "trim mode %d is unknown", mode);
     const bool split = mode == SK_TRIM_PE_SPLIT;
-    if (split && !in->text[1]) SK_FQ_BAD("fastq: SK_TRIM_PE_SPLIT needs text[1]");
-    if (!split && (in->text[1] || in->bytes[1])) SK_FQ_BAD("fastq: text[1] is only for SK_TRIM_PE_SPLIT");
+    if (split && !in->text[1]) SK_BAD(ctx, "fastq: SK_TRIM_PE_SPLIT needs text[1]");
+    if (!split && (in->text[1] || in->bytes[1])) SK_BAD(ctx, "fastq: text[1] is only for SK_TRIM_PE_SPLIT");
     for (int i = 0; i < (split ? 2 : 1); ++i)
-        if (!in->text[i] && in->bytes[i]) SK_FQ_BAD("fastq: text[%d] is NULL with %llu bytes", i, (unsigned long long)in->bytes[i]);
+        if (!in->text[i] && in->bytes[i]) SK_BAD(ctx, "fastq: text[%d] is NULL with %llu bytes", i, (unsigned long long)in->bytes[i]);
     for (int o = 0; o < 3; ++o) {
-        if (reinterpret_cast<uintptr_t>(out[o].text) & 15) SK_FQ_BAD("fastq: out[%d].text must be 16-byte aligned", o);
-        if (reinterpret_cast<uintptr_t>(out[o].record_index) & 7) SK_FQ_BAD("fastq: out[%d].record_index must be 8-byte aligned", o);
+        if (reinterpret_cast<uintptr_t>(out[o].text) & 15) SK_BAD(ctx, "fastq: out[%d].text must be 16-byte aligned", o);
+        if (reinterpret_cast<uintptr_t>(out[o].record_index) & 7) SK_BAD(ctx, "fastq: out[%d].record_index must be 8-byte aligned", o);
     }
     const uint64_t T = in->bytes[0] + (split ? in->bytes[1] : 0);
     if (sk_fq_pack_reads(in->bytes[0], split ? in->bytes[1] : 0, mode) >= (1ull << 32))
-        SK_FQ_BAD("fastq: %llu bytes of text is beyond what one call takes", (unsigned long long)T);
+        SK_BAD(ctx, "fastq: %llu bytes of text is beyond what one call takes", (unsigned long long)T);
     const size_t need = sk_trim_fastq_workspace_bytes(T, params->trunc_n) + extra;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_FQ_BAD("fastq: workspace must be 16-byte aligned and hold sk_trim_fastq%s_workspace_bytes(%llu, %d%s) = %zu bytes",
-                  extra ? "_ordered" : "", (unsigned long long)T, params->trunc_n, extra ? ", batch_capacity" : "", need);
-#undef SK_FQ_BAD
+        SK_BAD(ctx, "fastq: workspace must be 16-byte aligned and hold sk_trim_fastq%s_workspace_bytes(%llu, %d%s) = %zu bytes",
+               extra ? "_ordered" : "", (unsigned long long)T, params->trunc_n, extra ? ", batch_capacity" : "", need);
     return SK_OK;
 }
-} // namespace
 
-namespace {
 // Q of an N record of SK_TRIM_PE_COMBO_ALL: the quality type's lowest quality byte (reference src/sickle.h:85-91).  (The
 // parameter checks of the scan have passed by the time this is called, so the type is known.)
 int fastq_fail_qual(const sk_params *params)
@@ -812,41 +799,38 @@ int fastq_check_words(sk_ctx *ctx, const sk_fastq_lengths *lengths, const sk_fas
         uintptr_t words = 0;
         for (int i = 0; i < 2; ++i)
             words |= reinterpret_cast<uintptr_t>(lengths->bytes_dev[i]) | reinterpret_cast<uintptr_t>(lengths->valid_dev[i]);
-        if (words & 7) {
-            set_error(ctx, "fastq: bytes_dev and valid_dev must be 8-byte aligned");
-            return SK_EINVAL;
-        }
-        if (mode != SK_TRIM_PE_SPLIT && (lengths->bytes_dev[1] || lengths->valid_dev[1])) {
-            set_error(ctx, "fastq: bytes_dev[1] and valid_dev[1] are only for SK_TRIM_PE_SPLIT");
-            return SK_EINVAL;
-        }
+        if (words & 7) SK_BAD(ctx, "fastq: bytes_dev and valid_dev must be 8-byte aligned");
+        if (mode != SK_TRIM_PE_SPLIT && (lengths->bytes_dev[1] || lengths->valid_dev[1]))
+            SK_BAD(ctx, "fastq: bytes_dev[1] and valid_dev[1] are only for SK_TRIM_PE_SPLIT");
     }
     if (piece) {
-        if (piece->reserved != 0) {
-            set_error(ctx, "fastq: piece->reserved must be 0");
-            return SK_EINVAL;
-        }
-        if ((reinterpret_cast<uintptr_t>(piece->start_dev[0]) | reinterpret_cast<uintptr_t>(piece->start_dev[1])) & 7) {
-            set_error(ctx, "fastq: start_dev must be 8-byte aligned");
-            return SK_EINVAL;
-        }
-        if (mode != SK_TRIM_PE_SPLIT && piece->start_dev[1]) {
-            set_error(ctx, "fastq: start_dev[1] is only for SK_TRIM_PE_SPLIT");
-            return SK_EINVAL;
-        }
+        if (piece->reserved != 0) SK_BAD(ctx, "fastq: piece->reserved must be 0");
+        if ((reinterpret_cast<uintptr_t>(piece->start_dev[0]) | reinterpret_cast<uintptr_t>(piece->start_dev[1])) & 7)
+            SK_BAD(ctx, "fastq: start_dev must be 8-byte aligned");
+        if (mode != SK_TRIM_PE_SPLIT && piece->start_dev[1]) SK_BAD(ctx, "fastq: start_dev[1] is only for SK_TRIM_PE_SPLIT");
     }
     return SK_OK;
 }
-} // namespace
 
-namespace {
-// both FASTQ calls; order: NULL = read order; piece: NULL = the whole text (else order is NULL)
+// the order of both ordered calls
+int check_order(sk_ctx *ctx, const sk_fastq_order *order)
+{
+    if (!order || order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN ||
+        order->batch_capacity == 0 || order->batch_capacity > (1ull << 40))
+        SK_BAD(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
+    return SK_OK;
+}
+
+// Every FASTQ text call: the checks, then the front, the counted scan and the emission.  lengths: NULL = in->bytes are the
+// lengths; order: NULL = read order; piece: NULL = the whole text; state_out: not NULL = an ordered piece (piece and order
+// given), whose launchers take the states.
 int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
                 const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
-                void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr)
+                void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr,
+                const sk_fastq_order_state *state_in = nullptr, sk_fastq_order_state *state_out = nullptr)
 {
-    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes,
-                              order ? (size_t)sk_fq_order_shift(order->batch_capacity) : 0);
+    const uint64_t extra = !order ? 0 : state_out ? sk_fq_order_piece_shift(order->batch_capacity) : sk_fq_order_shift(order->batch_capacity);
+    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes, (size_t)extra);
     if (rc != SK_OK) return rc;
     rc = fastq_check_words(ctx, lengths, piece, mode);
     if (rc != SK_OK) return rc;
@@ -868,13 +852,45 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     const char *counted_env = getenv("SK_FQ_COUNTED");
     const int counted = !(counted_env && *counted_env == '0');
     const uint64_t *n_reads_dev = nullptr;
-    SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, piece, d_err, workspace, ctx->cu_count,
-                                      stream, &packed, &cuts, &n_reads_dev));
+    if (state_out)
+        SK_HIP(ctx, sk_launch_fastq_order_piece_front(in, lengths, mode, params->trunc_n, counted, order, piece, state_in, state_out,
+                                                      d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev));
+    else
+        SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, piece, d_err, workspace, ctx->cu_count,
+                                          stream, &packed, &cuts, &n_reads_dev));
     rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, fastq_fail_qual(params), out,
-                                     workspace, d_err, ctx->cu_count, stream));
+    if (state_out)
+        SK_HIP(ctx, sk_launch_fastq_order_piece_emit(in, mode, params->trunc_n, counted, order, state_in, state_out,
+                                                     fastq_fail_qual(params), out, workspace, d_err, ctx->cu_count, stream));
+    else
+        SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, fastq_fail_qual(params), out,
+                                         workspace, d_err, ctx->cu_count, stream));
     return SK_OK;
+}
+
+// The finish of every FASTQ text call: the header back (with the block of the order words behind it for an ordered piece),
+// the stream's live range-error word for the whole-text kinds, which judge it, the word cleared, one wait; then the
+// verdict, a function of those words alone (sk_fastq_verdict.h).
+int fastq_finish(sk_ctx *ctx, int kind, void *workspace, void *hip_stream, sk_fastq_counts *counts, sk_fastq_order_counts *oc,
+                 sk_fastq_piece_counts *pc, sk_fastq_order_piece_counts *opc)
+{
+    if (!ctx || !workspace || !counts) return SK_EINVAL;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    unsigned long long *d_err, *h_err;
+    int rc = err_word_of(ctx, stream, &d_err, &h_err);
+    if (rc != SK_OK) return rc;
+    uint64_t h[SK_FQ_HDR_WORDS + SK_FQOP_EXT_BYTES / 8];
+    static_assert(SK_FQOP_EXT_BYTES_AT == 8 * SK_FQ_HDR_WORDS, "the block follows the header");
+    const bool block = kind == SK_FQV_ORDERED_PIECE;
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, hipMemcpyAsync(h, workspace, block ? sizeof h : 8 * SK_FQ_HDR_WORDS, hipMemcpyDeviceToHost, stream));
+    if (!fqv_is_piece(kind)) SK_HIP(ctx, hipMemcpyAsync(h_err, d_err, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    rc = reset_error_word(ctx, d_err, stream);
+    if (rc != SK_OK) return rc;
+    SK_HIP(ctx, hipStreamSynchronize(stream));
+    return fqv_verdict(kind, h, block ? h + SK_FQ_HDR_WORDS : h, fqv_range_word(kind, h, *h_err), counts, oc, pc, opc,
+                       ctx->last_error, sizeof ctx->last_error);
 }
 } // namespace
 
@@ -885,84 +901,9 @@ int sk_trim_fastq_device_async(sk_ctx *ctx, const sk_params *params, const sk_fa
                        hip_stream);
 }
 
-namespace {
-// finish of both FASTQ calls
-int fastq_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts, sk_fastq_order_counts *oc, bool ordered)
-{
-    if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    unsigned long long *d_err, *h_err;
-    int rc = err_word_of(ctx, stream, &d_err, &h_err);
-    if (rc != SK_OK) return rc;
-    uint64_t h[SK_FQ_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipMemcpyAsync(h_err, d_err, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    rc = reset_error_word(ctx, d_err, stream);
-    if (rc != SK_OK) return rc;
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    *counts = sk_fastq_counts{};
-    for (int i = 0; i < 2; ++i) {
-        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
-        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] & 3;
-    }
-    const uint64_t fmt = h[SK_FQ_H_FMT];
-    const bool split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
-    const bool refused = ordered && (h[SK_FQO_H_LONG] != ~0ull || h[SK_FQO_H_OVERFLOW]);
-    const bool bad = fmt != ~0ull || refused;
-    counts->dropped_unpaired = !ordered && h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
-    for (int o = 0; o < 3; ++o) {
-        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
-        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
-    }
-    if (oc) {
-        *oc = sk_fastq_order_counts{};
-        oc->batches = h[SK_FQO_H_BATCHES];
-        oc->units = h[SK_FQO_H_UNITS];
-        oc->last_batch_units = h[SK_FQO_H_LAST_UNITS];
-        oc->records_unbatched[0] = h[SK_FQO_H_UNBATCHED];
-        oc->records_unbatched[1] = h[SK_FQO_H_UNBATCHED + 1];
-        oc->stopped_on_mismatch = (uint32_t)h[SK_FQO_H_MISMATCH];
-        oc->error_batch = refused ? UINT64_MAX : h[SK_FQO_H_ERROR_BATCH];
-    }
-    if (ordered && h[SK_FQO_H_LONG] != ~0ull) {
-        const uint64_t key = h[SK_FQO_H_LONG];
-        if (oc) {
-            oc->long_line_input = (uint32_t)(key >> 63);
-            oc->long_line = key & ~(1ull << 63);
-        }
-        set_error(ctx, "fastq: input %u, line %llu has batch_len - 1 bytes or more", (unsigned)(key >> 63),
-                  (unsigned long long)(key & ~(1ull << 63)));
-        return SK_ELONGLINE;
-    }
-    if (ordered && h[SK_FQO_H_OVERFLOW]) {
-        set_error(ctx, "fastq: the text has more batches than batch_capacity");
-        return SK_ESPACE;
-    }
-    if (bad) {
-        const uint64_t read = fmt >> 3;
-        counts->format_error = (int32_t)(fmt & 7);
-        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
-        counts->format_record = split ? read >> 1 : read;
-        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
-                  (unsigned long long)counts->format_record, counts->format_error);
-        return SK_EFORMAT;
-    }
-    if (decode_error(*h_err, &counts->range) == SK_ERANGE) {
-        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
-                  counts->range.pos + 1);
-        return SK_ERANGE;
-    }
-    for (int o = 0; o < 3; ++o)
-        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
-    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
-    return rc;
-}
-} // namespace
-
 int sk_trim_fastq_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts)
 {
-    return fastq_finish(ctx, workspace, hip_stream, counts, nullptr, false);
+    return fastq_finish(ctx, SK_FQV_PLAIN, workspace, hip_stream, counts, nullptr, nullptr, nullptr);
 }
 
 size_t sk_trim_fastq_ordered_workspace_bytes(uint64_t text_bytes, int32_t trunc_n, uint64_t batch_capacity)
@@ -970,38 +911,27 @@ size_t sk_trim_fastq_ordered_workspace_bytes(uint64_t text_bytes, int32_t trunc_
     return sk_trim_fastq_workspace_bytes(text_bytes, trunc_n) + (size_t)sk_fq_order_shift(batch_capacity);
 }
 
-namespace {
-// the ordered call; lengths: NULL = in->bytes are the lengths
-int fastq_ordered_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
-                        const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order,
-                        const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!ctx) return SK_EINVAL;
-    if (!order || order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN ||
-        order->batch_capacity == 0 || order->batch_capacity > (1ull << 40)) {
-        set_error(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
-        return SK_EINVAL;
-    }
-    return fastq_async(ctx, "sk_trim_fastq_ordered_device_async", params, in, lengths, mode, order, out, workspace,
-                       workspace_bytes, hip_stream);
-}
-} // namespace
-
 int sk_trim_fastq_ordered_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, int mode,
                                        const sk_fastq_order *order, const sk_fastq_output out[3], void *workspace,
                                        size_t workspace_bytes, void *hip_stream)
 {
-    return fastq_ordered_async(ctx, params, in, nullptr, mode, order, out, workspace, workspace_bytes, hip_stream);
+    if (!ctx) return SK_EINVAL;
+    if (int rc = check_order(ctx, order)) return rc;
+    return fastq_async(ctx, "sk_trim_fastq_ordered_device_async", params, in, nullptr, mode, order, out, workspace, workspace_bytes,
+                       hip_stream);
 }
 
+// order: NULL = read order, else the ordered call with the lengths on the device
 int sk_trim_fastq_chained_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
                                        const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order,
                                        const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
                                        void *hip_stream)
 {
-    if (order) return fastq_ordered_async(ctx, params, in, lengths, mode, order, out, workspace, workspace_bytes, hip_stream);
-    return fastq_async(ctx, "sk_trim_fastq_chained_device_async", params, in, lengths, mode, nullptr, out, workspace,
-                       workspace_bytes, hip_stream);
+    if (!ctx) return SK_EINVAL;
+    if (order)
+        if (int rc = check_order(ctx, order)) return rc;
+    return fastq_async(ctx, order ? "sk_trim_fastq_ordered_device_async" : "sk_trim_fastq_chained_device_async", params, in, lengths,
+                       mode, order, out, workspace, workspace_bytes, hip_stream);
 }
 
 int sk_trim_fastq_piece_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in,
@@ -1024,70 +954,10 @@ int sk_trim_fastq_piece_words(void *workspace, int input, const uint64_t **consu
     return SK_OK;
 }
 
-// Every verdict from the workspace's own words: the range error is the word the piece's emission captured
-// (SK_FQ_H_RANGE), or the one its frame scan found already set (SK_FQP_H_RANGE0).  The stream's live word is cleared, as
-// fastq_finish does, and never read.
 int sk_trim_fastq_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
                                       sk_fastq_piece_counts *pc)
 {
-    if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    unsigned long long *d_err, *h_err;
-    int rc = err_word_of(ctx, stream, &d_err, &h_err);
-    if (rc != SK_OK) return rc;
-    uint64_t h[SK_FQ_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    rc = reset_error_word(ctx, d_err, stream);
-    if (rc != SK_OK) return rc;
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    *counts = sk_fastq_counts{};
-    const bool more = h[SK_FQP_H_MORE] != 0, split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
-    const bool inherited = h[SK_FQP_H_RANGE0] != ~0ull;
-    for (int i = 0; i < 2; ++i) {
-        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
-        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] - 4 * h[SK_FQ_H_RECORDS + i]; // a piece carries whole records too
-    }
-    const uint64_t fmt = h[SK_FQ_H_FMT];
-    const bool bad = fmt != ~0ull;
-    counts->dropped_unpaired = !more && h[SK_FQ_H_MODE] == SK_TRIM_PE_INTERLEAVED ? (h[SK_FQ_H_RECORDS] & 1) : 0;
-    for (int o = 0; o < 3; ++o) {
-        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
-        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
-    }
-    if (pc) {
-        *pc = sk_fastq_piece_counts{};
-        for (int i = 0; i < 2; ++i) {
-            pc->consumed[i] = h[SK_FQP_H_CONSUMED + i];
-            pc->carried_bytes[i] = h[SK_FQP_H_END + i] - h[SK_FQP_H_CONSUMED + i];
-        }
-        pc->ok = (uint32_t)h[SK_FQP_H_OK];
-        pc->inherited_range = inherited;
-    }
-    if (inherited) {
-        decode_error(h[SK_FQP_H_RANGE0], &counts->range);
-        set_error(ctx, "fastq: an earlier call on the stream left a range error (read %u of that call); the piece took no record",
-                  counts->range.read);
-        return SK_ERANGE;
-    }
-    if (bad) {
-        const uint64_t read = fmt >> 3;
-        counts->format_error = (int32_t)(fmt & 7);
-        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
-        counts->format_record = split ? read >> 1 : read;
-        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
-                  (unsigned long long)counts->format_record, counts->format_error);
-        return SK_EFORMAT;
-    }
-    if (decode_error(h[SK_FQ_H_RANGE], &counts->range) == SK_ERANGE) {
-        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
-                  counts->range.pos + 1);
-        return SK_ERANGE;
-    }
-    for (int o = 0; o < 3; ++o)
-        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
-    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
-    return rc;
+    return fastq_finish(ctx, SK_FQV_PIECE, workspace, hip_stream, counts, nullptr, pc, nullptr);
 }
 
 int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int input, const uint8_t *prev_text,
@@ -1097,26 +967,20 @@ int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int inp
                                 sk_fastq_carry_words *words, void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
-#define SK_FQC_BAD(...)               \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
-    if (!next_text || !words) SK_FQC_BAD("carry: next_text and words are required");
-    if (input < 0 || input > 1) SK_FQC_BAD("carry: input is 0 or 1");
-    if (prev_workspace && !prev_text) SK_FQC_BAD("carry: prev_text is required with prev_workspace");
-    if (room & 15) SK_FQC_BAD("carry: room must be a multiple of 16");
+    if (!next_text || !words) SK_BAD(ctx, "carry: next_text and words are required");
+    if (input < 0 || input > 1) SK_BAD(ctx, "carry: input is 0 or 1");
+    if (prev_workspace && !prev_text) SK_BAD(ctx, "carry: prev_text is required with prev_workspace");
+    if (room & 15) SK_BAD(ctx, "carry: room must be a multiple of 16");
     uintptr_t w = reinterpret_cast<uintptr_t>(chunk_bytes_dev) | reinterpret_cast<uintptr_t>(chunk_valid_dev) |
                   reinterpret_cast<uintptr_t>(prev_words) | reinterpret_cast<uintptr_t>(other_prev_words) |
                   reinterpret_cast<uintptr_t>(words) | reinterpret_cast<uintptr_t>(prev_workspace);
-    if (w & 7) SK_FQC_BAD("carry: the device words and prev_workspace must be 8-byte aligned");
-    if (words == prev_words || words == other_prev_words) SK_FQC_BAD("carry: words must not be one of the previous words");
+    if (w & 7) SK_BAD(ctx, "carry: the device words and prev_workspace must be 8-byte aligned");
+    if (words == prev_words || words == other_prev_words) SK_BAD(ctx, "carry: words must not be one of the previous words");
     if (prev_workspace) {
         const uintptr_t p0 = reinterpret_cast<uintptr_t>(prev_text), p1 = p0 + prev_bytes;
         const uintptr_t n0 = reinterpret_cast<uintptr_t>(next_text), n1 = n0 + room;
-        if (p0 < n1 && n0 < p1) SK_FQC_BAD("carry: [next_text, next_text + room) overlaps the previous text");
+        if (p0 < n1 && n0 < p1) SK_BAD(ctx, "carry: [next_text, next_text + room) overlaps the previous text");
     }
-#undef SK_FQC_BAD
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_carry(static_cast<const uint64_t *>(prev_workspace), input, prev_text, next_text, room,
                                       chunk_bytes_dev, chunk_bytes, chunk_valid_dev, prev_words, other_prev_words, words,
@@ -1127,7 +991,7 @@ int sk_fastq_carry_device_async(sk_ctx *ctx, const void *prev_workspace, int inp
 int sk_trim_fastq_ordered_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
                                         sk_fastq_order_counts *order_counts)
 {
-    return fastq_finish(ctx, workspace, hip_stream, counts, order_counts, true);
+    return fastq_finish(ctx, SK_FQV_ORDERED, workspace, hip_stream, counts, order_counts, nullptr, nullptr);
 }
 
 int sk_trim_fastq_ordered_batches(void *workspace, const uint64_t **first_unit_dev)
@@ -1151,141 +1015,19 @@ int sk_trim_fastq_ordered_piece_device_async(sk_ctx *ctx, const sk_params *param
 {
     static_assert(sizeof(sk_fastq_order_state) == 64, "the kernels read the state as 8 words");
     if (!ctx) return SK_EINVAL;
-    if (!piece || !order || !state_out) {
-        set_error(ctx, "fastq: an ordered piece needs piece, order and state_out");
-        return SK_EINVAL;
-    }
-    if (order->threads == 0 || order->reserved != 0 || order->batch_len < SK_FQO_MIN_BATCH_LEN || order->batch_capacity == 0 ||
-        order->batch_capacity > (1ull << 40)) {
-        set_error(ctx, "fastq: order needs threads >= 1, reserved 0, batch_len >= 20 and 1 <= batch_capacity <= 2^40");
-        return SK_EINVAL;
-    }
-    if (state_in == state_out || ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 7)) {
-        set_error(ctx, "fastq: state_in and state_out must be 8-byte aligned and differ");
-        return SK_EINVAL;
-    }
-    int rc = fastq_check_args(ctx, "sk_trim_fastq_ordered_piece_device_async", params, in, mode, out, workspace, workspace_bytes,
-                              (size_t)sk_fq_order_piece_shift(order->batch_capacity));
-    if (rc != SK_OK) return rc;
-    rc = fastq_check_words(ctx, lengths, piece, mode);
-    if (rc != SK_OK) return rc;
-    sk_scan_args chk;
-    const uint64_t no_reads = 0;
-    sk_batch probe = {};
-    probe.offsets = &no_reads; // an empty `offsets` batch: only params is checked
-    rc = make_args(ctx, params, &probe, &chk);
-    if (rc != SK_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    unsigned long long *d_err, *h_err;
-    rc = err_word_of(ctx, stream, &d_err, &h_err);
-    if (rc != SK_OK) return rc;
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    sk_batch packed;
-    sk_cut_dev *cuts;
-    const char *counted_env = getenv("SK_FQ_COUNTED"); // as in fastq_async
-    const int counted = !(counted_env && *counted_env == '0');
-    const uint64_t *n_reads_dev = nullptr;
-    SK_HIP(ctx, sk_launch_fastq_order_piece_front(in, lengths, mode, params->trunc_n, counted, order, piece, state_in, state_out,
-                                                  d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev));
-    rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
-    if (rc != SK_OK) return rc;
-    SK_HIP(ctx, sk_launch_fastq_order_piece_emit(in, mode, params->trunc_n, counted, order, state_in, state_out,
-                                                 fastq_fail_qual(params), out, workspace, d_err, ctx->cu_count, stream));
-    return SK_OK;
+    if (!piece || !order || !state_out) SK_BAD(ctx, "fastq: an ordered piece needs piece, order and state_out");
+    if (int rc = check_order(ctx, order)) return rc;
+    if (state_in == state_out || ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 7))
+        SK_BAD(ctx, "fastq: state_in and state_out must be 8-byte aligned and differ");
+    return fastq_async(ctx, "sk_trim_fastq_ordered_piece_device_async", params, in, lengths, mode, order, out, workspace,
+                       workspace_bytes, hip_stream, piece, state_in, state_out);
 }
 
-// Every verdict from the workspace's own words, as sk_trim_fastq_piece_device_finish takes them.
 int sk_trim_fastq_ordered_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_counts *counts,
                                               sk_fastq_order_counts *oc, sk_fastq_piece_counts *pc,
                                               sk_fastq_order_piece_counts *opc)
 {
-    if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    unsigned long long *d_err, *h_err;
-    int rc = err_word_of(ctx, stream, &d_err, &h_err);
-    if (rc != SK_OK) return rc;
-    uint64_t h[SK_FQ_HDR_WORDS + SK_FQOP_EXT_BYTES / 8]; // the header and the extension block behind it
-    static_assert(SK_FQOP_EXT_BYTES_AT == 8 * SK_FQ_HDR_WORDS, "the block follows the header");
-    const uint64_t *x = h + SK_FQ_HDR_WORDS;
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    rc = reset_error_word(ctx, d_err, stream);
-    if (rc != SK_OK) return rc;
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    *counts = sk_fastq_counts{};
-    const bool split = h[SK_FQ_H_MODE] == SK_TRIM_PE_SPLIT;
-    const bool inherited_range = h[SK_FQP_H_RANGE0] != ~0ull, inherited = x[SK_FQOP_X_INHERITED] != 0;
-    const uint64_t fmt = h[SK_FQ_H_FMT], lng = x[SK_FQO_H_LONG];
-    const bool bad = fmt != ~0ull || lng != ~0ull;
-    for (int i = 0; i < 2; ++i) {
-        counts->records_in[i] = h[SK_FQ_H_RECORDS + i];
-        counts->tail_lines[i] = h[SK_FQ_H_LINES + i] - 4 * h[SK_FQ_H_RECORDS + i];
-    }
-    for (int o = 0; o < 3; ++o) {
-        counts->records[o] = bad ? 0 : h[SK_FQ_H_OUT_RECORDS + o];
-        counts->bytes[o] = bad ? 0 : h[SK_FQ_H_OUT_BYTES + o];
-    }
-    if (oc) {
-        *oc = sk_fastq_order_counts{};
-        oc->batches = x[SK_FQO_H_BATCHES];
-        oc->units = x[SK_FQO_H_UNITS];
-        oc->last_batch_units = x[SK_FQO_H_LAST_UNITS];
-        oc->records_unbatched[0] = x[SK_FQO_H_UNBATCHED];
-        oc->records_unbatched[1] = x[SK_FQO_H_UNBATCHED + 1];
-        oc->stopped_on_mismatch = (uint32_t)x[SK_FQO_H_MISMATCH];
-        oc->error_batch = lng != ~0ull || x[SK_FQO_H_ERROR_BATCH] == ~0ull ? UINT64_MAX
-                                                                            : x[SK_FQOP_X_BASE_BATCHES] + x[SK_FQO_H_ERROR_BATCH];
-        if (lng != ~0ull) {
-            oc->long_line_input = (uint32_t)(lng >> 63);
-            oc->long_line = lng & ~(1ull << 63);
-        }
-    }
-    if (pc) {
-        *pc = sk_fastq_piece_counts{};
-        for (int i = 0; i < 2; ++i) {
-            pc->consumed[i] = h[SK_FQP_H_CONSUMED + i];
-            pc->carried_bytes[i] = h[SK_FQP_H_END + i] - h[SK_FQP_H_CONSUMED + i];
-        }
-        pc->ok = (uint32_t)h[SK_FQP_H_OK];
-        pc->inherited_range = inherited_range;
-    }
-    if (opc) {
-        *opc = sk_fastq_order_piece_counts{};
-        opc->table_full = (uint32_t)x[SK_FQOP_X_TABLE_FULL];
-        opc->undetermined = (uint32_t)x[SK_FQOP_X_UNDETERMINED];
-        opc->inherited_failure = inherited;
-        memcpy(&opc->state, x + SK_FQOP_X_STATE, sizeof opc->state);
-    }
-    if (inherited_range) {
-        decode_error(h[SK_FQP_H_RANGE0], &counts->range);
-        set_error(ctx, "fastq: an earlier call on the stream left a range error (read %u of that call); the piece took no record",
-                  counts->range.read);
-        return SK_ERANGE;
-    }
-    if (inherited) return SK_OK; // void: the first failing piece is the one that reports
-    if (lng != ~0ull) {
-        set_error(ctx, "fastq: input %u, line %llu of the piece has batch_len - 1 bytes or more", (unsigned)(lng >> 63),
-                  (unsigned long long)(lng & ~(1ull << 63)));
-        return SK_ELONGLINE;
-    }
-    if (bad) {
-        const uint64_t read = fmt >> 3;
-        counts->format_error = (int32_t)(fmt & 7);
-        counts->format_input = split ? (uint32_t)(read & 1) : 0u;
-        counts->format_record = split ? read >> 1 : read;
-        set_error(ctx, "fastq: input %u, record %llu is malformed (reason %d)", counts->format_input,
-                  (unsigned long long)counts->format_record, counts->format_error);
-        return SK_EFORMAT;
-    }
-    if (decode_error(h[SK_FQ_H_RANGE], &counts->range) == SK_ERANGE) {
-        set_error(ctx, "fastq: quality value %d out of range in read %u at position %u", counts->range.ch, counts->range.read,
-                  counts->range.pos + 1);
-        return SK_ERANGE;
-    }
-    for (int o = 0; o < 3; ++o)
-        if (h[SK_FQ_H_PRODUCED + o] && !h[SK_FQ_H_FIT + o]) rc = SK_ESPACE;
-    if (rc == SK_ESPACE) set_error(ctx, "fastq: an output's buffers are too small for what it needs");
-    return rc;
+    return fastq_finish(ctx, SK_FQV_ORDERED_PIECE, workspace, hip_stream, counts, oc, pc, opc);
 }
 
 int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)
@@ -1315,101 +1057,93 @@ int sk_trim_fastq_output_words(void *fastq_workspace, int output, const uint64_t
     return SK_OK;
 }
 
-// every check before the first HIP call: bad arguments enqueue nothing and need no device
+namespace {
+// The calls that go behind a text call (report, audit, bases, rejects; who: "report:" ..) check every argument before the
+// first HIP call: bad arguments enqueue nothing and need no device.
+// the source, once the caller has seen that src and src->workspace are there
+int check_source(sk_ctx *ctx, const char *who, const sk_fastq_report_source *src)
+{
+    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_BAD(ctx, "%s src->workspace must be 16-byte aligned", who);
+    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_BAD(ctx, "%s source kind %u is unknown", who, src->kind);
+    if (src->reserved != 0) SK_BAD(ctx, "%s src->reserved must be 0", who);
+    return SK_OK;
+}
+
+// the mode, and the texts against it (in: NULL = no texts, where the caller allows that).  text0_in_se: an SE call reads
+// text[0] too (the audit looks at the names of pairs alone)
+int check_texts(sk_ctx *ctx, const char *who, const sk_fastq_input *in, int mode, bool text0_in_se)
+{
+    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_BAD(ctx, "%s mode %d is unknown", who, mode);
+    if (!in) return SK_OK;
+    if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_BAD(ctx, "%s SK_TRIM_PE_SPLIT needs text[1]", who);
+    if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_BAD(ctx, "%s text[1] is for SK_TRIM_PE_SPLIT only", who);
+    if ((text0_in_se || mode != SK_TRIM_SE) && !in->text[0] && in->bytes[0]) SK_BAD(ctx, "%s text[0] is NULL with bytes[0] != 0", who);
+    return SK_OK;
+}
+} // namespace
+
 int sk_trim_fastq_report_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, sk_fastq_report *report_dev,
                                       const sk_fastq_report_hists *hists, int flags, void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
-#define SK_FQR_BAD(...)               \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
-    if (!src || !src->workspace || !report_dev) SK_FQR_BAD("report: src, src->workspace and report_dev are required");
-    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQR_BAD("report: src->workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(report_dev) & 7) SK_FQR_BAD("report: report_dev must be 8-byte aligned");
-    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQR_BAD("report: source kind %u is unknown", src->kind);
-    if (src->reserved != 0) SK_FQR_BAD("report: src->reserved must be 0");
-    if (flags & ~SK_FQ_REPORT_RESET) SK_FQR_BAD("report: flags %d are unknown", flags);
+    if (!src || !src->workspace || !report_dev) SK_BAD(ctx, "report: src, src->workspace and report_dev are required");
+    if (int rc = check_source(ctx, "report:", src)) return rc;
+    if (reinterpret_cast<uintptr_t>(report_dev) & 7) SK_BAD(ctx, "report: report_dev must be 8-byte aligned");
+    if (flags & ~SK_FQ_REPORT_RESET) SK_BAD(ctx, "report: flags %d are unknown", flags);
     if (hists) {
         const uintptr_t len = reinterpret_cast<uintptr_t>(hists->len_in) | reinterpret_cast<uintptr_t>(hists->len_out);
         const uintptr_t pos = reinterpret_cast<uintptr_t>(hists->qsum_in) | reinterpret_cast<uintptr_t>(hists->qcnt_in) |
                               reinterpret_cast<uintptr_t>(hists->qsum_out) | reinterpret_cast<uintptr_t>(hists->qcnt_out);
-        if ((len | pos) & 7) SK_FQR_BAD("report: the histogram arrays must be 8-byte aligned");
-        if (len && hists->len_bins == 0) SK_FQR_BAD("report: len_bins is 0 with a length array given");
-        if (pos && hists->pos_bins == 0) SK_FQR_BAD("report: pos_bins is 0 with a position array given");
+        if ((len | pos) & 7) SK_BAD(ctx, "report: the histogram arrays must be 8-byte aligned");
+        if (len && hists->len_bins == 0) SK_BAD(ctx, "report: len_bins is 0 with a length array given");
+        if (pos && hists->pos_bins == 0) SK_BAD(ctx, "report: pos_bins is 0 with a position array given");
         if (hists->len_bins > SK_FQ_REPORT_MAX_LEN_BINS)
-            SK_FQR_BAD("report: len_bins %llu is above SK_FQ_REPORT_MAX_LEN_BINS = %u", (unsigned long long)hists->len_bins,
-                       SK_FQ_REPORT_MAX_LEN_BINS);
+            SK_BAD(ctx, "report: len_bins %llu is above SK_FQ_REPORT_MAX_LEN_BINS = %u", (unsigned long long)hists->len_bins,
+                   SK_FQ_REPORT_MAX_LEN_BINS);
         if (hists->pos_bins > SK_FQ_REPORT_MAX_POS_BINS)
-            SK_FQR_BAD("report: pos_bins %llu is above SK_FQ_REPORT_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
-                       SK_FQ_REPORT_MAX_POS_BINS);
+            SK_BAD(ctx, "report: pos_bins %llu is above SK_FQ_REPORT_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
+                   SK_FQ_REPORT_MAX_POS_BINS);
     }
-#undef SK_FQR_BAD
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_report(src, report_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
 }
 
-// every check before the first HIP call: bad arguments enqueue nothing and need no device
+// in: NULL = the names are not looked at
 int sk_trim_fastq_audit_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
                                      sk_fastq_audit *audit_dev, uint64_t *qual_hist_dev, int flags, void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
-#define SK_FQA_BAD(...)               \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
-    if (!src || !src->workspace || !audit_dev) SK_FQA_BAD("audit: src, src->workspace and audit_dev are required");
-    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQA_BAD("audit: src->workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(audit_dev) & 7) SK_FQA_BAD("audit: audit_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(qual_hist_dev) & 7) SK_FQA_BAD("audit: qual_hist_dev must be 8-byte aligned");
-    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQA_BAD("audit: source kind %u is unknown", src->kind);
-    if (src->reserved != 0) SK_FQA_BAD("audit: src->reserved must be 0");
-    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQA_BAD("audit: mode %d is unknown", mode);
-    if (flags & ~SK_FQ_AUDIT_RESET) SK_FQA_BAD("audit: flags %d are unknown", flags);
-    if (in) {
-        if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQA_BAD("audit: SK_TRIM_PE_SPLIT needs text[1]");
-        if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQA_BAD("audit: text[1] is for SK_TRIM_PE_SPLIT only");
-        if (mode != SK_TRIM_SE && !in->text[0] && in->bytes[0]) SK_FQA_BAD("audit: text[0] is NULL with bytes[0] != 0");
-    }
-#undef SK_FQA_BAD
+    if (!src || !src->workspace || !audit_dev) SK_BAD(ctx, "audit: src, src->workspace and audit_dev are required");
+    if (int rc = check_source(ctx, "audit:", src)) return rc;
+    if (reinterpret_cast<uintptr_t>(audit_dev) & 7) SK_BAD(ctx, "audit: audit_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(qual_hist_dev) & 7) SK_BAD(ctx, "audit: qual_hist_dev must be 8-byte aligned");
+    if (flags & ~SK_FQ_AUDIT_RESET) SK_BAD(ctx, "audit: flags %d are unknown", flags);
+    if (int rc = check_texts(ctx, "audit:", in, mode, false)) return rc;
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_audit(src, in, mode, audit_dev, qual_hist_dev, flags, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
 }
 
-// every check before the first HIP call: bad arguments enqueue nothing and need no device
+// the texts are the data: in is required
 int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
                                      sk_fastq_bases *bases_dev, const sk_fastq_bases_hists *hists, int flags, void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
-#define SK_FQB_BAD(...)               \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
-    if (!src || !src->workspace || !bases_dev || !in) SK_FQB_BAD("bases: src, src->workspace, bases_dev and in are required");
-    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQB_BAD("bases: src->workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(bases_dev) & 7) SK_FQB_BAD("bases: bases_dev must be 8-byte aligned");
-    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQB_BAD("bases: source kind %u is unknown", src->kind);
-    if (src->reserved != 0) SK_FQB_BAD("bases: src->reserved must be 0");
-    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQB_BAD("bases: mode %d is unknown", mode);
-    if (flags & ~SK_FQ_BASES_RESET) SK_FQB_BAD("bases: flags %d are unknown", flags);
-    if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQB_BAD("bases: SK_TRIM_PE_SPLIT needs text[1]");
-    if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQB_BAD("bases: text[1] is for SK_TRIM_PE_SPLIT only");
-    if (!in->text[0] && in->bytes[0]) SK_FQB_BAD("bases: text[0] is NULL with bytes[0] != 0");
+    if (!src || !src->workspace || !bases_dev || !in) SK_BAD(ctx, "bases: src, src->workspace, bases_dev and in are required");
+    if (int rc = check_source(ctx, "bases:", src)) return rc;
+    if (reinterpret_cast<uintptr_t>(bases_dev) & 7) SK_BAD(ctx, "bases: bases_dev must be 8-byte aligned");
+    if (flags & ~SK_FQ_BASES_RESET) SK_BAD(ctx, "bases: flags %d are unknown", flags);
+    if (int rc = check_texts(ctx, "bases:", in, mode, true)) return rc;
     if (hists) {
         const uintptr_t pos = reinterpret_cast<uintptr_t>(hists->pos_in) | reinterpret_cast<uintptr_t>(hists->pos_out);
         const uintptr_t gc = reinterpret_cast<uintptr_t>(hists->gc_in) | reinterpret_cast<uintptr_t>(hists->gc_out);
-        if ((pos | gc) & 7) SK_FQB_BAD("bases: the arrays must be 8-byte aligned");
-        if (pos && hists->pos_bins == 0) SK_FQB_BAD("bases: pos_bins is 0 with a position array given");
+        if ((pos | gc) & 7) SK_BAD(ctx, "bases: the arrays must be 8-byte aligned");
+        if (pos && hists->pos_bins == 0) SK_BAD(ctx, "bases: pos_bins is 0 with a position array given");
         if (hists->pos_bins > SK_FQ_BASES_MAX_POS_BINS)
-            SK_FQB_BAD("bases: pos_bins %llu is above SK_FQ_BASES_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
-                       SK_FQ_BASES_MAX_POS_BINS);
+            SK_BAD(ctx, "bases: pos_bins %llu is above SK_FQ_BASES_MAX_POS_BINS = %u", (unsigned long long)hists->pos_bins,
+                   SK_FQ_BASES_MAX_POS_BINS);
     }
-#undef SK_FQB_BAD
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_bases(src, in, mode, bases_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
@@ -1419,37 +1153,25 @@ size_t sk_trim_fastq_rejects_workspace_bytes(uint64_t text_bytes) { return (size
 
 uint64_t sk_trim_fastq_rejects_bound(uint64_t text_bytes) { return fqj_bound(text_bytes); }
 
-// every check before the first HIP call: bad arguments enqueue nothing and need no device
 int sk_trim_fastq_rejects_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
                                        const sk_fastq_output *out, int flags, void *workspace, size_t workspace_bytes,
                                        void *hip_stream)
 {
     if (!ctx) return SK_EINVAL;
-#define SK_FQJ_BAD(...)               \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
-    if (!src || !src->workspace || !in || !workspace) SK_FQJ_BAD("rejects: src, src->workspace, in and workspace are required");
-    if (reinterpret_cast<uintptr_t>(src->workspace) & 15) SK_FQJ_BAD("rejects: src->workspace must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) SK_FQJ_BAD("rejects: workspace must be 16-byte aligned");
-    if (out && (reinterpret_cast<uintptr_t>(out->text) & 15)) SK_FQJ_BAD("rejects: out->text must be 16-byte aligned");
-    if (out && (reinterpret_cast<uintptr_t>(out->record_index) & 7)) SK_FQJ_BAD("rejects: out->record_index must be 8-byte aligned");
-    if (src->kind > SK_FQ_REPORT_ORDERED_PIECE) SK_FQJ_BAD("rejects: source kind %u is unknown", src->kind);
-    if (src->reserved != 0) SK_FQJ_BAD("rejects: src->reserved must be 0");
-    if (mode < SK_TRIM_SE || mode > SK_TRIM_PE_COMBO_ALL) SK_FQJ_BAD("rejects: mode %d is unknown", mode);
-    if (flags & ~SK_FQ_REJECTS_PAIRS) SK_FQJ_BAD("rejects: flags %d are unknown", flags);
-    if ((flags & SK_FQ_REJECTS_PAIRS) && mode == SK_TRIM_SE) SK_FQJ_BAD("rejects: SK_FQ_REJECTS_PAIRS needs a pair mode");
-    if (mode == SK_TRIM_PE_SPLIT && !in->text[1]) SK_FQJ_BAD("rejects: SK_TRIM_PE_SPLIT needs text[1]");
-    if (mode != SK_TRIM_PE_SPLIT && in->text[1]) SK_FQJ_BAD("rejects: text[1] is for SK_TRIM_PE_SPLIT only");
-    if (!in->text[0] && in->bytes[0]) SK_FQJ_BAD("rejects: text[0] is NULL with bytes[0] != 0");
-    if (!in->text[1] && in->bytes[1]) SK_FQJ_BAD("rejects: text[1] is NULL with bytes[1] != 0");
-    if (src->text_bytes > (1ull << 35)) SK_FQJ_BAD("rejects: %llu bytes of text is beyond what a text call takes", (unsigned long long)src->text_bytes);
+    if (!src || !src->workspace || !in || !workspace) SK_BAD(ctx, "rejects: src, src->workspace, in and workspace are required");
+    if (int rc = check_source(ctx, "rejects:", src)) return rc;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) SK_BAD(ctx, "rejects: workspace must be 16-byte aligned");
+    if (out && (reinterpret_cast<uintptr_t>(out->text) & 15)) SK_BAD(ctx, "rejects: out->text must be 16-byte aligned");
+    if (out && (reinterpret_cast<uintptr_t>(out->record_index) & 7)) SK_BAD(ctx, "rejects: out->record_index must be 8-byte aligned");
+    if (int rc = check_texts(ctx, "rejects:", in, mode, true)) return rc;
+    if (flags & ~SK_FQ_REJECTS_PAIRS) SK_BAD(ctx, "rejects: flags %d are unknown", flags);
+    if ((flags & SK_FQ_REJECTS_PAIRS) && mode == SK_TRIM_SE) SK_BAD(ctx, "rejects: SK_FQ_REJECTS_PAIRS needs a pair mode");
+    if (!in->text[1] && in->bytes[1]) SK_BAD(ctx, "rejects: text[1] is NULL with bytes[1] != 0"); // (in every mode)
+    if (src->text_bytes > (1ull << 35)) SK_BAD(ctx, "rejects: %llu bytes of text is beyond what a text call takes", (unsigned long long)src->text_bytes);
     const size_t need = sk_trim_fastq_rejects_workspace_bytes(src->text_bytes);
     if (workspace_bytes < need)
-        SK_FQJ_BAD("rejects: workspace must hold sk_trim_fastq_rejects_workspace_bytes(%llu) = %zu bytes",
-                   (unsigned long long)src->text_bytes, need);
-#undef SK_FQJ_BAD
+        SK_BAD(ctx, "rejects: workspace must hold sk_trim_fastq_rejects_workspace_bytes(%llu) = %zu bytes",
+               (unsigned long long)src->text_bytes, need);
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_rejects(src, in, mode, out, flags, workspace, ctx->cu_count, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
@@ -1458,11 +1180,8 @@ int sk_trim_fastq_rejects_device_async(sk_ctx *ctx, const sk_fastq_report_source
 int sk_trim_fastq_rejects_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_rejects_counts *counts)
 {
     if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[FQJ_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
+    if (int rc = read_header(ctx, workspace, h, FQJ_HDR_WORDS, static_cast<hipStream_t>(hip_stream))) return rc;
     counts->records = h[FQJ_H_RECORDS];
     counts->bytes = h[FQJ_H_BYTES];
     counts->reads = h[FQJ_H_READS];
@@ -1509,25 +1228,19 @@ size_t sk_bgzf_workspace_bytes_flags(uint64_t text_bytes, int flags)
 int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uint64_t capacity, int flags, void *workspace,
                          size_t workspace_bytes, void *hip_stream)
 {
-#define SK_BGZF_BAD(...)              \
-    do {                              \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;             \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!in) SK_BGZF_BAD("sk_bgzf_device_async: in is required");
-    if (flags & ~(SK_BGZF_EOF | SK_BGZF_SEARCH)) SK_BGZF_BAD("bgzf: flags %d are unknown", flags);
-    if (!in->text && in->bytes) SK_BGZF_BAD("bgzf: text is NULL with %llu bytes", (unsigned long long)in->bytes);
+    if (!in) SK_BAD(ctx, "sk_bgzf_device_async: in is required");
+    if (flags & ~(SK_BGZF_EOF | SK_BGZF_SEARCH)) SK_BAD(ctx, "bgzf: flags %d are unknown", flags);
+    if (!in->text && in->bytes) SK_BAD(ctx, "bgzf: text is NULL with %llu bytes", (unsigned long long)in->bytes);
     if ((reinterpret_cast<uintptr_t>(in->bytes_dev) | reinterpret_cast<uintptr_t>(in->valid_dev)) & 7)
-        SK_BGZF_BAD("bgzf: bytes_dev and valid_dev must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out) & 15) SK_BGZF_BAD("bgzf: out must be 16-byte aligned");
-    if (!out && capacity) SK_BGZF_BAD("bgzf: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
-    if (in->bytes > (1ull << 60)) SK_BGZF_BAD("bgzf: %llu bytes of text is beyond what one call takes", (unsigned long long)in->bytes);
+        SK_BAD(ctx, "bgzf: bytes_dev and valid_dev must be 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_BAD(ctx, "bgzf: out must be 16-byte aligned");
+    if (!out && capacity) SK_BAD(ctx, "bgzf: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+    if (in->bytes > (1ull << 60)) SK_BAD(ctx, "bgzf: %llu bytes of text is beyond what one call takes", (unsigned long long)in->bytes);
     const size_t need = sk_bgzf_workspace_bytes_flags(in->bytes, flags);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_BGZF_BAD("bgzf: workspace must be 16-byte aligned and hold sk_bgzf_workspace_bytes_flags(%llu, %d) = %zu bytes",
-                    (unsigned long long)in->bytes, flags, need);
-#undef SK_BGZF_BAD
+        SK_BAD(ctx, "bgzf: workspace must be 16-byte aligned and hold sk_bgzf_workspace_bytes_flags(%llu, %d) = %zu bytes",
+               (unsigned long long)in->bytes, flags, need);
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_bgzf(in, out, capacity, flags, workspace, ctx->cu_count, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
@@ -1536,11 +1249,8 @@ int sk_bgzf_device_async(sk_ctx *ctx, const sk_bgzf_input *in, uint8_t *out, uin
 int sk_bgzf_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_bgzf_counts *counts)
 {
     if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[SK_BGZF_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
+    if (int rc = read_header(ctx, workspace, h, SK_BGZF_HDR_WORDS, static_cast<hipStream_t>(hip_stream))) return rc;
     counts->bytes_in = h[SK_BGZF_H_BYTES_IN];
     counts->blocks = h[SK_BGZF_H_BLOCKS];
     counts->stored_blocks = h[SK_BGZF_H_STORED];
@@ -1562,22 +1272,16 @@ size_t sk_bgzf_inflate_workspace_bytes(uint64_t image_bytes)
 int sk_bgzf_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
                                  void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-#define SK_GZ_BAD(...)               \
-    do {                             \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;            \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!image && image_bytes) SK_GZ_BAD("bgzf inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (!image && image_bytes) SK_BAD(ctx, "bgzf inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
     if (image_bytes > SK_INFLATE_MAX_IMAGE)
-        SK_GZ_BAD("bgzf inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
-    if (reinterpret_cast<uintptr_t>(out) & 15) SK_GZ_BAD("bgzf inflate: out must be 16-byte aligned");
-    if (!out && capacity) SK_GZ_BAD("bgzf inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+        SK_BAD(ctx, "bgzf inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_BAD(ctx, "bgzf inflate: out must be 16-byte aligned");
+    if (!out && capacity) SK_BAD(ctx, "bgzf inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
     const size_t need = sk_bgzf_inflate_workspace_bytes(image_bytes);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_GZ_BAD("bgzf inflate: workspace must be 16-byte aligned and hold sk_bgzf_inflate_workspace_bytes(%llu) = %zu bytes",
-                  (unsigned long long)image_bytes, need);
-#undef SK_GZ_BAD
+        SK_BAD(ctx, "bgzf inflate: workspace must be 16-byte aligned and hold sk_bgzf_inflate_workspace_bytes(%llu) = %zu bytes",
+               (unsigned long long)image_bytes, need);
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_bgzf_inflate(image, image_bytes, out, capacity, workspace, static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
@@ -1588,9 +1292,7 @@ int sk_bgzf_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream
     if (!ctx || !workspace || !counts) return SK_EINVAL;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[SK_INFLATE_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
+    if (int rc = read_header(ctx, workspace, h, SK_INFLATE_HDR_WORDS, stream)) return rc;
     memset(counts, 0, sizeof *counts);
     counts->bytes_in = h[SK_INFLATE_H_BYTES_IN];
     counts->members = h[SK_INFLATE_H_MEMBERS];
@@ -1640,54 +1342,54 @@ size_t sk_gzip_inflate_workspace_bytes(uint64_t image_bytes, uint64_t capacity)
 int sk_gzip_inflate_device_async(sk_ctx *ctx, const uint8_t *image, uint64_t image_bytes, uint8_t *out, uint64_t capacity,
                                  void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-#define SK_GZ_BAD(...)               \
-    do {                             \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;            \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!image && image_bytes) SK_GZ_BAD("gzip inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (!image && image_bytes) SK_BAD(ctx, "gzip inflate: image is NULL with %llu bytes", (unsigned long long)image_bytes);
     if (image_bytes > SK_GUNZIP_MAX_IMAGE)
-        SK_GZ_BAD("gzip inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
-    if (reinterpret_cast<uintptr_t>(out) & 15) SK_GZ_BAD("gzip inflate: out must be 16-byte aligned");
-    if (!out && capacity) SK_GZ_BAD("gzip inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
-    if (capacity > (1ull << 60)) SK_GZ_BAD("gzip inflate: a capacity of %llu bytes", (unsigned long long)capacity);
+        SK_BAD(ctx, "gzip inflate: an image of %llu bytes is beyond what one call takes (8 GiB)", (unsigned long long)image_bytes);
+    if (reinterpret_cast<uintptr_t>(out) & 15) SK_BAD(ctx, "gzip inflate: out must be 16-byte aligned");
+    if (!out && capacity) SK_BAD(ctx, "gzip inflate: out is NULL with a capacity of %llu bytes", (unsigned long long)capacity);
+    if (capacity > (1ull << 60)) SK_BAD(ctx, "gzip inflate: a capacity of %llu bytes", (unsigned long long)capacity);
     const uint64_t forced = gzip_forced_chunk();
     sk_gunzip_layout L;
     sk_gunzip_layout_of(image_bytes, capacity, forced, &L);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < L.total)
-        SK_GZ_BAD("gzip inflate: workspace must be 16-byte aligned and hold sk_gzip_inflate_workspace_bytes(%llu, %llu) = %llu bytes",
-                  (unsigned long long)image_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
-#undef SK_GZ_BAD
+        SK_BAD(ctx, "gzip inflate: workspace must be 16-byte aligned and hold sk_gzip_inflate_workspace_bytes(%llu, %llu) = %llu bytes",
+               (unsigned long long)image_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_gunzip(image, image_bytes, out, capacity, forced, workspace, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+// how both gzip finishes begin: the header (words: SKG_H_* of sk_gunzip_block.h) and the counts every call has
+static int gzip_finish_head(sk_ctx *ctx, void *workspace, void *hip_stream, uint64_t h[SK_GUNZIP_HDR_WORDS],
+                            sk_gzip_inflate_counts *counts)
+{
+    int rc = read_header(ctx, workspace, h, SK_GUNZIP_HDR_WORDS, static_cast<hipStream_t>(hip_stream));
+    if (rc != SK_OK) return rc;
+    memset(counts, 0, sizeof *counts);
+    counts->bytes_in = h[SKG_H_BYTES_IN];
+    counts->members = h[SKG_H_MEMBERS];
+    counts->bytes_out = h[SKG_H_BYTES_OUT];
+    counts->stretches = h[SKG_H_STRETCHES];
+    counts->stretches_used = h[SKG_H_USED];
     return SK_OK;
 }
 
 int sk_gzip_inflate_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_gzip_inflate_counts *counts)
 {
     if (!ctx || !workspace || !counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[SK_GUNZIP_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    memset(counts, 0, sizeof *counts);
-    counts->bytes_in = h[0];
-    counts->members = h[1];
-    counts->bytes_out = h[2];
-    counts->stretches = h[3];
-    counts->stretches_used = h[4];
-    const uint64_t key = h[6];
+    if (int rc = gzip_finish_head(ctx, workspace, hip_stream, h, counts)) return rc;
+    const uint64_t key = h[SKG_H_ERROR_KEY];
     if (key != ~0ull) {
         counts->error = (int32_t)(key & 7);
         counts->error_member = key >> 3;
-        counts->error_offset = h[7];
+        counts->error_offset = h[SKG_H_ERROR_OFFSET];
         set_error(ctx, "gzip inflate: member %llu is not valid gzip at byte %llu (reason %d)",
                   (unsigned long long)counts->error_member, (unsigned long long)counts->error_offset, counts->error);
         return SK_EDATA;
     }
-    if (!h[5]) {
+    if (!h[SKG_H_FIT]) {
         set_error(ctx, "gzip inflate: the text needs %llu bytes, more than the capacity", (unsigned long long)counts->bytes_out);
         return SK_ESPACE;
     }
@@ -1705,30 +1407,24 @@ int sk_gzip_inflate_piece_device_async(sk_ctx *ctx, const uint8_t *image, uint64
                                        const sk_gzip_piece_state *state_in, sk_gzip_piece_state *state_out, uint8_t *out,
                                        uint64_t capacity, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-#define SK_GZ_BAD(...)               \
-    do {                             \
-        set_error(ctx, __VA_ARGS__); \
-        return SK_EINVAL;            \
-    } while (0)
     if (!ctx) return SK_EINVAL;
-    if (!piece || !state_in || !state_out) SK_GZ_BAD("gzip piece: piece, state_in or state_out is NULL");
-    if (!image && image_bytes) SK_GZ_BAD("gzip piece: image is NULL with %llu bytes", (unsigned long long)image_bytes);
+    if (!piece || !state_in || !state_out) SK_BAD(ctx, "gzip piece: piece, state_in or state_out is NULL");
+    if (!image && image_bytes) SK_BAD(ctx, "gzip piece: image is NULL with %llu bytes", (unsigned long long)image_bytes);
     if (static_cast<const void *>(state_in) == static_cast<const void *>(state_out))
-        SK_GZ_BAD("gzip piece: state_out is state_in (pieces alternate two states)");
+        SK_BAD(ctx, "gzip piece: state_out is state_in (pieces alternate two states)");
     if ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 15)
-        SK_GZ_BAD("gzip piece: the states must be 16-byte aligned");
-    if (piece->reserved) SK_GZ_BAD("gzip piece: reserved must be 0");
+        SK_BAD(ctx, "gzip piece: the states must be 16-byte aligned");
+    if (piece->reserved) SK_BAD(ctx, "gzip piece: reserved must be 0");
     if (piece->window_bytes == 0 || piece->window_bytes > SK_GUNZIP_MAX_WINDOW)
-        SK_GZ_BAD("gzip piece: a window of %llu bytes (1 .. 8 GiB)", (unsigned long long)piece->window_bytes);
-    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) SK_GZ_BAD("gzip piece: out must be 16-byte aligned and not NULL");
-    if (capacity > (1ull << 60)) SK_GZ_BAD("gzip piece: a capacity of %llu bytes", (unsigned long long)capacity);
+        SK_BAD(ctx, "gzip piece: a window of %llu bytes (1 .. 8 GiB)", (unsigned long long)piece->window_bytes);
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) SK_BAD(ctx, "gzip piece: out must be 16-byte aligned and not NULL");
+    if (capacity > (1ull << 60)) SK_BAD(ctx, "gzip piece: a capacity of %llu bytes", (unsigned long long)capacity);
     const uint64_t forced = gzip_forced_chunk();
     sk_gunzip_piece_layout L;
     sk_gunzip_piece_layout_of(piece->window_bytes, capacity, forced, &L);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < L.total)
-        SK_GZ_BAD("gzip piece: workspace must be 16-byte aligned and hold sk_gzip_inflate_piece_workspace_bytes(%llu, %llu) = %llu bytes",
-                  (unsigned long long)piece->window_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
-#undef SK_GZ_BAD
+        SK_BAD(ctx, "gzip piece: workspace must be 16-byte aligned and hold sk_gzip_inflate_piece_workspace_bytes(%llu, %llu) = %llu bytes",
+               (unsigned long long)piece->window_bytes, (unsigned long long)capacity, (unsigned long long)L.total);
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_gunzip_piece(image, image_bytes, piece, state_in, state_out, out, capacity, forced, workspace,
                                        static_cast<hipStream_t>(hip_stream)));
@@ -1739,18 +1435,9 @@ int sk_gzip_inflate_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_
                                         sk_gzip_piece_counts *piece_counts)
 {
     if (!ctx || !workspace || !counts || !piece_counts) return SK_EINVAL;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     uint64_t h[SK_GUNZIP_HDR_WORDS];
-    SK_HIP(ctx, hipSetDevice(ctx->device));
-    SK_HIP(ctx, hipMemcpyAsync(h, workspace, sizeof h, hipMemcpyDeviceToHost, stream));
-    SK_HIP(ctx, hipStreamSynchronize(stream));
-    memset(counts, 0, sizeof *counts);
+    if (int rc = gzip_finish_head(ctx, workspace, hip_stream, h, counts)) return rc;
     memset(piece_counts, 0, sizeof *piece_counts);
-    counts->bytes_in = h[0];
-    counts->members = h[1];
-    counts->bytes_out = h[2];
-    counts->stretches = h[3];
-    counts->stretches_used = h[4];
     piece_counts->pos_bit = h[SK_GUNZIP_H_P_POS_BIT];
     piece_counts->in_member = h[SK_GUNZIP_H_P_IN_MEMBER];
     if ((h[SK_GUNZIP_H_P_POS_BIT] >> 3) >= h[SK_GUNZIP_H_P_IMAGE_OFFSET])
@@ -1774,10 +1461,7 @@ int sk_gzip_inflate_piece_device_finish(sk_ctx *ctx, void *workspace, void *hip_
                   (unsigned long long)counts->bytes_out);
         return SK_ESPACE;
     }
-    if (status) {
-        set_error(ctx, "gzip piece: the state's position is outside the image handed in");
-        return SK_EINVAL;
-    }
+    if (status) SK_BAD(ctx, "gzip piece: the state's position is outside the image handed in");
     return SK_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "sickle_amd.h"
+#include "sk_fastq_words.h"
 
 #define SK_TILE_THREADS 256
 #define SK_TILE_WAVES (SK_TILE_THREADS / 64)
@@ -158,26 +159,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 #define SK_FQ_CHUNK_BYTES 65536u
 #define SK_FQ_BLOCK_READS 2048u
 #define SK_FQ_BLOCK_WORDS 8u
-#define SK_FQ_HDR_WORDS 32u
-#define SK_FQ_H_LINES 0        // [2] lines of each input
-#define SK_FQ_H_RECORDS 2      // [2] complete records of each input
-#define SK_FQ_H_FMT 4          // (read << 3) | SK_FQ_* of the lowest malformed record, or ~0
-#define SK_FQ_H_NREAL 5        // reads of the packed batch that are records (the rest are empty)
-#define SK_FQ_H_PACKED 6       // bytes of the packed qual (and seq)
-#define SK_FQ_H_OUT_RECORDS 7  // [3]
-#define SK_FQ_H_OUT_BYTES 10   // [3]
-#define SK_FQ_H_FIT 13         // [3] produced, no error, within its capacities: the emission writes it
-#define SK_FQ_H_PRODUCED 16    // [3] out[o].text != NULL for an output of the mode
-#define SK_FQ_H_RANGE 19       // the stream's range-error word as the emission saw it
-#define SK_FQ_H_MODE 20        // the call's framing mode (SK_TRIM_PE_INTERLEAVED for SK_TRIM_PE_COMBO_ALL)
-// Piece calls (sk_trim_fastq_piece_device_async with piece != NULL) use words 21..29, which are otherwise the ordered
-// calls' (sk_fastq_order.h); an ordered piece keeps these here and its order words in an extension block (below).
-#define SK_FQP_H_START 21      // [2] s_i: the window's first byte, offset in text[i]
-#define SK_FQP_H_END 23        // [2] n_i: the window's end (sk_trim_fastq_piece_words' end)
-#define SK_FQP_H_CONSUMED 25   // [2] offset in text[i] of the first byte the piece did not consume
-#define SK_FQP_H_OK 27         // 1 iff no format error, the range-error word clear at both looks, every produced output fitted
-#define SK_FQP_H_RANGE0 28     // the stream's range-error word as the frame scan saw it, before the piece's own scan
-#define SK_FQP_H_MORE 29       // the piece's `more`
+// SK_FQ_HDR_WORDS and the header's words, SK_FQ_H_* and the piece calls' SK_FQP_H_*: sk_fastq_words.h (no HIP: the host reads them too)
 struct sk_fq_layout {
     uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
 };
