@@ -1333,6 +1333,102 @@ int sk_trim_fastq_rejects_device_async(sk_ctx *ctx, const sk_fastq_report_source
 int sk_trim_fastq_rejects_device_finish(sk_ctx *ctx, void *workspace, void *hip_stream, sk_fastq_rejects_counts *counts);
 int sk_trim_fastq_rejects_output_words(void *rejects_workspace, const uint64_t **bytes_dev, const uint64_t **written_dev);
 
+/*
+ * The adapters: where the reads run into a 3' adapter, on the device, over the workspace AND the texts of a text call that
+ * has been enqueued on the same stream: per read the leftmost occurrence of up to eight adapter sequences, summed into
+ * exact integer counts (FastQC's adapter content; the adapter bases that sickle's window trim leaves in the output; the
+ * mates whose clip points agree) and, optionally, written as one clip point per read.  Nothing acts on the result: the
+ * text call's output is what it was.  This comment is the normative text; the rule as code is
+ * sickle_amd/csrc/sk_fastq_adapters.h.  The host CLI does not use it.
+ *
+ * The set (sk_fastq_adapter_set, host memory; the call reads it before it returns): n adapters, 1 .. SK_FQ_ADAPTERS_MAX;
+ * len[a] in 1 .. SK_FQ_ADAPTER_MAX_LEN; seq[a][0 .. len[a]) bytes from "ACGTacgt" only, compared without regard to case
+ * (the bytes behind len[a] play no part); min_overlap >= 1 and <= every len[a]; max_mismatch_permille in 0 .. 500;
+ * reserved 0.
+ * Reads are the report's: read r of the call's packed batch with r below the reads the call trimmed.  A dropped odd record,
+ * a piece's carry and the records behind an ordered call's last batch are not reads.  In the pair framings reads 2k and
+ * 2k + 1 are pair k, where both are reads.
+ * The seq line of read r is the bases': found through the call's record descriptors in text[0], or for SK_TRIM_PE_SPLIT in
+ * text[r & 1]; its length L is offsets[r + 1] - offsets[r]; its bytes are the text's, with params->trunc_n or without.
+ * Matching.  A read byte b matches the adapter base c (upper case) iff (b & 0xDF) == c.  'N', IUPAC codes, '\r' and bytes
+ * >= 0x80 match nothing.
+ * A hit.  For adapter a of length A and a start p with 0 <= p <= L - min_overlap the overlap is v = min(A, L - p) and m is
+ * the number of bytes among read[p .. p + v) that do not match adapter[0 .. v).  (a, p) is a hit iff v >= min_overlap and
+ * m <= floor(v * max_mismatch_permille / 1000).  The read's hit is the hit with the lowest p, among the adapters at that p
+ * the one with the lowest a; v and m are that hit's.  A read shorter than min_overlap has none.
+ *   calls, calls_failed   calls that added / that did not (below)
+ *   reads, kept           as in the report
+ *   reads_hit             reads with a hit;  reads_hit_kept: kept reads with a hit
+ *   hits[a]               reads whose hit is adapter a
+ *   hits_full             hits with v == A;  hits_at_0: hits with p == 0 (no insert at all)
+ *   mismatches            sum of m over the hits;  bases_behind: sum of L - p over the hits
+ *   reads_hit_out         kept reads with a hit and p < three: adapter bases survive the quality trim
+ *   bases_hit_out         sum over those reads of three - max(p, five)
+ *   pairs_both, pairs_one pairs with a hit in both mates, in exactly one; both 0 for SK_TRIM_SE
+ *   pairs_same_clip       pairs with a hit in both mates and equal p, the signature of a read-through
+ *   reserved              zero
+ * Arrays (sk_fastq_adapters_out, may be NULL, as may each array in it; device memory that the caller owns):
+ * pos[8 * pos_bins] (uint64_t): entry a * pos_bins + min(p, pos_bins - 1) counts the hits of adapter a at p; pos_bins <=
+ * SK_FQ_ADAPTERS_MAX_POS_BINS; FastQC's cumulative curve is a prefix sum that the caller takes.  overlap[8 * 65]
+ * (uint64_t): entry a * 65 + v.  Both accumulate like the struct.  clip[clip_capacity] (uint32_t, 4-byte aligned): one
+ * entry per read of THIS call, in the call's read numbering: a << 24 | p for a hit (p < 2^24 by SK_MAX_READ_LEN),
+ * SK_FQ_CLIP_NONE for a read without one.  Entries at or beyond clip_capacity, and at or beyond the call's reads, are never
+ * written; clip does not accumulate, and SK_FQ_ADAPTERS_RESET does not touch it.
+ * src is the report's source descriptor.  in and mode are what the text call was given; the texts are required, and
+ * in->bytes bound every load of a seq byte.
+ * Validity is the bases': the report's, from the call's own workspace (a format or range verdict, a void piece,
+ * SK_ELONGLINE, a full batch table), and a mode whose framing mode differs from the one the text call recorded counts as
+ * failed too.  A call that does not add increments calls_failed and touches nothing else, neither in the struct nor in
+ * pos, overlap or clip.  SK_ESPACE of the text call does not matter: a counting call is searched in full.
+ * When.  On the text call's stream, behind it, before the workspace AND THE TEXTS are reused.  It only enqueues kernels: no
+ * copy, no allocation, no wait.  SK_FQ_ADAPTERS_RESET zeroes the struct, pos and overlap first, by a kernel of its own; a
+ * zeroed struct is a valid start.  Calls that add to one struct must be on one stream.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: the bases' cases (ctx, src, src->workspace, adapters_dev or in
+ * NULL; a workspace that is not 16-byte aligned, a struct or a uint64_t array that is not 8-byte aligned; an unknown kind,
+ * mode or flags; src->reserved != 0; SK_TRIM_PE_SPLIT and text[1] NULL, another mode and text[1] not NULL; text[0] NULL with
+ * bytes[0] != 0); set NULL or a set outside the bounds above; clip given with clip_capacity 0 or not 4-byte aligned;
+ * pos_bins of 0 with pos given, or above its limit.
+ */
+#define SK_FQ_ADAPTERS_RESET 1
+#define SK_FQ_ADAPTERS_MAX 8u
+#define SK_FQ_ADAPTER_MAX_LEN 64u
+#define SK_FQ_ADAPTERS_MAX_POS_BINS 2048u
+#define SK_FQ_ADAPTERS_OVERLAP_BINS 65u
+#define SK_FQ_CLIP_NONE 0xFFFFFFFFu
+
+typedef struct {
+    uint32_t n;
+    uint32_t len[8];
+    uint8_t seq[8][64];
+    uint32_t min_overlap;
+    uint32_t max_mismatch_permille;
+    uint32_t reserved; /* 0 */
+} sk_fastq_adapter_set; /* host memory, 560 bytes */
+
+typedef struct {
+    uint64_t calls, calls_failed;
+    uint64_t reads, kept;
+    uint64_t reads_hit, reads_hit_kept;
+    uint64_t hits[8];
+    uint64_t hits_full, hits_at_0;
+    uint64_t mismatches, bases_behind;
+    uint64_t reads_hit_out, bases_hit_out;
+    uint64_t pairs_both, pairs_one, pairs_same_clip;
+    uint64_t reserved;
+} sk_fastq_adapters; /* device memory, 8-byte aligned, 192 bytes */
+
+typedef struct {
+    uint64_t *pos;     /* device, 8-byte aligned, [8 * pos_bins], or NULL */
+    uint64_t pos_bins;
+    uint64_t *overlap; /* device, 8-byte aligned, [8 * SK_FQ_ADAPTERS_OVERLAP_BINS], or NULL */
+    uint32_t *clip;    /* device, 4-byte aligned, [clip_capacity], or NULL */
+    uint64_t clip_capacity;
+} sk_fastq_adapters_out;
+
+int sk_trim_fastq_adapters_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                        const sk_fastq_adapter_set *set, sk_fastq_adapters *adapters_dev,
+                                        const sk_fastq_adapters_out *out, int flags, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

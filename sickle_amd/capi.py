@@ -53,7 +53,15 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_ordered_piece_device_finish", "sk_trim_fastq_report_device_async",
            "sk_trim_fastq_audit_device_async", "sk_trim_fastq_bases_device_async",
            "sk_trim_fastq_rejects_workspace_bytes", "sk_trim_fastq_rejects_bound", "sk_trim_fastq_rejects_device_async",
-           "sk_trim_fastq_rejects_device_finish", "sk_trim_fastq_rejects_output_words")
+           "sk_trim_fastq_rejects_device_finish", "sk_trim_fastq_rejects_output_words",
+           "sk_trim_fastq_adapters_device_async")
+# sk_trim_fastq_adapters_device_async (include/sickle_amd.h)
+SK_FQ_ADAPTERS_RESET = 1
+SK_FQ_ADAPTERS_MAX = 8
+SK_FQ_ADAPTER_MAX_LEN = 64
+SK_FQ_ADAPTERS_MAX_POS_BINS = 2048
+SK_FQ_ADAPTERS_OVERLAP_BINS = 65
+SK_FQ_CLIP_NONE = 0xFFFFFFFF
 # sk_trim_fastq_rejects_device_async (include/sickle_amd.h)
 SK_FQ_REJECTS_PAIRS = 1
 # sk_trim_fastq_bases_device_async (include/sickle_amd.h)
@@ -341,6 +349,109 @@ class _BasesBuffers:
             G = SK_FQ_BASES_GC_BINS
             b["gc_in"], b["gc_out"] = w[at:at + G].copy(), w[at + G:at + 2 * G].copy()
         return b
+
+
+class FastqAdapterSet(C.Structure):
+    """sk_fastq_adapter_set (host memory)"""
+    _fields_ = [("n", C.c_uint32), ("len", C.c_uint32 * 8), ("seq", (C.c_uint8 * 64) * 8), ("min_overlap", C.c_uint32),
+                ("max_mismatch_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def adapter_set(seqs, min_overlap=3, max_mismatch_permille=100):
+    """-> the FastqAdapterSet of up to eight adapter sequences (str or bytes).  Only what the struct cannot hold is
+    refused here (ValueError); everything else is the call's to refuse (SK_EINVAL)."""
+    seqs = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in seqs]
+    if len(seqs) > SK_FQ_ADAPTERS_MAX or any(len(s) > SK_FQ_ADAPTER_MAX_LEN for s in seqs):
+        raise ValueError("adapters: at most %d sequences of at most %d bases" % (SK_FQ_ADAPTERS_MAX, SK_FQ_ADAPTER_MAX_LEN))
+    st = FastqAdapterSet()
+    st.n, st.min_overlap, st.max_mismatch_permille = len(seqs), int(min_overlap), int(max_mismatch_permille)
+    for a, s in enumerate(seqs):
+        st.len[a] = len(s)
+        for j, b in enumerate(s):
+            st.seq[a][j] = b
+    return st
+
+
+class FastqAdapters(C.Structure):
+    """sk_fastq_adapters: every member is a uint64_t"""
+    _fields_ = [("calls", C.c_uint64), ("calls_failed", C.c_uint64), ("reads", C.c_uint64), ("kept", C.c_uint64),
+                ("reads_hit", C.c_uint64), ("reads_hit_kept", C.c_uint64), ("hits", C.c_uint64 * 8),
+                ("hits_full", C.c_uint64), ("hits_at_0", C.c_uint64), ("mismatches", C.c_uint64),
+                ("bases_behind", C.c_uint64), ("reads_hit_out", C.c_uint64), ("bases_hit_out", C.c_uint64),
+                ("pairs_both", C.c_uint64), ("pairs_one", C.c_uint64), ("pairs_same_clip", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        """the members but `reserved`, as ints; hits as a list of eight"""
+        return {name: (list(getattr(self, name)) if name == "hits" else int(getattr(self, name)))
+                for name, _ in self._fields_ if name != "reserved"}
+
+
+ADAPTERS_WORDS = C.sizeof(FastqAdapters) // 8
+
+
+class FastqAdaptersOut(C.Structure):
+    """sk_fastq_adapters_out"""
+    _fields_ = [("pos", C.c_void_p), ("pos_bins", C.c_uint64), ("overlap", C.c_void_p), ("clip", C.c_void_p),
+                ("clip_capacity", C.c_uint64)]
+
+
+class _AdaptersBuffers:
+    """The set and the device words of one adapters=dict(seqs=[..], min_overlap=3, max_mismatch_permille=100,
+    pos_bins=None, overlap=False, clip=False) of a driver: the sk_fastq_adapters, then pos and overlap where asked for, in
+    one tensor; the clip words are a tensor of their own, which only a driver that knows its reads gives (with_clip)."""
+
+    def __init__(self, adapters, dev, clip_ok=False):
+        import torch
+        if not isinstance(adapters, dict) or "seqs" not in adapters:
+            raise ValueError("adapters: a dict with seqs=[...]")
+        unknown = set(adapters) - {"seqs", "min_overlap", "max_mismatch_permille", "pos_bins", "overlap", "clip"}
+        if unknown:
+            raise ValueError("adapters: unknown keys %r" % sorted(unknown))
+        self.set = adapter_set(adapters["seqs"], adapters.get("min_overlap", 3), adapters.get("max_mismatch_permille", 100))
+        self.pos_bins, self.overlap = int(adapters.get("pos_bins") or 0), bool(adapters.get("overlap", False))
+        self.want_clip = bool(adapters.get("clip", False))
+        if self.want_clip and not clip_ok:
+            raise ValueError("adapters: clip=True is trim_fastq's alone")
+        V = 8 * SK_FQ_ADAPTERS_OVERLAP_BINS if self.overlap else 0
+        self.buf = torch.empty(ADAPTERS_WORDS + 8 * self.pos_bins + V, dtype=torch.int64, device=dev)
+        self.ptr, self.dev, self.clip = self.buf.data_ptr(), dev, None
+        self._out()
+
+    def _out(self):
+        at = lambda words: self.ptr + 8 * (ADAPTERS_WORDS + words)
+        P = self.pos_bins
+        self.out = None
+        if P or self.overlap or self.clip is not None:
+            self.out = FastqAdaptersOut(at(0) if P else None, P, at(8 * P) if self.overlap else None,
+                                        self.clip.data_ptr() if self.clip is not None else None,
+                                        self.clip.numel() if self.clip is not None else 0)
+
+    def with_clip(self, reads):
+        """a clip word per read of a call of at most `reads` reads"""
+        import torch
+        self.clip = torch.empty(max(int(reads), 1), dtype=torch.int32, device=self.dev)
+        self._out()
+
+    def read(self):
+        """-> the adapters as a dict: sk_fastq_adapters's members but `reserved`; pos as a uint64 array of shape
+        (8, pos_bins) and overlap of shape (8, 65), where asked for; with clip words: clip, an int64 tensor with the start
+        per read (-1: no hit), and adapter, an int64 tensor with the adapter's number (-1: no hit)"""
+        w = self.buf.cpu().numpy().view(np.uint64)
+        d = FastqAdapters.from_buffer_copy(w[:ADAPTERS_WORDS].tobytes()).as_dict()
+        at, P = ADAPTERS_WORDS, self.pos_bins
+        if P:
+            d["pos"] = w[at:at + 8 * P].reshape(8, P).copy()
+        at += 8 * P
+        if self.overlap:
+            d["overlap"] = w[at:at + 8 * SK_FQ_ADAPTERS_OVERLAP_BINS].reshape(8, SK_FQ_ADAPTERS_OVERLAP_BINS).copy()
+        if self.clip is not None:
+            import torch
+            words = self.clip[:d["reads"]].to(torch.int64) & 0xFFFFFFFF
+            none = words == SK_FQ_CLIP_NONE
+            d["clip"] = torch.where(none, torch.full_like(words, -1), words & 0xFFFFFF)
+            d["adapter"] = torch.where(none, torch.full_like(words, -1), words >> 24)
+        return d
 
 
 class FastqRejectsCounts(C.Structure):
@@ -681,8 +792,12 @@ def lib():
         L.sk_trim_fastq_bases_device_async.restype = C.c_int
         L.sk_trim_fastq_bases_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                        C.c_int, C.c_void_p, C.POINTER(FastqBasesHists), C.c_int, C.c_void_p]
+        L.sk_trim_fastq_adapters_device_async.restype = C.c_int
+        L.sk_trim_fastq_adapters_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
+                                                          C.c_int, C.POINTER(FastqAdapterSet), C.c_void_p,
+                                                          C.POINTER(FastqAdaptersOut), C.c_int, C.c_void_p]
         L.sk_trim_fastq_audit_device_async.restype = C.c_int
-        L.sk_trim_fastq_audit_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
+        L.sk_trim_fastq_audit_device_async.argtypes =[C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.sk_trim_fastq_rejects_workspace_bytes.restype = C.c_size_t
         L.sk_trim_fastq_rejects_workspace_bytes.argtypes = [C.c_uint64]
@@ -985,6 +1100,20 @@ class Context:
                                                            C.byref(hists) if hists is not None else None,
                                                            SK_FQ_BASES_RESET if reset else 0, stream))
 
+    def trim_fastq_adapters_device_async(self, workspace_ptr, text_bytes, trunc_n, adapters_ptr, text_ptrs, text_bounds, set,
+                                         mode="se", kind="plain", batch_capacity=0, out=None, reset=False, stream=None):
+        """sk_trim_fastq_adapters_device_async on raw device pointers: the adapter search over the workspace and the texts
+        of a text call already enqueued on `stream`.  kind, text_bytes, trunc_n, batch_capacity: as
+        trim_fastq_report_device_async's; text_ptrs, text_bounds, mode: the text call's; set: a FastqAdapterSet
+        (adapter_set(seqs, ..)); adapters_ptr: a sk_fastq_adapters in device memory; out: a FastqAdaptersOut or None.
+        Only enqueues."""
+        src = _report_source(workspace_ptr, kind, trunc_n, text_bytes, batch_capacity)
+        inp = None if text_ptrs is None else C.byref(_fastq_input(text_ptrs, text_bounds))
+        self._check(lib().sk_trim_fastq_adapters_device_async(self._h, C.byref(src), inp, TRIM_MODES.get(mode, mode),
+                                                              C.byref(set) if set is not None else None, adapters_ptr,
+                                                              C.byref(out) if out is not None else None,
+                                                              SK_FQ_ADAPTERS_RESET if reset else 0, stream))
+
     def trim_fastq_rejects_device_async(self, src_workspace_ptr, text_bytes, trunc_n, text_ptrs, text_bounds, out, workspace_ptr,
                                         workspace_bytes, mode="se", kind="plain", batch_capacity=0, pairs=False, stream=None):
         """sk_trim_fastq_rejects_device_async on raw device pointers: the records of the reads that were not kept, over
@@ -1121,7 +1250,7 @@ class Context:
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
                           search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
-                          rejects=False):
+                          rejects=False, adapters=False):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -1160,26 +1289,30 @@ class Context:
         of the reads the piece did not keep ("pairs": both mates of every pair with such a mate), the input's own four
         lines, in read order also with order=; with gz=True BGZF members written through the call's output words, of which
         only the last piece's carry the EOF member.  The entries concatenated are the rejects of the whole file.  .rejects
-        holds the summed records and bytes after the last piece (None until then, and after a failure)."""
+        holds the summed records and bytes after the last piece (None until then, and after a failure).
+        adapters=dict(seqs=[..], ..) as trim_fastq's, without clip: sk_trim_fastq_adapters_device_async behind every piece,
+        over the piece's workspace and its text buffers, with the reset in front of the first piece only; the struct and
+        the histograms of the whole file are read back once into .adapters (None until then, and after a failure)."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects)
+                           audit, bases, rejects, adapters)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
-                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False, rejects=False):
+                       max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False, rejects=False,
+                       adapters=False):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity, report, audit, bases, rejects: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report, audit, bases, rejects, adapters: as in trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects)
+                           audit, bases, rejects, adapters)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
-                         rejects=False):
+                         rejects=False, adapters=False):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -1190,11 +1323,11 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity, report, audit, bases, rejects: as in trim_fastq_stream."""
+        batch_capacity, report, audit, bases, rejects, adapters: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
         st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                         audit, bases, rejects)
+                         audit, bases, rejects, adapters)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1228,7 +1361,7 @@ class Context:
         return call(second)
 
     def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
-                   audit=False, bases=False, rejects=False):
+                   audit=False, bases=False, rejects=False, adapters=False):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -1257,19 +1390,26 @@ class Context:
         both mates of every pair with such a mate, SK_FQ_REJECTS_PAIRS), the input's own four lines, in read order.  A
         counting rejects call behind the counting pass sizes the buffer, the writing one goes behind the writing pass and
         in front of its finish.  counts["rejects"] = {"text": uint8 tensor, "index": int64 tensor of read numbers (None
-        without record_index=True), "records", "bytes", "reads"}.  rejects=False: the call is what it was, to the launch."""
+        without record_index=True), "records", "bytes", "reads"}.  rejects=False: the call is what it was, to the launch.
+        adapters=dict(seqs=[..], min_overlap=3, max_mismatch_permille=100, pos_bins=None, overlap=False, clip=False): the
+        3' adapter search of the writing pass (sk_trim_fastq_adapters_device_async, enqueued behind it, over its workspace
+        and the texts) is returned as counts["adapters"]: sk_fastq_adapters's members as ints (hits: eight) and, where
+        asked for, pos as a uint64 array of shape (8, pos_bins) and overlap of shape (8, 65); with clip=True also clip, an
+        int64 tensor on the device with every read's clip point (-1: no hit), and adapter, the hit's adapter likewise.
+        Nothing acts on the result.  adapters=False: the call is what it was, to the launch, and nothing is allocated."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
                                                                                   record_index, o, report, audit, bases,
-                                                                                  rejects))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects)
+                                                                                  rejects, adapters))
+        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects,
+                                adapters)
 
     def _enqueue_behind(self, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream, rep=None, aud=None, bas=None,
-                        rej=None):
+                        rej=None, adp=None):
         """What follows a driver's text call on its stream, over its workspace and its texts: the report, the audit, the
-        bases, then the rejects, each where its buffers are given (rep, aud, bas: the drivers' buffer objects; rej: the
-        rejects call's workspace tensor, its FastqOutput or None, its flags).  kind: "plain" or "piece"; order: the text
+        bases, then the rejects, then the adapter search, each where its buffers are given (rep, aud, bas, adp: the
+        drivers' buffer objects; rej: the rejects call's workspace tensor, its FastqOutput or None, its flags).  kind: "plain" or "piece"; order: the text
         call's FastqOrder or None; reset: zero what accumulates (not the rejects, which do not).  The audit does without the
         names when a text is empty (no pointer); the bases and the rejects, which need `in`, give an empty text their own
         buffer's address with the bound 0, of which no byte is loaded."""
@@ -1293,9 +1433,13 @@ class Context:
             p, b = own(rws.data_ptr())
             self.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, p, b, out, rws.data_ptr(), rws.numel(), mode=mode,
                                                  kind=kind, batch_capacity=cap, pairs=flags, stream=stream)
+        if adp:
+            p, b = own(adp.ptr)
+            self.trim_fastq_adapters_device_async(ws_ptr, total, trunc_n, adp.ptr, p, b, adp.set, mode=mode, kind=kind,
+                                                  batch_capacity=cap, out=adp.out, reset=reset, stream=stream)
 
     def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False,
-                    rejects=False):
+                    rejects=False, adapters=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1306,6 +1450,7 @@ class Context:
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
+        adp = _AdaptersBuffers(adapters, dev, clip_ok=True) if adapters else None
         rej_out = [None]
         if rejects:
             rej_flags = _rejects_flags(rejects)
@@ -1322,7 +1467,7 @@ class Context:
             # is the wait; the rejects: a counting call behind the counting pass, the writing one behind the writing pass
             self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream,
                                  rep=final and rep, aud=final and aud, bas=final and bas,
-                                 rej=(rws, rej_out[0], rej_flags) if rejects else None)
+                                 rej=(rws, rej_out[0], rej_flags) if rejects else None, adp=final and adp)
             return (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
         counts = run([FastqOutput() for _ in range(3)])
         if rejects:
@@ -1339,6 +1484,8 @@ class Context:
             idx = torch.empty(max(R, 1), dtype=torch.int64, device=dev) if record_index else None
             bufs[o] = (t, idx)
             outs[o] = FastqOutput(t.data_ptr(), B, idx.data_ptr() if record_index else None, R)
+        if adp and adp.want_clip:  # the counting pass has told the reads: a record of each input is a read at most
+            adp.with_clip(sum(counts["records_in"]))
         counts = run(outs, True)
         res = [None] * 3
         for o in used:
@@ -1349,6 +1496,8 @@ class Context:
             counts["audit"] = aud.read()
         if bas:
             counts["bases"] = bas.read()
+        if adp:
+            counts["adapters"] = adp.read()
         if rejects:
             got = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
             counts["rejects"] = {"text": rej_text[:got["bytes"]], "index": rej_idx[:got["records"]] if record_index else None,
@@ -1389,22 +1538,22 @@ class Context:
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
     def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False,
-                      audit=False, bases=False):
+                      audit=False, bases=False, adapters=False):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
         than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
         as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as
-        trim_fastq's, counts["bases"]."""
+        trim_fastq's, counts["bases"].  adapters: as trim_fastq's, counts["adapters"], without clip."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
-                                                                                     search, report, audit, bases))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases)
+                                                                                     search, report, audit, bases, adapters))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases, adapters)
 
     def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False,
-                       bases=False):
+                       bases=False, adapters=False):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
@@ -1429,7 +1578,9 @@ class Context:
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
-        self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream, rep, aud, bas)
+        adp = _AdaptersBuffers(adapters, dev) if adapters else None
+        self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream, rep, aud, bas,
+                             adp=adp)
         for o in used:
             images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1444,6 +1595,8 @@ class Context:
             counts["audit"] = aud.read()
         if bas:
             counts["bases"] = bas.read()
+        if adp:
+            counts["adapters"] = adp.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     # ---- BGZF read on the device --------------------------------------------------------------
@@ -1611,7 +1764,7 @@ class Context:
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
     def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False,
-                         bases=False):
+                         bases=False, adapters=False):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1651,8 +1804,9 @@ class Context:
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
+        adp = _AdaptersBuffers(adapters, dev) if adapters else None
         self._enqueue_behind(ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order, True,
-                             stream, rep, aud, bas)
+                             stream, rep, aud, bas, adp=adp)
         for o in used:
             out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
             zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
@@ -1682,10 +1836,12 @@ class Context:
             counts["audit"] = aud.read()
         if bas:
             counts["bases"] = bas.read()
+        if adp:
+            counts["adapters"] = adp.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
-                kind=None, report=False, audit=False, bases=False):
+                kind=None, report=False, audit=False, bases=False, adapters=False):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
         trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
@@ -1703,7 +1859,7 @@ class Context:
         names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
         enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more.
         report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as trim_fastq's,
-        counts["bases"]."""
+        counts["bases"].  adapters: as trim_fastq_gz's, counts["adapters"]."""
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -1715,11 +1871,11 @@ class Context:
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
                                                                                        max_read_len, o, search, report, audit,
-                                                                                       bases))
+                                                                                       bases, adapters))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
-                                  report=report, audit=audit, bases=bases)
+                                  report=report, audit=audit, bases=bases, adapters=adapters)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -1849,7 +2005,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False):
+                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False, adapters=False):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -1903,6 +2059,8 @@ class FastqStream:
         self._aud = _AuditBuffers(dev) if audit else None
         self.bases = None
         self._bas = _BasesBuffers(bases, dev) if bases else None
+        self.adapters = None
+        self._adp = _AdaptersBuffers(adapters, dev) if adapters else None
         self.rejects = None
         self._rej = bool(rejects)
         if rejects:  # a workspace and a text buffer (an image, a writer workspace) per slot, sized by the slot's text buffers
@@ -1999,7 +2157,7 @@ class FastqStream:
         rej = (self.jws[slot], FastqOutput(self.jout[slot].data_ptr(), self.jcap, None, 0), self._rej_flags) if self._rej else None
         c._enqueue_behind(self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
                           self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream, self._rep, self._aud,
-                          self._bas, rej)
+                          self._bas, rej, self._adp)
         if self._rej and self.gz:
             b, w = c.trim_fastq_rejects_output_words(self.jws[slot].data_ptr())
             c.bgzf_device_async(self.jout[slot].data_ptr(), self.jcap, self.jimg[slot].data_ptr(), self.jimg_cap,
@@ -2103,6 +2261,8 @@ class FastqStream:
             self.audit = self._aud.read()
         if self._bas:
             self.bases = self._bas.read()
+        if self._adp:
+            self.adapters = self._adp.read()
         if self._rej:
             self.rejects = dict(self._rej_sum)
 

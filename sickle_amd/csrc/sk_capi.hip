@@ -14,6 +14,7 @@
 
 #include "sickle_amd.h"
 #include "sk_device.h"
+#include "sk_fastq_adapters.h"
 #include "sk_fastq_rejects.h"
 #include "sk_fastq_verdict.h"
 #include "sk_gunzip_block.h"
@@ -1146,6 +1147,35 @@ int sk_trim_fastq_bases_device_async(sk_ctx *ctx, const sk_fastq_report_source *
     }
     SK_HIP(ctx, hipSetDevice(ctx->device));
     SK_HIP(ctx, sk_launch_fastq_bases(src, in, mode, bases_dev, hists, flags, static_cast<hipStream_t>(hip_stream)));
+    return SK_OK;
+}
+
+// the texts are the data: in is required; the set is read here, on the host
+int sk_trim_fastq_adapters_device_async(sk_ctx *ctx, const sk_fastq_report_source *src, const sk_fastq_input *in, int mode,
+                                        const sk_fastq_adapter_set *set, sk_fastq_adapters *adapters_dev,
+                                        const sk_fastq_adapters_out *out, int flags, void *hip_stream)
+{
+    if (!ctx) return SK_EINVAL;
+    if (!src || !src->workspace || !adapters_dev || !in || !set)
+        SK_BAD(ctx, "adapters: src, src->workspace, adapters_dev, in and set are required");
+    if (int rc = check_source(ctx, "adapters:", src)) return rc;
+    if (reinterpret_cast<uintptr_t>(adapters_dev) & 7) SK_BAD(ctx, "adapters: adapters_dev must be 8-byte aligned");
+    if (flags & ~SK_FQ_ADAPTERS_RESET) SK_BAD(ctx, "adapters: flags %d are unknown", flags);
+    if (int rc = check_texts(ctx, "adapters:", in, mode, true)) return rc;
+    if (const char *why = fqd_set_error(set)) SK_BAD(ctx, "adapters: set: %s", why);
+    if (out) {
+        if ((reinterpret_cast<uintptr_t>(out->pos) | reinterpret_cast<uintptr_t>(out->overlap)) & 7)
+            SK_BAD(ctx, "adapters: pos and overlap must be 8-byte aligned");
+        if (out->pos && out->pos_bins == 0) SK_BAD(ctx, "adapters: pos_bins is 0 with pos given");
+        if (out->pos_bins > SK_FQ_ADAPTERS_MAX_POS_BINS)
+            SK_BAD(ctx, "adapters: pos_bins %llu is above SK_FQ_ADAPTERS_MAX_POS_BINS = %u", (unsigned long long)out->pos_bins,
+                   SK_FQ_ADAPTERS_MAX_POS_BINS);
+        if (reinterpret_cast<uintptr_t>(out->clip) & 3) SK_BAD(ctx, "adapters: clip must be 4-byte aligned");
+        if (out->clip && out->clip_capacity == 0) SK_BAD(ctx, "adapters: clip_capacity is 0 with clip given");
+    }
+    SK_HIP(ctx, hipSetDevice(ctx->device));
+    SK_HIP(ctx, sk_launch_fastq_adapters(src, in, mode, set, adapters_dev, out, flags, ctx->cu_count,
+                                         static_cast<hipStream_t>(hip_stream)));
     return SK_OK;
 }
 

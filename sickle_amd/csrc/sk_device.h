@@ -440,6 +440,14 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_reje
                                                                                     const sk_fastq_output *out, int flags,
                                                                                     void *workspace, int cu_count,
                                                                                     hipStream_t stream);
+// the adapter search over a text call's workspace and texts (sk_fastq_adapters.hip); the arguments have passed the checks
+// of sk_trim_fastq_adapters_device_async
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adapters(const sk_fastq_report_source *src,
+                                                                                     const sk_fastq_input *in, int mode,
+                                                                                     const sk_fastq_adapter_set *set,
+                                                                                     sk_fastq_adapters *adapters_dev,
+                                                                                     const sk_fastq_adapters_out *out, int flags,
+                                                                                     int cu_count, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif

@@ -1,0 +1,351 @@
+// sk_fastq_adapters.hip -- the adapter search over a finished text call's workspace and texts
+// (sk_trim_fastq_adapters_device_async): the rule of sk_fastq_adapters.h on the device, summed into a sk_fastq_adapters and
+// the caller's arrays.
+//
+// Launches on the text call's stream, behind its emission; no inter-workgroup waiting, and the result does not depend on
+// the order of workgroups: every global write is an integer atomic add, but for the reset kernel's stores and the clip
+// words, of which each has one writer.
+//   0 reset   (SK_FQ_ADAPTERS_RESET only) zeroes the struct, pos and overlap
+//   1 search  The pass is bound by instructions, (line length x adapter bases) base comparisons a read, not by bytes, so
+//             it is laid out by reads and not, like the report's and the bases' passes, by packed positions.  A wave takes
+//             64 consecutive reads (whole pairs) a turn: lane j loads read j's bounds, cut and seq start, coalesced, and the
+//             wave then searches the 64 lines one after the other, every lane on the same line, the line's figures
+//             broadcast from lane j.  A line is walked in tiles of 64 starts, lane j the start t0 + j.  Lane j loads ONE
+//             byte a tile, base t + j, and three wave ballots over its code turn the 64 bytes into one 64-bit word per
+//             plane (fqd_planes) in scalar registers: the line is never staged in LDS, and a base is loaded and encoded
+//             once.  The bytes are loaded three tiles ahead of their use, the next line's first three tiles while this
+//             line is searched, so that no compare waits for memory.  The tile's window words are a tile's word and the
+//             next one's; a lane forms its own 64-base window by a funnel shift by its lane number and compares it with
+//             every adapter, whose planes are kernel arguments (fqd_start: two XORs, an OR with the invalid bits, a mask
+//             to the overlap and one popcount per adapter; the kernel is a template on the number of adapters, so that
+//             the loop over them unrolls and their planes stay in scalar registers).  The lowest set bit of the ballot
+//             over the lanes' hits is the lowest start, and that lane names the adapter; the walk of a line ends at its
+//             first tile with a hit.
+//             What a read adds to the struct is summed a word a lane (lane w holds word w: fqd_read_word, fqd_pair_word) in
+//             registers over the wave's reads, then over the workgroup's waves in LDS, then one global atomic per non-zero
+//             word.  pos and overlap take one global atomic per hit, by lane 0; the clip words of a wave's 64 reads leave
+//             in one coalesced store, lane j's the word of read j.
+// Every workgroup takes the call's validity from the header (fqd_valid) and leaves at once when the call does not add.
+// Every descriptor index is bounded by the slots of the section, every offsets index by the reads the section holds, every
+// seq byte by in->bytes[i], a line's length by SK_MAX_READ_LEN: a source that names the wrong layout or the wrong texts
+// gives wrong numbers, no load outside the workspace and the texts, and no unbounded walk.
+#include <hip/hip_runtime.h>
+
+#include "sk_device.h"
+#include "sk_fastq_adapters.h"
+#include "sk_fastq_audit.h"
+#include "sk_fastq_order.h"
+#include "sk_fastq_report.h"
+
+namespace {
+
+typedef unsigned long long fqd_ull;
+
+#define FQD_THREADS 256
+#define FQD_WAVES (FQD_THREADS / 64)
+#define FQD_MAX_BLOCKS 4096u // the groups of reads beyond them are taken in strides of the grid
+
+static_assert(FQD_WORDS <= 64, "a lane holds a word of the struct");
+
+struct fqd_args {
+    const uint64_t *hdr;
+    const uint64_t *order_words; // ordered kinds: where the SK_FQO_H_* words lie
+    const uint64_t *desc;        // 5 words per slot, input 0's slots first
+    const uint64_t *offsets;
+    const sk_cut_dev *cuts;
+    uint64_t *res; // sk_fastq_adapters as FQD_WORDS words
+    uint64_t *pos, *overlap;
+    uint32_t *clip;
+    uint64_t clip_capacity;
+    const uint8_t *text[2];
+    uint64_t bytes[2];
+    uint64_t slots0;     // input 0's slots: input 1's descriptors lie behind them
+    uint64_t slot_bound; // slots of the descriptor section
+    uint64_t n_bound;    // the most reads the packed batch can hold
+    uint32_t pos_bins;
+    int32_t kind;
+    int32_t mode; // the call's framing mode
+    fqd_codes codes;
+};
+
+__device__ __forceinline__ bool fqd_valid(const fqd_args &a)
+{
+    const uint64_t *h = a.hdr;
+    const bool piece = a.kind == SK_FQ_REPORT_PIECE || a.kind == SK_FQ_REPORT_ORDERED_PIECE;
+    const uint64_t range0 = piece ? h[SK_FQP_H_RANGE0] : ~0ull;
+    bool refused = false;
+    if (a.order_words) {
+        refused = a.order_words[SK_FQO_H_LONG] != ~0ull || a.order_words[SK_FQO_H_OVERFLOW] != 0;
+        if (a.kind == SK_FQ_REPORT_ORDERED_PIECE && a.order_words[SK_FQOP_X_INHERITED]) refused = true; // void
+    }
+    return (int64_t)h[SK_FQ_H_MODE] == (int64_t)a.mode && fqp_call_valid(h[SK_FQ_H_FMT], h[SK_FQ_H_RANGE], range0, refused);
+}
+
+__device__ __forceinline__ int fqd_input(const fqd_args &a, uint64_t r) { return a.mode == SK_TRIM_PE_SPLIT ? (int)(r & 1) : 0; }
+
+// where the seq line of read r starts in its text, never beyond the text; the text's length: no descriptor slot for it
+__device__ __forceinline__ uint64_t fqd_seq_start(const fqd_args &a, uint64_t r)
+{
+    const int i = fqd_input(a, r);
+    const uint64_t k = a.mode == SK_TRIM_PE_SPLIT ? r >> 1 : r;
+    const uint64_t slot = (i ? a.slots0 : 0) + k;
+    if (slot >= a.slot_bound) return a.bytes[i];
+    return min(min(a.desc[5 * slot + 1], a.bytes[i]) + 1, a.bytes[i]);
+}
+
+// a seq line as the wave sees it: wave-uniform
+struct fqd_line {
+    const uint8_t *text;
+    uint64_t bytes, sq, L; // the text's length, where the line starts in it, its length
+};
+
+// lane j's byte of bases [t, t + 64) of a line: base t + j as the text has it; 0, which is no letter, for a base at or
+// beyond L and for a byte at or beyond the text's end
+__device__ __forceinline__ uint32_t fqd_raw(const fqd_line &ln, uint64_t t, int lane)
+{
+    const uint64_t i = t + (uint64_t)lane;
+    const bool in = i < ln.L && ln.sq + i < ln.bytes;
+    if (ln.bytes == 0) return 0u; // uniform: no text, no load
+    // (a lane without a byte of its own loads the line's first, or the text's last where the line starts at its end: one
+    // unconditional load instead of a branch over one, and from the cache lines the other lanes load)
+    const uint32_t b = ln.text[in ? ln.sq + i : min(ln.sq, ln.bytes - 1)];
+    return in ? b : 0u;
+}
+
+// the wave's 64 bytes as a word per plane: three ballots over the lanes' codes
+__device__ __forceinline__ fqd_planes fqd_ballot_planes(uint32_t raw)
+{
+    const uint32_t code = fqd_code((uint8_t)raw);
+    fqd_planes w;
+    w.lo = __builtin_amdgcn_ballot_w64((code & 1u) != 0);
+    w.hi = __builtin_amdgcn_ballot_w64((code & 2u) != 0);
+    w.valid = __builtin_amdgcn_ballot_w64(code < 4u);
+    return w;
+}
+
+__device__ __forceinline__ uint64_t fqd_uniform(uint64_t x)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+    return (uint64_t)hi << 32 | lo;
+}
+
+// ------------------------------------------------------------------------------------------
+// 0 reset
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FQD_THREADS) sk_fq_adapters_reset_kernel(fqd_args a)
+{
+    const uint32_t i = blockIdx.x * FQD_THREADS + threadIdx.x;
+    if (i < FQD_WORDS) a.res[i] = 0;
+    if (a.pos && i < 8u * a.pos_bins) a.pos[i] = 0;
+    if (a.overlap && i < 8u * SK_FQ_ADAPTERS_OVERLAP_BINS) a.overlap[i] = 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// 1 the search
+// ------------------------------------------------------------------------------------------
+// lane j's word of x (j wave-uniform), in every lane
+__device__ __forceinline__ uint32_t fqd_lane32(uint32_t x, int j) { return (uint32_t)__builtin_amdgcn_readlane((int)x, j); }
+__device__ __forceinline__ uint64_t fqd_lane64(uint64_t x, int j)
+{
+    return (uint64_t)fqd_lane32((uint32_t)(x >> 32), j) << 32 | fqd_lane32((uint32_t)x, j);
+}
+
+// The hit of a line (wave-uniform in and out; every lane returns the same fqd_read, whose L is the line's).  c0, c1, c2: the
+// lanes' bytes of the line's first three tiles (fqd_raw), loaded by the caller ahead of time.  Further tiles are loaded
+// three tiles ahead of their use, so that a load's latency is other tiles' compares.
+template <uint32_t N>
+__device__ __forceinline__ fqd_read fqd_search_line(const fqd_codes &codes, const fqd_line &ln, uint32_t c0, uint32_t c1, uint32_t c2, int lane)
+{
+    fqd_read rd = {};
+    rd.L = ln.L;
+    const uint64_t L = ln.L, mo = codes.min_overlap;
+    if (L < mo) return rd;
+    const uint64_t last = L - mo; // the last start
+    fqd_planes w0 = fqd_ballot_planes(c0);
+    for (uint64_t t0 = 0; t0 <= last; t0 += 64) { // at most 2^18 tiles
+        const uint32_t c3 = t0 + 192 < L ? fqd_raw(ln, t0 + 192, lane) : 0u;
+        const fqd_planes w1 = fqd_ballot_planes(c1);
+        const uint64_t p = t0 + (uint64_t)lane;
+        uint32_t ad = FQD_NO_ADAPTER;
+        if (p <= last) {
+            const uint64_t lo = fqd_funnel(w0.lo, w1.lo, (uint32_t)lane), hi = fqd_funnel(w0.hi, w1.hi, (uint32_t)lane);
+            const uint64_t valid = fqd_funnel(w0.valid, w1.valid, (uint32_t)lane);
+            ad = fqd_start(&codes, N, lo, hi, valid, L, p); // N == codes.n
+        }
+        const uint64_t hits = __builtin_amdgcn_ballot_w64(ad != FQD_NO_ADAPTER);
+        if (hits) { // uniform: the lowest lane with a hit holds the lowest start; its overlap and mismatches once more
+            const uint32_t src = (uint32_t)__builtin_ctzll(hits);
+            rd.hit = 1;
+            rd.a = fqd_lane32(ad, (int)src);
+            rd.p = t0 + (uint64_t)src;
+            uint32_t A = 0;
+            uint64_t ad_lo = 0, ad_hi = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 8; ++j) { // (no runtime index into the kernel's arguments)
+                A = rd.a == j ? codes.len[j] : A;
+                ad_lo = rd.a == j ? codes.lo[j] : ad_lo;
+                ad_hi = rd.a == j ? codes.hi[j] : ad_hi;
+            }
+            rd.A = A;
+            rd.v = fqd_overlap(A, L, rd.p);
+            rd.m = fqd_mismatches(fqd_funnel(w0.lo, w1.lo, src), fqd_funnel(w0.hi, w1.hi, src), fqd_funnel(w0.valid, w1.valid, src),
+                                  ad_lo, ad_hi, rd.v);
+            return rd;
+        }
+        w0 = w1;
+        c1 = c2;
+        c2 = c3;
+    }
+    return rd;
+}
+
+// N: the set's adapters, so that the loop over them unrolls and their planes stay in scalar registers
+template <uint32_t N>
+__global__ void __launch_bounds__(FQD_THREADS) sk_fq_adapters_kernel(fqd_args a)
+{
+    __shared__ fqd_ull s_sum[FQD_WORDS];
+    const int t = threadIdx.x, lane = t & 63;
+    const bool valid = fqd_valid(a); // uniform
+    if (blockIdx.x == 0 && t == 0) atomicAdd(reinterpret_cast<fqd_ull *>(a.res + (valid ? FQD_W_CALLS : FQD_W_CALLS_FAILED)), 1ull);
+    if (!valid) return;
+    const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    if (R == 0) return;
+    if (t < FQD_WORDS) s_sum[t] = 0;
+    __syncthreads();
+    const bool pairs = a.mode != SK_TRIM_SE, split = a.mode == SK_TRIM_PE_SPLIT;
+    const uint64_t groups = (R + 63) / 64; // 64 consecutive reads, whole pairs, a wave's turn
+    const uint64_t wave = fqd_uniform((uint64_t)blockIdx.x * FQD_WAVES + (uint64_t)(t >> 6)), n_waves = (uint64_t)gridDim.x * FQD_WAVES;
+    uint64_t acc = 0; // lane w: what the wave's reads add to word w
+    for (uint64_t g = wave; g < groups; g += n_waves) {
+        // lane j: where read 64 g + j lies and how it was cut, by coalesced loads
+        const uint64_t base = 64 * g, mine = base + (uint64_t)lane;
+        const int n = (int)min((uint64_t)64, R - base); // uniform
+        uint64_t my_L = 0, my_sq = 0;
+        sk_cut_dev my_cut = {0, -1};
+        if (mine < R) {
+            const uint64_t b = a.offsets[mine], e = a.offsets[mine + 1]; // mine < R <= n_bound
+            my_L = e > b ? min(e - b, (uint64_t)SK_MAX_READ_LEN_DEV) : 0;
+            my_sq = fqd_seq_start(a, mine);
+            my_cut = a.cuts[mine];
+        }
+        auto line = [&](int j) {
+            const int i = split ? j & 1 : 0; // base is even: read base + j lies in input j & 1
+            fqd_line ln;
+            ln.text = a.text[i];
+            ln.bytes = a.bytes[i];
+            ln.sq = fqd_lane64(my_sq, j);
+            ln.L = fqd_lane64(my_L, j);
+            return ln;
+        };
+        uint32_t my_clip = SK_FQ_CLIP_NONE;
+        fqd_read prev = {};
+        // read j + 1's first three tiles are loaded while read j is searched
+        fqd_line cur = line(0);
+        uint32_t c0 = fqd_raw(cur, 0, lane), c1 = fqd_raw(cur, 64, lane), c2 = fqd_raw(cur, 128, lane);
+        for (int j = 0; j < n; ++j) {
+            fqd_line nxt = cur;
+            uint32_t n0 = 0, n1 = 0, n2 = 0;
+            if (j + 1 < n) {
+                nxt = line(j + 1);
+                n0 = fqd_raw(nxt, 0, lane);
+                n1 = fqd_raw(nxt, 64, lane);
+                n2 = fqd_raw(nxt, 128, lane);
+            }
+            fqd_read rd = fqd_search_line<N>(a.codes, cur, c0, c1, c2, lane);
+            rd.five = (int32_t)fqd_lane32((uint32_t)my_cut.five, j);
+            rd.three = (int32_t)fqd_lane32((uint32_t)my_cut.three, j);
+            if (!rd.hit) { // uniform, and most reads
+                acc += fqd_miss_word((uint32_t)lane, &rd);
+            } else if (lane >= FQD_W_READS && lane <= FQD_W_BASES_HIT_OUT) {
+                acc += fqd_read_word((uint32_t)lane, &rd);
+            }
+            if (pairs && (j & 1) && lane >= FQD_W_PAIRS_BOTH && lane <= FQD_W_PAIRS_SAME_CLIP)
+                acc += fqd_pair_word((uint32_t)lane, &prev, &rd); // reads base + j - 1 and base + j are a pair, both below R
+            if (lane == j) my_clip = fqd_clip_word(&rd);
+            if (lane == 0 && rd.hit) {
+                if (a.pos) atomicAdd(reinterpret_cast<fqd_ull *>(a.pos + (uint64_t)rd.a * a.pos_bins + fqp_bin(rd.p, a.pos_bins)), 1ull);
+                if (a.overlap) atomicAdd(reinterpret_cast<fqd_ull *>(a.overlap + rd.a * SK_FQ_ADAPTERS_OVERLAP_BINS + rd.v), 1ull);
+            }
+            prev = rd;
+            cur = nxt;
+            c0 = n0;
+            c1 = n1;
+            c2 = n2;
+        }
+        if (a.clip && mine < R && mine < a.clip_capacity) a.clip[mine] = my_clip; // the group's words in one store
+    }
+    if (lane < FQD_WORDS && acc) atomicAdd(&s_sum[lane], (fqd_ull)acc);
+    __syncthreads();
+    if (t >= FQD_W_READS && t < FQD_W_RESERVED && s_sum[t]) atomicAdd(reinterpret_cast<fqd_ull *>(a.res + t), s_sum[t]);
+}
+
+} // namespace
+
+// the arguments have passed the checks of sk_trim_fastq_adapters_device_async (sk_capi.hip)
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adapters(const sk_fastq_report_source *src,
+                                                                                     const sk_fastq_input *in, int mode,
+                                                                                     const sk_fastq_adapter_set *set,
+                                                                                     sk_fastq_adapters *adapters_dev,
+                                                                                     const sk_fastq_adapters_out *out, int flags,
+                                                                                     int cu_count, hipStream_t stream)
+{
+    sk_fq_layout L;
+    sk_fq_layout_of(src->text_bytes, src->trunc_n, &L);
+    const uint8_t *base = static_cast<const uint8_t *>(src->workspace);
+    uint64_t shift = 0;
+    fqd_args a = {};
+    a.hdr = reinterpret_cast<const uint64_t *>(base);
+    if (src->kind == SK_FQ_REPORT_ORDERED) {
+        shift = sk_fq_order_shift(src->batch_capacity);
+        a.order_words = a.hdr;
+    } else if (src->kind == SK_FQ_REPORT_ORDERED_PIECE) {
+        shift = sk_fq_order_piece_shift(src->batch_capacity);
+        a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
+    }
+    a.desc = reinterpret_cast<const uint64_t *>(base + shift + L.desc);
+    a.offsets = reinterpret_cast<const uint64_t *>(base + shift + L.offsets);
+    a.cuts = reinterpret_cast<const sk_cut_dev *>(base + shift + L.cuts);
+    a.res = reinterpret_cast<uint64_t *>(adapters_dev);
+    a.kind = (int32_t)src->kind;
+    a.mode = fqa_framing_mode(mode);
+    a.n_bound = 2 * ((src->text_bytes + 2) / 16) + 2; // N of sk_fq_layout_of: the offsets and cuts sections hold this many reads
+    a.slot_bound = (L.offsets - L.desc) / 40;
+    const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
+    for (int i = 0; i < n_in; ++i) {
+        a.text[i] = static_cast<const uint8_t *>(in->text[i]);
+        a.bytes[i] = in->text[i] ? in->bytes[i] : 0;
+    }
+    a.slots0 = sk_fq_slots(a.bytes[0]);
+    if (out) {
+        a.pos = out->pos;
+        a.pos_bins = out->pos ? (uint32_t)out->pos_bins : 0;
+        a.overlap = out->overlap;
+        a.clip = out->clip;
+        a.clip_capacity = out->clip ? out->clip_capacity : 0;
+    }
+    fqd_encode_set(set, &a.codes);
+    const dim3 threads(FQD_THREADS);
+    if (flags & SK_FQ_ADAPTERS_RESET) {
+        uint32_t words = 8u * a.pos_bins;
+        if (words < 8u * SK_FQ_ADAPTERS_OVERLAP_BINS) words = 8u * SK_FQ_ADAPTERS_OVERLAP_BINS;
+        hipLaunchKernelGGL(sk_fq_adapters_reset_kernel, dim3((words + FQD_THREADS - 1) / FQD_THREADS), threads, 0, stream, a);
+    }
+    // a wave a group of 64 reads, at most a few workgroups a CU: the rest of the groups in strides of the grid; block 0 counts
+    // the call
+    uint64_t blocks = ((a.n_bound + 63) / 64 + FQD_WAVES - 1) / FQD_WAVES;
+    const uint64_t cap = cu_count > 0 ? min((uint64_t)cu_count * 16u, (uint64_t)FQD_MAX_BLOCKS) : FQD_MAX_BLOCKS;
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    const dim3 grid((unsigned)blocks);
+    switch (a.codes.n) {
+    case 1: hipLaunchKernelGGL(sk_fq_adapters_kernel<1>, grid, threads, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(sk_fq_adapters_kernel<2>, grid, threads, 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(sk_fq_adapters_kernel<3>, grid, threads, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL(sk_fq_adapters_kernel<4>, grid, threads, 0, stream, a); break;
+    case 5: hipLaunchKernelGGL(sk_fq_adapters_kernel<5>, grid, threads, 0, stream, a); break;
+    case 6: hipLaunchKernelGGL(sk_fq_adapters_kernel<6>, grid, threads, 0, stream, a); break;
+    case 7: hipLaunchKernelGGL(sk_fq_adapters_kernel<7>, grid, threads, 0, stream, a); break;
+    default: hipLaunchKernelGGL(sk_fq_adapters_kernel<8>, grid, threads, 0, stream, a); break;
+    }
+    return hipGetLastError();
+}
