@@ -1429,6 +1429,84 @@ int sk_trim_fastq_adapters_device_async(sk_ctx *ctx, const sk_fastq_report_sourc
                                         const sk_fastq_adapter_set *set, sk_fastq_adapters *adapters_dev,
                                         const sk_fastq_adapters_out *out, int flags, void *hip_stream);
 
+/*
+ * The clipped text call: a text call of any kind that clips every read at its 3' adapter hit IN FRONT OF the quality trim,
+ * on the device, inside the call: the search runs between the format checks and the pack, and the pack takes the first p
+ * bases of a read with a hit at p.  This comment is the normative text; the rule as code is sickle_amd/csrc/
+ * sk_fastq_clip.h (and, for the hit, sk_fastq_adapters.h).  The host CLI does not use it.
+ *
+ * The kind.  clip->lengths, piece, order, state_in and state_out are each NULL or what the call of that kind takes, and
+ * the members that are not NULL name the kind exactly as the five calls above do: all NULL is sk_trim_fastq_device_async;
+ * lengths alone the chained call; piece (with or without lengths) the piece call; order (with or without lengths) the
+ * ordered call; state_out, which needs both piece and order, the ordered piece.  The finish is the finish of that kind,
+ * and the header words, the output words and the piece words are unchanged.
+ * The hit of a read is exactly the adapters' (above), with the seq line's length L taken from the record descriptor, the
+ * bytes between the end of the name line and the end of the seq line, instead of the packed batch: the lowest start p,
+ * then the lowest adapter a; partial overlaps at the read's end, min_overlap and the permille allowance; either case
+ * matches, and 'N', IUPAC codes, '\r' and bytes >= 0x80 match nothing.  Mates are clipped independently.
+ * The packed length of read r is min(L, p) when the read has a hit and L otherwise.  Everything behind the clip point
+ * does not exist for the scan: a quality byte out of range behind p is no SK_ERANGE, an 'N' behind p does not count for
+ * params->trunc_n, and params->length_threshold applies to the clipped length.  A read clipped to 0 bases (p == 0) is an
+ * empty read, which the scan discards; the pair rule then routes its mate to the singles, and SK_TRIM_PE_COMBO_ALL
+ * writes it as an N record.  No new check refuses it: SK_FQ_SEQ_EMPTY stays a property of the text alone.
+ * The output is therefore what the unclipped call writes for a text whose hit reads had seq and qual cut to p bytes
+ * before the call saw them (with p >= 1; no valid text holds a p == 0 read's truncation).  Format checks, framing, pair
+ * counts, read numbering, ordering, capacities and "nothing is written on an error" are untouched, and a clipped call's
+ * outputs never exceed the unclipped call's bounds (sk_trim_fastq_output_bound and the like hold as they are).
+ * The workspace is the kind's own (sk_trim_fastq_workspace_bytes, .._ordered_.., .._ordered_piece_..) plus
+ * sk_trim_fastq_clip_extra_bytes(text_bytes): a 128-byte block of this call's own sums and 4 * (2H + 2) bytes of clip
+ * words, H = (text_bytes + 2) / 16, rounded up to 16.  The clip section is the last `extra` bytes of that requirement, so
+ * no section of the kind's layout moves and a sk_fastq_report_source describes the workspace as it always did.
+ * *clip->clip_words_dev (where clip_words_dev is not NULL) is set before the call returns to where this call's clip
+ * words lie in its workspace: one uint32_t per read, in the call's read numbering, a << 24 | p or SK_FQ_CLIP_NONE,
+ * written for the reads of a call without a format verdict and valid until the workspace is reused.
+ * clip->stats_dev (device memory that the caller owns, or NULL) accumulates like the side calls' structs: a one-workgroup
+ * kernel behind the emission adds this call's sums iff the call's verdict is clean, with the report's validity (above),
+ * read from the call's own workspace; otherwise it increments calls_failed and touches nothing else.
+ *   calls, calls_failed   calls that added / that did not
+ *   reads                 the reads of the call (the report's)
+ *   reads_clipped         reads with a hit;  reads_emptied: those with p == 0
+ *   bases_clipped         sum of L - p over the hits
+ *   hits[a]               reads whose hit is adapter a
+ *   reserved              zero
+ * SK_FQ_CLIP_RESET zeroes the struct first, by a kernel of its own; a zeroed struct is a valid start.  Calls that add to
+ * one struct must be on one stream.
+ * What the side calls see behind a clipped call.  The report, the bases, the audit, the adapters and the rejects take a
+ * read's length from the packed batch, so they describe the run as if the text had held the clipped reads: the report's
+ * bases_in is after the clip, and what is missing is bases_clipped; the adapters search the clipped reads; a read
+ * emptied by the clip counts among the bases' reads and gc_none_in, as a read of no bases does by their rule.  The rejects
+ * still write a discarded read's own four lines uncut, adapter included, so their identity "output + rejects = input" NO
+ * LONGER HOLDS behind a clipped call: the kept reads have lost their clipped bases and no text holds them.
+ * SK_EINVAL, with sk_last_error text and nothing enqueued: everything the call of the kind refuses; clip or clip->set
+ * NULL; a set outside the adapters' bounds; clip->reserved != 0 or flags other than SK_FQ_CLIP_RESET; state_out without
+ * piece and order; stats_dev not 8-byte aligned; a workspace smaller than the kind's size plus the extra.
+ */
+#define SK_FQ_CLIP_RESET 1u
+
+typedef struct {
+    uint64_t calls, calls_failed;
+    uint64_t reads, reads_clipped, reads_emptied, bases_clipped;
+    uint64_t hits[8];
+    uint64_t reserved[2];
+} sk_fastq_clip_stats; /* device memory, 8-byte aligned, 128 bytes */
+
+typedef struct {
+    const sk_fastq_adapter_set *set; /* required; host memory, read before the call returns */
+    const sk_fastq_lengths *lengths;
+    const sk_fastq_piece *piece;
+    const sk_fastq_order *order;
+    const sk_fastq_order_state *state_in;
+    sk_fastq_order_state *state_out;     /* each NULL or as in the call of that kind */
+    sk_fastq_clip_stats *stats_dev;      /* or NULL */
+    const uint32_t **clip_words_dev;     /* out, or NULL: where this call's clip words lie in its workspace */
+    uint32_t flags, reserved;            /* SK_FQ_CLIP_RESET; 0 */
+} sk_fastq_clip;
+
+size_t sk_trim_fastq_clip_extra_bytes(uint64_t text_bytes); /* pure, no device */
+int sk_trim_fastq_clipped_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, const sk_fastq_clip *clip,
+                                       int mode, const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                       void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,7 +54,7 @@ EXPORTS = ("sk_quality_constants", "sk_typename", "sk_abi_version", "sk_device_c
            "sk_trim_fastq_audit_device_async", "sk_trim_fastq_bases_device_async",
            "sk_trim_fastq_rejects_workspace_bytes", "sk_trim_fastq_rejects_bound", "sk_trim_fastq_rejects_device_async",
            "sk_trim_fastq_rejects_device_finish", "sk_trim_fastq_rejects_output_words",
-           "sk_trim_fastq_adapters_device_async")
+           "sk_trim_fastq_adapters_device_async", "sk_trim_fastq_clip_extra_bytes", "sk_trim_fastq_clipped_device_async")
 # sk_trim_fastq_adapters_device_async (include/sickle_amd.h)
 SK_FQ_ADAPTERS_RESET = 1
 SK_FQ_ADAPTERS_MAX = 8
@@ -62,6 +62,8 @@ SK_FQ_ADAPTER_MAX_LEN = 64
 SK_FQ_ADAPTERS_MAX_POS_BINS = 2048
 SK_FQ_ADAPTERS_OVERLAP_BINS = 65
 SK_FQ_CLIP_NONE = 0xFFFFFFFF
+# sk_trim_fastq_clipped_device_async (include/sickle_amd.h)
+SK_FQ_CLIP_RESET = 1
 # sk_trim_fastq_rejects_device_async (include/sickle_amd.h)
 SK_FQ_REJECTS_PAIRS = 1
 # sk_trim_fastq_bases_device_async (include/sickle_amd.h)
@@ -454,6 +456,58 @@ class _AdaptersBuffers:
         return d
 
 
+class FastqClipStats(C.Structure):
+    """sk_fastq_clip_stats: every member is a uint64_t"""
+    _fields_ = [("calls", C.c_uint64), ("calls_failed", C.c_uint64), ("reads", C.c_uint64), ("reads_clipped", C.c_uint64),
+                ("reads_emptied", C.c_uint64), ("bases_clipped", C.c_uint64), ("hits", C.c_uint64 * 8),
+                ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        """the members but `reserved`, as ints; hits as a list of eight"""
+        return {name: (list(getattr(self, name)) if name == "hits" else int(getattr(self, name)))
+                for name, _ in self._fields_ if name != "reserved"}
+
+
+CLIP_WORDS = C.sizeof(FastqClipStats) // 8
+
+
+class FastqClip(C.Structure):
+    """sk_fastq_clip"""
+    _fields_ = [("set", C.POINTER(FastqAdapterSet)), ("lengths", C.c_void_p), ("piece", C.c_void_p), ("order", C.c_void_p),
+                ("state_in", C.c_void_p), ("state_out", C.c_void_p), ("stats_dev", C.c_void_p),
+                ("clip_words_dev", C.POINTER(C.c_void_p)), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def fastq_clip_extra_bytes(text_bytes):
+    """sk_trim_fastq_clip_extra_bytes: what a clipped call's workspace holds behind its kind's own"""
+    return lib().sk_trim_fastq_clip_extra_bytes(text_bytes)
+
+
+class _ClipBuffers:
+    """The set and the device words of one clip_adapters=dict(seqs=[..], min_overlap=3, max_mismatch_permille=100,
+    clip=False) of a driver: a sk_fastq_clip_stats, which the driver's clipped calls add to.  reset: whether the next call
+    zeroes it first (the drivers set it in front of each call)."""
+
+    def __init__(self, clip_adapters, dev, clip_ok=False):
+        import torch
+        if not isinstance(clip_adapters, dict) or "seqs" not in clip_adapters:
+            raise ValueError("clip_adapters: a dict with seqs=[...]")
+        unknown = set(clip_adapters) - {"seqs", "min_overlap", "max_mismatch_permille", "clip"}
+        if unknown:
+            raise ValueError("clip_adapters: unknown keys %r" % sorted(unknown))
+        self.set = adapter_set(clip_adapters["seqs"], clip_adapters.get("min_overlap", 3),
+                               clip_adapters.get("max_mismatch_permille", 100))
+        self.want_clip = bool(clip_adapters.get("clip", False))
+        if self.want_clip and not clip_ok:
+            raise ValueError("clip_adapters: clip=True is trim_fastq's alone")
+        self.buf = torch.zeros(CLIP_WORDS, dtype=torch.int64, device=dev)
+        self.ptr, self.reset, self.words_ptr = self.buf.data_ptr(), True, None
+
+    def read(self):
+        """-> sk_fastq_clip_stats's members but `reserved`, as ints"""
+        return FastqClipStats.from_buffer_copy(self.buf.cpu().numpy().tobytes()).as_dict()
+
+
 class FastqRejectsCounts(C.Structure):
     """sk_fastq_rejects_counts"""
     _fields_ = [("records", C.c_uint64), ("bytes", C.c_uint64), ("reads", C.c_uint64), ("valid", C.c_uint32),
@@ -796,6 +850,11 @@ def lib():
         L.sk_trim_fastq_adapters_device_async.argtypes = [C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                           C.c_int, C.POINTER(FastqAdapterSet), C.c_void_p,
                                                           C.POINTER(FastqAdaptersOut), C.c_int, C.c_void_p]
+        L.sk_trim_fastq_clip_extra_bytes.restype = C.c_size_t
+        L.sk_trim_fastq_clip_extra_bytes.argtypes = [C.c_uint64]
+        L.sk_trim_fastq_clipped_device_async.restype = C.c_int
+        L.sk_trim_fastq_clipped_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(FastqInput), C.POINTER(FastqClip),
+                                                         C.c_int, C.POINTER(FastqOutput), C.c_void_p, C.c_size_t, C.c_void_p]
         L.sk_trim_fastq_audit_device_async.restype = C.c_int
         L.sk_trim_fastq_audit_device_async.argtypes =[C.c_void_p, C.POINTER(FastqReportSource), C.POINTER(FastqInput),
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -857,11 +916,13 @@ def _source_kind(kind, order):
     return {"plain": "ordered", "piece": "ordered_piece"}[kind], order.batch_capacity
 
 
-def _fastq_ws_bytes(sizes, trunc_n, order):
-    """the workspace of a whole-text call on texts of these sizes; order: a FastqOrder or None"""
+def _fastq_ws_bytes(sizes, trunc_n, order, clip=None):
+    """the workspace of a whole-text call on texts of these sizes; order: a FastqOrder or None; clip: not None = a clipped
+    call, whose clip section follows"""
+    extra = lib().sk_trim_fastq_clip_extra_bytes(sum(sizes)) if clip is not None else 0
     if order is None:
-        return lib().sk_trim_fastq_workspace_bytes(sum(sizes), trunc_n)
-    return lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), trunc_n, order.batch_capacity)
+        return lib().sk_trim_fastq_workspace_bytes(sum(sizes), trunc_n) + extra
+    return lib().sk_trim_fastq_ordered_workspace_bytes(sum(sizes), trunc_n, order.batch_capacity) + extra
 
 
 class Context:
@@ -1050,10 +1111,52 @@ class Context:
         return tuple(res)
 
     # ---- FASTQ text on the device -------------------------------------------------------------
+    def trim_fastq_clipped_device_async(self, params, text_ptrs, text_bounds, set, outs, workspace_ptr, workspace_bytes,
+                                        mode="se", bytes_dev_ptrs=None, valid_dev_ptrs=None, start_dev_ptrs=None, more=False,
+                                        piece=False, order=None, state_in_ptr=None, state_out_ptr=None, stats_ptr=None,
+                                        reset=False, max_read_len=0, stream=None, flags=None, reserved=0):
+        """sk_trim_fastq_clipped_device_async on raw device pointers: the text call of the kind the arguments name, with
+        every read clipped at its 3' adapter hit in front of the scan.  set: a FastqAdapterSet (adapter_set(seqs, ..)).
+        bytes_dev_ptrs / valid_dev_ptrs given (lists, as the chained call's): device lengths; piece=True (or start_dev_ptrs
+        given): a piece, with `more`; order: a FastqOrder; state_out_ptr: an ordered piece.  stats_ptr: a
+        sk_fastq_clip_stats in device memory or None; reset: SK_FQ_CLIP_RESET (flags: the raw word instead).  The workspace
+        holds the kind's bytes plus fastq_clip_extra_bytes; the finish is the kind's.  -> the device address of this call's
+        clip words in its workspace."""
+        inp = _fastq_input(text_ptrs, text_bounds, max_read_len)
+        keep = []
+        clip = FastqClip()
+        clip.set = C.pointer(set) if set is not None else None
+        if bytes_dev_ptrs is not None or valid_dev_ptrs is not None:
+            keep.append(_fastq_lengths(bytes_dev_ptrs or (), valid_dev_ptrs or ()))
+            clip.lengths = C.addressof(keep[-1])
+        if piece or start_dev_ptrs is not None:
+            keep.append(_fastq_piece(start_dev_ptrs or (), more))
+            clip.piece = C.addressof(keep[-1])
+        if order is not None:
+            clip.order = C.addressof(order)
+        clip.state_in, clip.state_out, clip.stats_dev = state_in_ptr, state_out_ptr, stats_ptr
+        words = C.c_void_p()
+        clip.clip_words_dev = C.pointer(words)
+        clip.flags = (SK_FQ_CLIP_RESET if reset else 0) if flags is None else flags
+        clip.reserved = reserved
+        self._check(lib().sk_trim_fastq_clipped_device_async(self._h, C.byref(params), C.byref(inp), C.byref(clip),
+                                                             TRIM_MODES.get(mode, mode), _fastq_outputs(outs), workspace_ptr,
+                                                             workspace_bytes, stream))
+        return words.value
+
+    def _clipped(self, clip, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes, **kind):
+        """a driver's text call as the clipped call of its kind; clip: its _ClipBuffers"""
+        clip.words_ptr = self.trim_fastq_clipped_device_async(params, text_ptrs, text_bounds, clip.set, outs, workspace_ptr,
+                                                              workspace_bytes, stats_ptr=clip.ptr, reset=clip.reset, **kind)
+
     def trim_fastq_device_async(self, params, text_ptrs, text_bytes, outs, workspace_ptr, workspace_bytes, mode="se",
-                                max_read_len=0, stream=None):
+                                max_read_len=0, stream=None, clip=None):
         """sk_trim_fastq_device_async on raw device pointers; text_ptrs / text_bytes: one or two entries, outs: up to
-        three FastqOutput (missing ones are not produced)."""
+        three FastqOutput (missing ones are not produced).  clip (the drivers' own, as in the four calls below): a
+        _ClipBuffers, and the call is sk_trim_fastq_clipped_device_async of this kind."""
+        if clip is not None:
+            return self._clipped(clip, params, text_ptrs, text_bytes, outs, workspace_ptr, workspace_bytes, mode=mode,
+                                 max_read_len=max_read_len, stream=stream)
         inp = _fastq_input(text_ptrs, text_bytes, max_read_len)
         self._check(lib().sk_trim_fastq_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
                                                      _fastq_outputs(outs), workspace_ptr, workspace_bytes, stream))
@@ -1149,9 +1252,12 @@ class Context:
         return b.value, w.value
 
     def trim_fastq_ordered_device_async(self, params, text_ptrs, text_bytes, order, outs, workspace_ptr, workspace_bytes,
-                                        mode="se", max_read_len=0, stream=None):
+                                        mode="se", max_read_len=0, stream=None, clip=None):
         """sk_trim_fastq_ordered_device_async on raw device pointers; order: a FastqOrder; the rest as
         trim_fastq_device_async."""
+        if clip is not None:
+            return self._clipped(clip, params, text_ptrs, text_bytes, outs, workspace_ptr, workspace_bytes, mode=mode,
+                                 order=order, max_read_len=max_read_len, stream=stream)
         inp = _fastq_input(text_ptrs, text_bytes, max_read_len)
         self._check(lib().sk_trim_fastq_ordered_device_async(self._h, C.byref(params), C.byref(inp), TRIM_MODES.get(mode, mode),
                                                              C.byref(order), _fastq_outputs(outs), workspace_ptr,
@@ -1169,11 +1275,15 @@ class Context:
 
     def trim_fastq_chained_device_async(self, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes,
                                         bytes_dev_ptrs=(), valid_dev_ptrs=(), mode="se", order=None, max_read_len=0,
-                                        stream=None):
+                                        stream=None, clip=None):
         """sk_trim_fastq_chained_device_async on raw device pointers: text_bounds are upper bounds on the texts' lengths,
         bytes_dev_ptrs / valid_dev_ptrs (up to two entries each, None = not given) the device words that hold the lengths
         and their validity, e.g. those of bgzf_inflate_output_words.  order: a FastqOrder or None (read order); the
         workspace and the finish are those of trim_fastq_ordered_device_async / trim_fastq_device_async accordingly."""
+        if clip is not None:
+            return self._clipped(clip, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes, mode=mode,
+                                 bytes_dev_ptrs=list(bytes_dev_ptrs), valid_dev_ptrs=list(valid_dev_ptrs), order=order,
+                                 max_read_len=max_read_len, stream=stream)
         inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
         self._check(lib().sk_trim_fastq_chained_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
                                                              TRIM_MODES.get(mode, mode),
@@ -1183,10 +1293,15 @@ class Context:
     # ---- FASTQ text in pieces ------------------------------------------------------------------
     def trim_fastq_piece_device_async(self, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes,
                                       bytes_dev_ptrs=(), valid_dev_ptrs=(), start_dev_ptrs=(), more=False, mode="se",
-                                      max_read_len=0, stream=None, piece=True):
+                                      max_read_len=0, stream=None, piece=True, clip=None):
         """sk_trim_fastq_piece_device_async on raw device pointers: trim_fastq_chained_device_async (read order) on the
         window that starts at the device words start_dev_ptrs (None = 0); more: more text follows, so only whole records
         (pairs) are taken and the rest is the carry.  piece=False passes piece == NULL: the chained call itself."""
+        if clip is not None:
+            return self._clipped(clip, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes, mode=mode,
+                                 bytes_dev_ptrs=list(bytes_dev_ptrs), valid_dev_ptrs=list(valid_dev_ptrs),
+                                 start_dev_ptrs=list(start_dev_ptrs) if piece else None, more=more, piece=piece,
+                                 max_read_len=max_read_len, stream=stream)
         inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
         pc = _fastq_piece(start_dev_ptrs, more)
         self._check(lib().sk_trim_fastq_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
@@ -1207,10 +1322,17 @@ class Context:
 
     def trim_fastq_ordered_piece_device_async(self, params, text_ptrs, text_bounds, order, state_in_ptr, state_out_ptr, outs,
                                               workspace_ptr, workspace_bytes, bytes_dev_ptrs=(), valid_dev_ptrs=(),
-                                              start_dev_ptrs=(), more=False, mode="se", max_read_len=0, stream=None):
+                                              start_dev_ptrs=(), more=False, mode="se", max_read_len=0, stream=None,
+                                              clip=None):
         """sk_trim_fastq_ordered_piece_device_async on raw device pointers: trim_fastq_piece_device_async whose records are
         the batches the piece can commit, in the -a T order.  order: a FastqOrder; state_in_ptr (None: the start of a
         stream) and state_out_ptr: FastqOrderState in device memory."""
+        if clip is not None:
+            return self._clipped(clip, params, text_ptrs, text_bounds, outs, workspace_ptr, workspace_bytes, mode=mode,
+                                 bytes_dev_ptrs=list(bytes_dev_ptrs), valid_dev_ptrs=list(valid_dev_ptrs),
+                                 start_dev_ptrs=list(start_dev_ptrs), more=more, piece=True, order=order,
+                                 state_in_ptr=state_in_ptr, state_out_ptr=state_out_ptr, max_read_len=max_read_len,
+                                 stream=stream)
         inp, lengths = _fastq_input(text_ptrs, text_bounds, max_read_len), _fastq_lengths(bytes_dev_ptrs, valid_dev_ptrs)
         pc = _fastq_piece(start_dev_ptrs, more)
         self._check(lib().sk_trim_fastq_ordered_piece_device_async(self._h, C.byref(params), C.byref(inp), C.byref(lengths),
@@ -1250,7 +1372,7 @@ class Context:
 
     def trim_fastq_stream(self, params, chunks, chunks2=None, mode="se", piece_bytes=64 << 20, room=None, gz=False,
                           search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
-                          rejects=False, adapters=False):
+                          rejects=False, adapters=False, clip_adapters=None):
         """FASTQ text of any length on the host -> trimmed FASTQ text, piece by piece (sk_trim_fastq_piece_device_async
         and sk_fastq_carry_device_async) on the current stream.  chunks (chunks2 for mode "pe_split"): a bytes-like object
         or an iterable of bytes-like objects of any sizes; they are re-cut into pieces of piece_bytes.  Returns a
@@ -1292,27 +1414,31 @@ class Context:
         holds the summed records and bytes after the last piece (None until then, and after a failure).
         adapters=dict(seqs=[..], ..) as trim_fastq's, without clip: sk_trim_fastq_adapters_device_async behind every piece,
         over the piece's workspace and its text buffers, with the reset in front of the first piece only; the struct and
-        the histograms of the whole file are read back once into .adapters (None until then, and after a failure)."""
+        the histograms of the whole file are read back once into .adapters (None until then, and after a failure).
+        clip_adapters=dict(seqs=[..], ..) as trim_fastq's, without clip: every piece is the clipped call of its kind
+        (sk_trim_fastq_clipped_device_async), and the stats of the whole file are read back once into .clip (None until then,
+        and after a failure).  None: the pieces are the calls they were, and nothing is allocated."""
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects, adapters)
+                           audit, bases, rejects, adapters, clip_adapters)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
                        max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False, rejects=False,
-                       adapters=False):
+                       adapters=False, clip_adapters=None):
         """trim_fastq_stream for BGZF image(s) on the host (bytes-like): the host walks the members' BSIZE fields and cuts
         each image into groups of whole members of at most piece_bytes of text (ISIZE sums; piece_bytes >= 65536), every
         group is uploaded and inflated by sk_bgzf_inflate_device_async straight behind the carry, and the reader's device
         words give the carry the chunk's length and validity.  Raises GzDataError for a bad group (member numbers and
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
-        (use trim_gz).  order, batch_capacity, report, audit, bases, rejects, adapters: as in trim_fastq_stream."""
+        (use trim_gz).  order, batch_capacity, report, audit, bases, rejects, adapters, clip_adapters: as in
+        trim_fastq_stream."""
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
         return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects, adapters)
+                           audit, bases, rejects, adapters, clip_adapters)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
-                         rejects=False, adapters=False):
+                         rejects=False, adapters=False, clip_adapters=None):
         """trim_gz_stream for ANY gzip image (bytes or uint8 arrays on the host; plain gzip, what gzip, pigz and zlib
         write, and BGZF too): a FastqStream.  Each image is uploaded once, whole (device_bytes includes it: the memory
         depends on the piece size and on the COMPRESSED file's size, not on the text's), and read by one
@@ -1323,11 +1449,11 @@ class Context:
         more text than the piece may take raises TrimError naming piece_bytes (split inputs are steered down to half a
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
-        batch_capacity, report, audit, bases, rejects, adapters: as in trim_fastq_stream."""
+        batch_capacity, report, audit, bases, rejects, adapters, clip_adapters: as in trim_fastq_stream."""
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
         st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                         audit, bases, rejects, adapters)
+                         audit, bases, rejects, adapters, clip_adapters)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1361,7 +1487,7 @@ class Context:
         return call(second)
 
     def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
-                   audit=False, bases=False, rejects=False, adapters=False):
+                   audit=False, bases=False, rejects=False, adapters=False, clip_adapters=None):
         """FASTQ text in device memory (uint8 torch tensors; text2 for mode "pe_split") -> trimmed FASTQ text, on the
         current stream.  A count-only pass sizes the outputs, a second one writes them.  Returns (outputs, counts):
         three entries, None where the mode has no such output, each a uint8 tensor narrowed to its bytes, or with
@@ -1396,14 +1522,19 @@ class Context:
         and the texts) is returned as counts["adapters"]: sk_fastq_adapters's members as ints (hits: eight) and, where
         asked for, pos as a uint64 array of shape (8, pos_bins) and overlap of shape (8, 65); with clip=True also clip, an
         int64 tensor on the device with every read's clip point (-1: no hit), and adapter, the hit's adapter likewise.
-        Nothing acts on the result.  adapters=False: the call is what it was, to the launch, and nothing is allocated."""
+        Nothing acts on the result.  adapters=False: the call is what it was, to the launch, and nothing is allocated.
+        clip_adapters=dict(seqs=[..], min_overlap=3, max_mismatch_permille=100, clip=False): both passes are the clipped
+        call (sk_trim_fastq_clipped_device_async): every read is clipped at its 3' adapter hit in front of the quality
+        trim, and everything above describes the clipped reads.  counts["clip"] holds sk_fastq_clip_stats's members of the
+        writing pass as ints (hits: eight); with clip=True also clip and adapter, int64 tensors as adapters=dict(clip=True)'s.
+        None: nothing is launched, nothing extra is allocated, and the calls are the ones they were."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
                                                                                   record_index, o, report, audit, bases,
-                                                                                  rejects, adapters))
+                                                                                  rejects, adapters, clip_adapters))
         return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects,
-                                adapters)
+                                adapters, clip_adapters)
 
     def _enqueue_behind(self, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream, rep=None, aud=None, bas=None,
                         rej=None, adp=None):
@@ -1439,13 +1570,14 @@ class Context:
                                                   batch_capacity=cap, out=adp.out, reset=reset, stream=stream)
 
     def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False,
-                    rejects=False, adapters=False):
+                    rejects=False, adapters=False, clip_adapters=None):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order)
+        clp = _ClipBuffers(clip_adapters, dev, clip_ok=True) if clip_adapters is not None else None
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
@@ -1459,10 +1591,10 @@ class Context:
         def run(outs, final=False):
             if order is None:
                 self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                             max_read_len=max_read_len, stream=stream)
+                                             max_read_len=max_read_len, stream=stream, clip=clp)
             else:
                 self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                     max_read_len=max_read_len, stream=stream)
+                                                     max_read_len=max_read_len, stream=stream, clip=clp)
             # the report, the audit and the bases go behind the writing pass's emission and in front of its finish, which
             # is the wait; the rejects: a counting call behind the counting pass, the writing one behind the writing pass
             self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream,
@@ -1498,6 +1630,14 @@ class Context:
             counts["bases"] = bas.read()
         if adp:
             counts["adapters"] = adp.read()
+        if clp:  # every call zeroed the stats first: these are the writing pass's
+            counts["clip"] = clp.read()
+            if clp.want_clip:  # the words lie in the workspace: a copy that outlives it
+                at = clp.words_ptr - ws.data_ptr()
+                words = ws[at:at + 4 * counts["clip"]["reads"]].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+                none = words == SK_FQ_CLIP_NONE
+                counts["clip"]["clip"] = torch.where(none, torch.full_like(words, -1), words & 0xFFFFFF)
+                counts["clip"]["adapter"] = torch.where(none, torch.full_like(words, -1), words >> 24)
         if rejects:
             got = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
             counts["rejects"] = {"text": rej_text[:got["bytes"]], "index": rej_idx[:got["records"]] if record_index else None,
@@ -1538,28 +1678,32 @@ class Context:
         return out[:self.bgzf_device_finish(ws.data_ptr(), stream)["bytes_out"]]
 
     def trim_fastq_gz(self, params, text, text2=None, mode="se", max_read_len=0, order=None, search=False, report=False,
-                      audit=False, bases=False, adapters=False):
+                      audit=False, bases=False, adapters=False, clip_adapters=None):
         """FASTQ text in device memory -> the trimmed texts as BGZF images (.fastq.gz files as they stand), in one pass on
         the current stream: the outputs are sized by the inputs (fastq_output_bound: a trimmed text never exceeds them by more
         than one newline each, and by one byte per record in mode "pe_combo_all"), every produced output's image is enqueued behind the trim, fed by the trim's device words, and
         only then does anything wait.  Returns (images, counts) like trim_fastq; raises what it raises.  order: as
         trim_fastq's (a batch table that was too small is seen at the end only: the pass then runs once more).  search:
         as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as
-        trim_fastq's, counts["bases"].  adapters: as trim_fastq's, counts["adapters"], without clip."""
+        trim_fastq's, counts["bases"].  adapters: as trim_fastq's, counts["adapters"], without clip.  clip_adapters: as
+        trim_fastq's, counts["clip"], without clip."""
         if order is not None:
             sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
             return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
-                                                                                     search, report, audit, bases, adapters))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases, adapters)
+                                                                                     search, report, audit, bases, adapters,
+                                                                                     clip_adapters))
+        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases, adapters,
+                                   clip_adapters)
 
     def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False,
-                       bases=False, adapters=False):
+                       bases=False, adapters=False, clip_adapters=None):
         import torch
         dev = text.device
         texts = [text] if text2 is None else [text, text2]
         ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order)
+        clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = TRIM_OUTPUTS[mode]
         cap = fastq_output_bound(sum(sizes), mode)
@@ -1571,10 +1715,10 @@ class Context:
             outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
         if order is None:
             self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                         max_read_len=max_read_len, stream=stream)
+                                         max_read_len=max_read_len, stream=stream, clip=clp)
         else:
             self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                 max_read_len=max_read_len, stream=stream)
+                                                 max_read_len=max_read_len, stream=stream, clip=clp)
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
@@ -1597,6 +1741,8 @@ class Context:
             counts["bases"] = bas.read()
         if adp:
             counts["adapters"] = adp.read()
+        if clp:
+            counts["clip"] = clp.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     # ---- BGZF read on the device --------------------------------------------------------------
@@ -1764,7 +1910,7 @@ class Context:
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
     def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False,
-                         bases=False, adapters=False):
+                         bases=False, adapters=False, clip_adapters=None):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1788,7 +1934,8 @@ class Context:
             readers.append((fin, rws))
             nbytes.append(b)
             valid.append(w)
-        ws_bytes = _fastq_ws_bytes(capacities, params.trunc_n, order)
+        clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
+        ws_bytes = _fastq_ws_bytes(capacities, params.trunc_n, order, clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         used = TRIM_OUTPUTS[mode]
         cap = fastq_output_bound(sum(capacities), mode)
@@ -1800,7 +1947,7 @@ class Context:
             outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
         self.trim_fastq_chained_device_async(params, [t.data_ptr() for t in texts], capacities, outs, ws.data_ptr(), ws_bytes,
                                              bytes_dev_ptrs=nbytes, valid_dev_ptrs=valid, mode=mode, order=order,
-                                             max_read_len=max_read_len, stream=stream)
+                                             max_read_len=max_read_len, stream=stream, clip=clp)
         rep = _ReportBuffers(report, dev) if report else None
         aud = _AuditBuffers(dev) if audit else None
         bas = _BasesBuffers(bases, dev) if bases else None
@@ -1838,10 +1985,12 @@ class Context:
             counts["bases"] = bas.read()
         if adp:
             counts["adapters"] = adp.read()
+        if clp:
+            counts["clip"] = clp.read()
         return (res, counts, rep.read()) if rep else (res, counts)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
-                kind=None, report=False, audit=False, bases=False, adapters=False):
+                kind=None, report=False, audit=False, bases=False, adapters=False, clip_adapters=None):
         """.fastq.gz image(s) in device memory, BGZF or plain gzip -> the trimmed texts as BGZF images, every byte of work
         on the device.  Returns what trim_fastq_gz returns; raises GzDataError and what it raises.  order: as
         trim_fastq's (the reference takes batch_len from the compressed file's size).  search: as bgzf's.
@@ -1859,7 +2008,8 @@ class Context:
         names the reader (one value, or a pair); None looks at the first 16 bytes of each image before anything is
         enqueued.  An ordered call whose batch table was too small is seen at the end and the pass runs once more.
         report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as trim_fastq's,
-        counts["bases"].  adapters: as trim_fastq_gz's, counts["adapters"]."""
+        counts["bases"].  adapters: as trim_fastq_gz's, counts["adapters"].  clip_adapters: as trim_fastq_gz's,
+        counts["clip"]."""
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -1871,11 +2021,11 @@ class Context:
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
                                                                                        max_read_len, o, search, report, audit,
-                                                                                       bases, adapters))
+                                                                                       bases, adapters, clip_adapters))
         text = self._gunzip_any(image)
         text2 = None if image2 is None else self._gunzip_any(image2)
         return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
-                                  report=report, audit=audit, bases=bases, adapters=adapters)
+                                  report=report, audit=audit, bases=bases, adapters=adapters, clip_adapters=clip_adapters)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -2005,7 +2155,7 @@ class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
     def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False, adapters=False):
+                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False, adapters=False, clip_adapters=None):
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -2038,6 +2188,10 @@ class FastqStream:
             self.ws_bytes = L.sk_trim_fastq_ordered_piece_workspace_bytes(n_in * cap_in, params.trunc_n, cap)
         else:
             self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
+        self.clip = None
+        self._clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
+        if self._clp:  # every piece's clip section lies behind ITS kind's bytes, which its bounds make no more than these
+            self.ws_bytes += L.sk_trim_fastq_clip_extra_bytes(n_in * cap_in)
         self.ws = [alloc(self.ws_bytes) for _ in range(2)]
         self.out_cap = fastq_output_bound(n_in * cap_in, mode)
         self.out = [[alloc(self.out_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
@@ -2142,6 +2296,9 @@ class FastqStream:
                      valid_dev_ptrs=[self._words_ptr(i, slot) + 16 for i in range(n_in)],
                      start_dev_ptrs=[self._words_ptr(i, slot) for i in range(n_in)], more=more, mode=self.mode,
                      max_read_len=self.max_read_len, stream=self.stream)
+        if self._clp:  # the stats are zeroed in front of the first piece only
+            self._clp.reset = k == 0
+            words["clip"] = self._clp
         if self.order is None:
             c.trim_fastq_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds, outs,
                                             self.ws[slot].data_ptr(), self.ws_bytes, **words)
@@ -2263,6 +2420,8 @@ class FastqStream:
             self.bases = self._bas.read()
         if self._adp:
             self.adapters = self._adp.read()
+        if self._clp:
+            self.clip = self._clp.read()
         if self._rej:
             self.rejects = dict(self._rej_sum)
 

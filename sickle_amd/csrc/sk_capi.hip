@@ -15,6 +15,7 @@
 #include "sickle_amd.h"
 #include "sk_device.h"
 #include "sk_fastq_adapters.h"
+#include "sk_fastq_clip.h"
 #include "sk_fastq_rejects.h"
 #include "sk_fastq_verdict.h"
 #include "sk_gunzip_block.h"
@@ -758,9 +759,10 @@ size_t sk_trim_fastq_workspace_bytes(uint64_t text_bytes, int32_t trunc_n)
 
 namespace {
 // the argument checks of every FASTQ text call; extra = what an ordered call's batch table (and an ordered piece's block)
-// adds to the workspace
+// adds to the workspace; clipped: the clip section follows (*kind_bytes: where)
 int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in, int mode,
-                     const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, size_t extra)
+                     const sk_fastq_output out[3], void *workspace, size_t workspace_bytes, size_t extra, bool clipped = false,
+                     size_t *kind_bytes = nullptr)
 {
     if (!ctx) return SK_EINVAL;
     if (!params || !in || !out) SK_BAD(ctx, "%s: params, in and out are required", who);
@@ -778,10 +780,14 @@ int fastq_check_args(sk_ctx *ctx, const char *who, const sk_params *params, cons
     const uint64_t T = in->bytes[0] + (split ? in->bytes[1] : 0);
     if (sk_fq_pack_reads(in->bytes[0], split ? in->bytes[1] : 0, mode) >= (1ull << 32))
         SK_BAD(ctx, "fastq: %llu bytes of text is beyond what one call takes", (unsigned long long)T);
-    const size_t need = sk_trim_fastq_workspace_bytes(T, params->trunc_n) + extra;
+    // a clipped call: the clip section is the last bytes of the requirement, behind everything the kind lays out
+    const size_t kind_need = sk_trim_fastq_workspace_bytes(T, params->trunc_n) + extra;
+    const size_t need = kind_need + (clipped ? sk_trim_fastq_clip_extra_bytes(T) : 0);
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < need)
-        SK_BAD(ctx, "fastq: workspace must be 16-byte aligned and hold sk_trim_fastq%s_workspace_bytes(%llu, %d%s) = %zu bytes",
-               extra ? "_ordered" : "", (unsigned long long)T, params->trunc_n, extra ? ", batch_capacity" : "", need);
+        SK_BAD(ctx, "fastq: workspace must be 16-byte aligned and hold sk_trim_fastq%s_workspace_bytes(%llu, %d%s)%s = %zu bytes",
+               extra ? "_ordered" : "", (unsigned long long)T, params->trunc_n, extra ? ", batch_capacity" : "",
+               clipped ? " + sk_trim_fastq_clip_extra_bytes" : "", need);
+    if (kind_bytes) *kind_bytes = kind_need;
     return SK_OK;
 }
 
@@ -824,14 +830,17 @@ int check_order(sk_ctx *ctx, const sk_fastq_order *order)
 
 // Every FASTQ text call: the checks, then the front, the counted scan and the emission.  lengths: NULL = in->bytes are the
 // lengths; order: NULL = read order; piece: NULL = the whole text; state_out: not NULL = an ordered piece (piece and order
-// given), whose launchers take the states.
+// given), whose launchers take the states.  clip: not NULL = the clipped call (its own checks have passed): the search in
+// the front, the clip section behind the kind's workspace, the commit of its sums behind the emission.
 int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_fastq_input *in,
                 const sk_fastq_lengths *lengths, int mode, const sk_fastq_order *order, const sk_fastq_output out[3],
                 void *workspace, size_t workspace_bytes, void *hip_stream, const sk_fastq_piece *piece = nullptr,
-                const sk_fastq_order_state *state_in = nullptr, sk_fastq_order_state *state_out = nullptr)
+                const sk_fastq_order_state *state_in = nullptr, sk_fastq_order_state *state_out = nullptr,
+                const sk_fastq_clip *clip = nullptr)
 {
     const uint64_t extra = !order ? 0 : state_out ? sk_fq_order_piece_shift(order->batch_capacity) : sk_fq_order_shift(order->batch_capacity);
-    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes, (size_t)extra);
+    size_t kind_bytes = 0;
+    int rc = fastq_check_args(ctx, who, params, in, mode, out, workspace, workspace_bytes, (size_t)extra, clip != nullptr, &kind_bytes);
     if (rc != SK_OK) return rc;
     rc = fastq_check_words(ctx, lengths, piece, mode);
     if (rc != SK_OK) return rc;
@@ -853,12 +862,22 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     const char *counted_env = getenv("SK_FQ_COUNTED");
     const int counted = !(counted_env && *counted_env == '0');
     const uint64_t *n_reads_dev = nullptr;
+    sk_fq_clip_front clip_front = {};
+    const sk_fq_clip_front *cf = nullptr;
+    if (clip) {
+        clip_front.set = clip->set;
+        clip_front.section = static_cast<uint8_t *>(workspace) + kind_bytes;
+        cf = &clip_front;
+        if (clip->clip_words_dev)
+            *clip->clip_words_dev = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(clip_front.section) + FQC_STATS_BYTES);
+        if (clip->stats_dev && (clip->flags & SK_FQ_CLIP_RESET)) SK_HIP(ctx, sk_launch_fastq_clip_reset(clip->stats_dev, stream));
+    }
     if (state_out)
         SK_HIP(ctx, sk_launch_fastq_order_piece_front(in, lengths, mode, params->trunc_n, counted, order, piece, state_in, state_out,
-                                                      d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev));
+                                                      d_err, workspace, ctx->cu_count, stream, &packed, &cuts, &n_reads_dev, cf));
     else
         SK_HIP(ctx, sk_launch_fastq_front(in, lengths, mode, params->trunc_n, counted, order, piece, d_err, workspace, ctx->cu_count,
-                                          stream, &packed, &cuts, &n_reads_dev));
+                                          stream, &packed, &cuts, &n_reads_dev, cf));
     rc = sk_scan_counted_device_async(ctx, params, &packed, n_reads_dev, reinterpret_cast<sk_cut *>(cuts), hip_stream);
     if (rc != SK_OK) return rc;
     if (state_out)
@@ -867,6 +886,10 @@ int fastq_async(sk_ctx *ctx, const char *who, const sk_params *params, const sk_
     else
         SK_HIP(ctx, sk_launch_fastq_emit(in, mode, params->trunc_n, counted, order, piece != nullptr, fastq_fail_qual(params), out,
                                          workspace, d_err, ctx->cu_count, stream));
+    if (clip && clip->stats_dev) {
+        const uint32_t kind = state_out ? SK_FQ_REPORT_ORDERED_PIECE : order ? SK_FQ_REPORT_ORDERED : piece ? SK_FQ_REPORT_PIECE : SK_FQ_REPORT_PLAIN;
+        SK_HIP(ctx, sk_launch_fastq_clip_commit(workspace, kind, mode, clip_front.section, clip->stats_dev, stream));
+    }
     return SK_OK;
 }
 
@@ -1029,6 +1052,35 @@ int sk_trim_fastq_ordered_piece_device_finish(sk_ctx *ctx, void *workspace, void
                                               sk_fastq_order_piece_counts *opc)
 {
     return fastq_finish(ctx, SK_FQV_ORDERED_PIECE, workspace, hip_stream, counts, oc, pc, opc);
+}
+
+// ---- the clipped call: every kind through the one front ----
+size_t sk_trim_fastq_clip_extra_bytes(uint64_t text_bytes) { return (size_t)fqc_extra_bytes(text_bytes); }
+
+int sk_trim_fastq_clipped_device_async(sk_ctx *ctx, const sk_params *params, const sk_fastq_input *in, const sk_fastq_clip *clip,
+                                       int mode, const sk_fastq_output out[3], void *workspace, size_t workspace_bytes,
+                                       void *hip_stream)
+{
+    static_assert(sizeof(sk_fastq_clip_stats) == 128, "the kernels add the stats as 16 words");
+    if (!ctx) return SK_EINVAL;
+    if (!clip || !clip->set) SK_BAD(ctx, "clip: clip and clip->set are required");
+    if (const char *why = fqd_set_error(clip->set)) SK_BAD(ctx, "clip: set: %s", why);
+    if (clip->reserved != 0) SK_BAD(ctx, "clip: reserved must be 0");
+    if (clip->flags & ~SK_FQ_CLIP_RESET) SK_BAD(ctx, "clip: flags %u are unknown", clip->flags);
+    if (reinterpret_cast<uintptr_t>(clip->stats_dev) & 7) SK_BAD(ctx, "clip: stats_dev must be 8-byte aligned");
+    const char *who = "sk_trim_fastq_clipped_device_async";
+    if (clip->state_out || clip->state_in) { // the ordered piece's own checks
+        if (!clip->piece || !clip->order || !clip->state_out) SK_BAD(ctx, "fastq: an ordered piece needs piece, order and state_out");
+        if (clip->state_in == clip->state_out ||
+            ((reinterpret_cast<uintptr_t>(clip->state_in) | reinterpret_cast<uintptr_t>(clip->state_out)) & 7))
+            SK_BAD(ctx, "fastq: state_in and state_out must be 8-byte aligned and differ");
+    } else if (clip->piece && clip->order) {
+        SK_BAD(ctx, "fastq: an ordered piece needs piece, order and state_out");
+    }
+    if (clip->order)
+        if (int rc = check_order(ctx, clip->order)) return rc;
+    return fastq_async(ctx, who, params, in, clip->lengths, mode, clip->order, out, workspace, workspace_bytes, hip_stream, clip->piece,
+                       clip->state_in, clip->state_out, clip);
 }
 
 int sk_bgzf_inflate_output_words(void *workspace, const uint64_t **bytes_dev, const uint64_t **written_dev)

@@ -160,6 +160,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 #define SK_FQ_BLOCK_READS 2048u
 #define SK_FQ_BLOCK_WORDS 8u
 // SK_FQ_HDR_WORDS and the header's words, SK_FQ_H_* and the piece calls' SK_FQP_H_*: sk_fastq_words.h (no HIP: the host reads them too)
+struct sk_fq_clip_front;
 struct sk_fq_layout {
     uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
 };
@@ -198,6 +199,8 @@ static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * 
 // alone, which takes fail_qual, the Q of its N records (sk_fastq_record.h).
 // counted: the packed batch is for sk_scan_counted_device_async with *n_reads_dev (the header's SK_FQ_H_NREAL) -- packed->n_reads
 // stays the bound -- and the per-read steps of the pack and the emission stop at that word too; 0: everything walks the bound.
+// clip: NULL = no clip; else (sk_trim_fastq_clipped_device_async) the search of sk_launch_fastq_clip runs behind the check
+// and the pack takes a read's length through its clip word (sk_fastq_clip.h).
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_front(const sk_fastq_input *in,
                                                                                   const sk_fastq_lengths *lengths, int mode,
                                                                                   int trunc_n, int counted,
@@ -207,7 +210,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
                                                                                   sk_cut_dev **cuts,
-                                                                                  const uint64_t **n_reads_dev);
+                                                                                  const uint64_t **n_reads_dev,
+                                                                                  const struct sk_fq_clip_front *clip);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit(const sk_fastq_input *in, int mode, int trunc_n,
                                                                                  int counted, const sk_fastq_order *order,
                                                                                  int piece, int fail_qual,
@@ -222,7 +226,8 @@ static inline uint64_t sk_fq_order_piece_shift(uint64_t batch_capacity) { return
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_front(
     const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted, const sk_fastq_order *order,
     const sk_fastq_piece *piece, const void *state_in, void *state_out, const unsigned long long *errword, void *workspace,
-    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev);
+    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev,
+    const struct sk_fq_clip_front *clip);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_emit(
     const sk_fastq_input *in, int mode, int trunc_n, int counted, const sk_fastq_order *order, const void *state_in,
     void *state_out, int fail_qual, const sk_fastq_output *out, void *workspace, const unsigned long long *errword,
@@ -448,6 +453,37 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adap
                                                                                      sk_fastq_adapters *adapters_dev,
                                                                                      const sk_fastq_adapters_out *out, int flags,
                                                                                      int cu_count, hipStream_t stream);
+// the clip of a clipped text call (sk_trim_fastq_clipped_device_async; sk_fastq_adapters.hip, sk_fastq_clip.h).
+// sk_fq_clip_front: what such a call hands its front launcher, which passes a NULL for every other call: the set and the
+// clip section of the workspace, the call-local stats block (128 bytes) with the clip words behind it.
+struct sk_fq_clip_front {
+    const sk_fastq_adapter_set *set;
+    void *section;
+};
+// sk_fq_clip_src: the front's view of the text and the workspace, as the search kernel takes it
+struct sk_fq_clip_src {
+    const uint64_t *hdr;
+    const uint64_t *desc[2]; // 5 words per slot
+    uint64_t slots[2];
+    const uint8_t *text[2];
+    uint64_t bytes[2]; // the lengths, or their bounds
+    const uint64_t *bytes_dev[2], *valid_dev[2];
+    uint64_t n_pack;
+    int32_t mode; // the framing mode
+};
+// behind the front's check, in front of its pack: zeroes the section's stats block, then searches
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip(const sk_fq_clip_src *src,
+                                                                                 const sk_fq_clip_front *clip, int cu_count,
+                                                                                 hipStream_t stream);
+// zeroes a caller's sk_fastq_clip_stats (SK_FQ_CLIP_RESET)
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip_reset(sk_fastq_clip_stats *stats_dev,
+                                                                                       hipStream_t stream);
+// behind the emission: the section's sums into stats_dev, by the validity of the call behind `workspace` (kind:
+// SK_FQ_REPORT_*; mode: the call's)
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip_commit(const void *workspace, uint32_t kind,
+                                                                                        int mode, const void *section,
+                                                                                        sk_fastq_clip_stats *stats_dev,
+                                                                                        hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_read_probe(const void *buf, size_t bytes, uint32_t *sink, int cu_count,
                                            hipStream_t stream);
 #endif

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
+#include "sk_fastq_clip.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_record.h"
 
@@ -77,6 +78,9 @@ struct fq_args {
     // scan captures *errword
     const uint64_t *start_dev[2];
     int32_t piece; // 0: no piece (the words 21.. of the header are not touched), 1: a piece, more == 0, 2: more != 0
+    // clipped calls (sk_trim_fastq_clipped_device_async): read r's clip word, written by sk_fq_clip_kernel in front of the
+    // pack; NULL: no clip
+    const uint32_t *clip;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -393,12 +397,14 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_check_kernel(fq_args a)
 // ------------------------------------------------------------------------------------------
 // 5-7 pack: the packed batch's offsets
 // ------------------------------------------------------------------------------------------
-// qual length of packed read r (0 beyond the framed records and for every read of a malformed text)
+// qual length of packed read r (0 beyond the framed records and for every read of a malformed text); of a clipped call the
+// bases in front of the read's clip point (sk_fastq_clip.h)
 __device__ __forceinline__ uint64_t fq_pack_len(const fq_args &a, uint64_t r, uint64_t n_real, bool bad)
 {
     if (bad || r >= n_real) return 0;
     const fq_rec x = fq_record(a, r);
-    return x.e3 - x.e2 - 1;
+    const uint64_t len = x.e3 - x.e2 - 1;
+    return a.clip ? fqc_packed_len(len, a.clip[r]) : len; // uniform
 }
 
 __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_count_kernel(fq_args a)
@@ -1363,10 +1369,32 @@ void fq_make_args(const sk_fastq_input *in, const sk_fastq_lengths *lengths, int
     a.errword = errword;
     a.start_dev[0] = a.start_dev[1] = nullptr;
     a.piece = 0;
+    a.clip = nullptr;
     for (int o = 0; o < 3; ++o) {
         const bool used = o == 0 || (!combo_all && ((mode == SK_TRIM_PE_SPLIT && o == 1) || (mode != SK_TRIM_SE && o == 2)));
         a.out[o] = used && out ? fq_out{out[o].text, out[o].capacity, out[o].record_index, out[o].record_capacity} : fq_out{};
     }
+}
+
+// a clipped call's search, between the check and the pack: the clip words are the pack's from here on.  Its launcher ends
+// with hipGetLastError, which clears the runtime's error: what it returns stands for every launch of the front so far, and
+// the front hands it on
+hipError_t fq_launch_clip(fq_args &a, const sk_fq_clip_front *clip, int cu_count, hipStream_t stream)
+{
+    sk_fq_clip_src src = {};
+    src.hdr = a.hdr;
+    for (int i = 0; i < 2; ++i) {
+        src.desc[i] = a.desc[i];
+        src.slots[i] = a.slots[i];
+        src.text[i] = a.text[i];
+        src.bytes[i] = a.bytes[i];
+        src.bytes_dev[i] = a.bytes_dev[i];
+        src.valid_dev[i] = a.valid_dev[i];
+    }
+    src.n_pack = a.n_pack;
+    src.mode = a.mode;
+    a.clip = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(clip->section) + FQC_STATS_BYTES);
+    return sk_launch_fastq_clip(&src, clip, cu_count, stream);
 }
 
 } // namespace
@@ -1391,7 +1419,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
                                                                                   void *workspace, int cu_count,
                                                                                   hipStream_t stream, sk_batch *packed,
                                                                                   sk_cut_dev **cuts,
-                                                                                  const uint64_t **n_reads_dev)
+                                                                                  const uint64_t **n_reads_dev,
+                                                                                  const sk_fq_clip_front *clip)
 {
     fq_args a;
     fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, piece ? errword : nullptr, a,
@@ -1410,6 +1439,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_fron
         hipLaunchKernelGGL(sk_fq_order_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a, o);
     } else {
         hipLaunchKernelGGL(sk_fq_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a);
+    }
+    if (clip) {
+        const hipError_t e = fq_launch_clip(a, clip, cu_count, stream);
+        if (e != hipSuccess) return e; // nothing of the call is waited for: the caller fails it
     }
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_pack_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
@@ -1468,7 +1501,8 @@ void fq_make_opiece(const sk_fastq_order *order, const void *state_in, void *sta
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_front(
     const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted, const sk_fastq_order *order,
     const sk_fastq_piece *piece, const void *state_in, void *state_out, const unsigned long long *errword, void *workspace,
-    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev)
+    int cu_count, hipStream_t stream, sk_batch *packed, sk_cut_dev **cuts, const uint64_t **n_reads_dev,
+    const sk_fq_clip_front *clip)
 {
     fq_args a;
     fq_make_args(in, lengths, mode, trunc_n, counted, nullptr, workspace, errword, a, sk_fq_order_piece_shift(order->batch_capacity));
@@ -1483,6 +1517,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_orde
     if (nc) hipLaunchKernelGGL(sk_fq_frame_lines_kernel, dim3((unsigned)nc), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_order_piece_chain_kernel, dim3(1), dim3(64), 0, stream, a, o, p);
     hipLaunchKernelGGL(sk_fq_order_piece_check_kernel, dim3((unsigned)cu_count * 4), dim3(FQ_THREADS), 0, stream, a, o, p);
+    if (clip) {
+        const hipError_t e = fq_launch_clip(a, clip, cu_count, stream);
+        if (e != hipSuccess) return e; // nothing of the call is waited for: the caller fails it
+    }
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_count_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);
     hipLaunchKernelGGL(sk_fq_pack_scan_kernel, dim3(1), dim3(FQ_THREADS), 0, stream, a);
     if (a.n_blocks) hipLaunchKernelGGL(sk_fq_pack_place_kernel, dim3((unsigned)a.n_blocks), dim3(FQ_THREADS), 0, stream, a);

@@ -34,6 +34,7 @@
 #include "sk_device.h"
 #include "sk_fastq_adapters.h"
 #include "sk_fastq_audit.h"
+#include "sk_fastq_clip.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_report.h"
 
@@ -279,6 +280,119 @@ __global__ void __launch_bounds__(FQD_THREADS) sk_fq_adapters_kernel(fqd_args a)
     if (t >= FQD_W_READS && t < FQD_W_RESERVED && s_sum[t]) atomicAdd(reinterpret_cast<fqd_ull *>(a.res + t), s_sum[t]);
 }
 
+// ------------------------------------------------------------------------------------------
+// the clip of a clipped text call (sk_trim_fastq_clipped_device_async, sk_fastq_clip.h)
+// ------------------------------------------------------------------------------------------
+// The search again, inside the front of a text call, between its check and its pack: the same wave of 64 reads and the same
+// walk of a line (fqd_search_line), with a line's length from its record descriptor (fqc_line), since the packed batch
+// does not exist yet.  No cuts, no pair words, no histograms.  It writes the clip word of every read, which the pack then
+// reads, and this call's own sums into the head of the clip section, which sk_fq_clip_reset_kernel has zeroed.
+struct fqc_args {
+    sk_fq_clip_src s;
+    uint64_t *stats; // the call-local block, FQC_WORDS words
+    uint32_t *clip;  // s.n_pack words at least
+    fqd_codes codes;
+};
+
+// zeroes FQC_WORDS words: the call-local block in front of every search, a caller's struct with SK_FQ_CLIP_RESET
+__global__ void __launch_bounds__(64) sk_fq_clip_reset_kernel(uint64_t *words)
+{
+    if (threadIdx.x < FQC_WORDS) words[threadIdx.x] = 0;
+}
+
+// text i's length: never beyond the bound the workspace was sized by (== fq_length of sk_fastq.hip)
+__device__ __forceinline__ uint64_t fqc_length(const sk_fq_clip_src &s, int i)
+{
+    uint64_t n = s.bytes[i];
+    if (s.bytes_dev[i]) n = min(n, *s.bytes_dev[i]);
+    if (s.valid_dev[i] && *s.valid_dev[i] == 0) n = 0;
+    return n;
+}
+
+template <uint32_t N>
+__global__ void __launch_bounds__(FQD_THREADS) sk_fq_clip_kernel(fqc_args a)
+{
+    __shared__ fqd_ull s_sum[FQC_WORDS];
+    const int t = threadIdx.x, lane = t & 63;
+    // a malformed text: its descriptors are not to be trusted, and the pack packs nothing either
+    if (a.s.hdr[SK_FQ_H_FMT] != ~0ull) return; // uniform
+    const uint64_t R = min(a.s.hdr[SK_FQ_H_NREAL], a.s.n_pack);
+    if (R == 0) return;
+    if (t < FQC_WORDS) s_sum[t] = 0;
+    __syncthreads();
+    const bool split = a.s.mode == SK_TRIM_PE_SPLIT;
+    const uint64_t bytes[2] = {fqc_length(a.s, 0), split ? fqc_length(a.s, 1) : 0};
+    const uint64_t groups = (R + 63) / 64; // 64 consecutive reads a wave's turn
+    const uint64_t wave = fqd_uniform((uint64_t)blockIdx.x * FQD_WAVES + (uint64_t)(t >> 6)), n_waves = (uint64_t)gridDim.x * FQD_WAVES;
+    uint64_t acc = 0; // lane w: what the wave's reads add to word w
+    for (uint64_t g = wave; g < groups; g += n_waves) {
+        // lane j: where the seq line of read 64 g + j lies, from its descriptor's two words, by coalesced loads
+        const uint64_t base = 64 * g, mine = base + (uint64_t)lane;
+        const int n = (int)min((uint64_t)64, R - base); // uniform
+        uint64_t my_L = 0, my_sq = 0;
+        if (mine < R) {
+            const int i = split ? (int)(mine & 1) : 0;
+            const uint64_t k = split ? mine >> 1 : mine;
+            if (k < a.s.slots[i]) { // (always: every record with a line has a slot)
+                const uint64_t *d = a.s.desc[i] + 5 * k;
+                const fqc_span sp = fqc_line(d[1], d[2], i ? bytes[1] : bytes[0]);
+                my_L = sp.L;
+                my_sq = sp.sq;
+            }
+        }
+        auto line = [&](int j) {
+            const int i = split ? j & 1 : 0; // base is even: read base + j lies in input j & 1
+            fqd_line ln;
+            ln.text = a.s.text[i];
+            ln.bytes = i ? bytes[1] : bytes[0];
+            ln.sq = fqd_lane64(my_sq, j);
+            ln.L = fqd_lane64(my_L, j);
+            return ln;
+        };
+        uint32_t my_clip = SK_FQ_CLIP_NONE;
+        // read j + 1's first three tiles are loaded while read j is searched
+        fqd_line cur = line(0);
+        uint32_t c0 = fqd_raw(cur, 0, lane), c1 = fqd_raw(cur, 64, lane), c2 = fqd_raw(cur, 128, lane);
+        for (int j = 0; j < n; ++j) {
+            fqd_line nxt = cur;
+            uint32_t n0 = 0, n1 = 0, n2 = 0;
+            if (j + 1 < n) {
+                nxt = line(j + 1);
+                n0 = fqd_raw(nxt, 0, lane);
+                n1 = fqd_raw(nxt, 64, lane);
+                n2 = fqd_raw(nxt, 128, lane);
+            }
+            const fqd_read rd = fqd_search_line<N>(a.codes, cur, c0, c1, c2, lane);
+            if (!rd.hit) { // uniform, and most reads
+                acc += lane == FQC_W_READS;
+            } else {
+                if (lane >= FQC_W_READS && lane < FQC_W_RESERVED) acc += fqc_read_word((uint32_t)lane, &rd);
+                if (lane == j) my_clip = fqd_clip_word(&rd);
+            }
+            cur = nxt;
+            c0 = n0;
+            c1 = n1;
+            c2 = n2;
+        }
+        if (mine < R) a.clip[mine] = my_clip; // the group's words in one store; mine < R <= n_pack
+    }
+    if (lane < FQC_WORDS && acc) atomicAdd(&s_sum[lane], (fqd_ull)acc);
+    __syncthreads();
+    if (t >= FQC_W_READS && t < FQC_W_RESERVED && s_sum[t]) atomicAdd(reinterpret_cast<fqd_ull *>(a.stats + t), s_sum[t]);
+}
+
+// behind the emission, one workgroup: the call-local sums into the caller's struct iff the call adds (fqd_valid)
+__global__ void __launch_bounds__(64) sk_fq_clip_commit_kernel(fqd_args a, const uint64_t *local, uint64_t *stats)
+{
+    const uint32_t w = threadIdx.x;
+    if (w >= FQC_W_RESERVED) return;
+    const bool valid = fqd_valid(a); // uniform
+    uint64_t add = 0;
+    if (valid) add = w == FQC_W_CALLS ? 1 : w >= FQC_W_READS ? local[w] : 0;
+    else add = w == FQC_W_CALLS_FAILED;
+    if (add) atomicAdd(reinterpret_cast<fqd_ull *>(stats + w), (fqd_ull)add);
+}
+
 } // namespace
 
 // the arguments have passed the checks of sk_trim_fastq_adapters_device_async (sk_capi.hip)
@@ -347,5 +461,59 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adap
     case 7: hipLaunchKernelGGL(sk_fq_adapters_kernel<7>, grid, threads, 0, stream, a); break;
     default: hipLaunchKernelGGL(sk_fq_adapters_kernel<8>, grid, threads, 0, stream, a); break;
     }
+    return hipGetLastError();
+}
+
+// the set has passed fqd_set_error (sk_trim_fastq_clipped_device_async, sk_capi.hip)
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip(const sk_fq_clip_src *src,
+                                                                                 const sk_fq_clip_front *clip, int cu_count,
+                                                                                 hipStream_t stream)
+{
+    fqc_args a = {};
+    a.s = *src;
+    a.stats = static_cast<uint64_t *>(clip->section);
+    a.clip = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(clip->section) + FQC_STATS_BYTES);
+    fqd_encode_set(clip->set, &a.codes);
+    hipLaunchKernelGGL(sk_fq_clip_reset_kernel, dim3(1), dim3(64), 0, stream, a.stats);
+    // the adapters' grid: a wave a group of 64 reads, the rest of the groups in strides of the grid
+    uint64_t blocks = ((src->n_pack + 63) / 64 + FQD_WAVES - 1) / FQD_WAVES;
+    const uint64_t cap = cu_count > 0 ? min((uint64_t)cu_count * 16u, (uint64_t)FQD_MAX_BLOCKS) : FQD_MAX_BLOCKS;
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    const dim3 grid((unsigned)blocks), threads(FQD_THREADS);
+    switch (a.codes.n) {
+    case 1: hipLaunchKernelGGL(sk_fq_clip_kernel<1>, grid, threads, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(sk_fq_clip_kernel<2>, grid, threads, 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(sk_fq_clip_kernel<3>, grid, threads, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL(sk_fq_clip_kernel<4>, grid, threads, 0, stream, a); break;
+    case 5: hipLaunchKernelGGL(sk_fq_clip_kernel<5>, grid, threads, 0, stream, a); break;
+    case 6: hipLaunchKernelGGL(sk_fq_clip_kernel<6>, grid, threads, 0, stream, a); break;
+    case 7: hipLaunchKernelGGL(sk_fq_clip_kernel<7>, grid, threads, 0, stream, a); break;
+    default: hipLaunchKernelGGL(sk_fq_clip_kernel<8>, grid, threads, 0, stream, a); break;
+    }
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip_reset(sk_fastq_clip_stats *stats_dev,
+                                                                                       hipStream_t stream)
+{
+    hipLaunchKernelGGL(sk_fq_clip_reset_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<uint64_t *>(stats_dev));
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip_commit(const void *workspace, uint32_t kind,
+                                                                                        int mode, const void *section,
+                                                                                        sk_fastq_clip_stats *stats_dev,
+                                                                                        hipStream_t stream)
+{
+    const uint8_t *base = static_cast<const uint8_t *>(workspace);
+    fqd_args a = {}; // the words fqd_valid reads
+    a.hdr = reinterpret_cast<const uint64_t *>(base);
+    if (kind == SK_FQ_REPORT_ORDERED) a.order_words = a.hdr;
+    else if (kind == SK_FQ_REPORT_ORDERED_PIECE) a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
+    a.kind = (int32_t)kind;
+    a.mode = fqa_framing_mode(mode);
+    hipLaunchKernelGGL(sk_fq_clip_commit_kernel, dim3(1), dim3(64), 0, stream, a, static_cast<const uint64_t *>(section),
+                       reinterpret_cast<uint64_t *>(stats_dev));
     return hipGetLastError();
 }

@@ -143,6 +143,22 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
     if (!valid) return;
     const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
     if (R == 0) return;
+    // The pass below walks packed positions and meets a read at its bytes, so a read of no bases is met nowhere.  No text
+    // that passes the checks holds one, but a clipped call (sk_trim_fastq_clipped_device_async) packs one for every read
+    // with its hit at 0: a read that came in, that the scan discarded, and that has no A, C, G or T.  The workgroups share
+    // the reads evenly and count them from the offsets: a coalesced load a read, and no atomic where there is none.
+    {
+        const uint64_t r0 = R / gridDim.x * blockIdx.x + min((uint64_t)blockIdx.x, R % gridDim.x);
+        const uint64_t r1 = r0 + R / gridDim.x + (blockIdx.x < R % gridDim.x ? 1 : 0);
+        uint32_t empty = 0;
+        for (uint64_t k = r0 + t; k < r1; k += FQB_THREADS) empty += a.offsets[k] == a.offsets[k + 1]; // k + 1 <= R
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) empty += __shfl_xor(empty, d);
+        if (lane == 0 && empty) {
+            fqb_add(a.bas + FQB_W_READS, empty);
+            fqb_add(a.bas + FQB_W_GC_NONE_IN, empty);
+        }
+    }
     // == SK_FQ_H_PACKED: the reads behind the count are empty.  (Never beyond the section, and the walks below never leave
     // offsets[0 .. R]: a source that names the wrong layout gives wrong numbers, not loads outside the workspace.)
     const uint64_t total = min(a.offsets[R], a.q_bound);
