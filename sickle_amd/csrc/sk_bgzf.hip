@@ -18,10 +18,9 @@
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
+#include "sk_device_prims.h"
 #include "sk_bgzf_args.h"
 #include "sk_bgzf_block.h"
-
-typedef unsigned bz_u4 __attribute__((ext_vector_type(4)));
 
 #define BZ_THREADS 256
 #define BZ_PACK_WG_PER_CU 8u
@@ -83,39 +82,6 @@ __global__ void __launch_bounds__(SKD_LANES) sk_bgzf_block_kernel(bz_args a)
 // ------------------------------------------------------------------------------------------
 // 2 scan of the member sizes (one workgroup), counts and verdict
 // ------------------------------------------------------------------------------------------
-// exclusive prefix sums of two values over the workgroup; total[] = the sums over it.  lds: 2 * BZ_THREADS / 64 words.
-__device__ __forceinline__ void bz_block_scan(uint64_t (&v)[2], uint64_t (&total)[2], uint64_t *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc[2] = {v[0], v[1]};
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint64_t t = __shfl_up(inc[i], d);
-            if (lane >= d) inc[i] += t;
-        }
-    }
-    if (lane == 63) {
-        lds[w * 2] = inc[0];
-        lds[w * 2 + 1] = inc[1];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        uint64_t base = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < BZ_THREADS / 64; ++ww) {
-            const uint64_t x = lds[ww * 2 + i];
-            base += ww < w ? x : 0;
-            tot += x;
-        }
-        v[i] = base + inc[i] - v[i];
-        total[i] = tot;
-    }
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(BZ_THREADS) sk_bgzf_scan_kernel(bz_args a)
 {
     __shared__ uint64_t lds[2 * BZ_THREADS / 64];
@@ -129,7 +95,7 @@ __global__ void __launch_bounds__(BZ_THREADS) sk_bgzf_scan_kernel(bz_args a)
             v[0] = skb_member_bytes(body & ~SKB_STORED_FLAG);
             v[1] = body >> 31;
         }
-        bz_block_scan(v, tot, lds);
+        sk_block_scan<2, BZ_THREADS>(v, tot, lds);
         if (b < nb) a.table[b].off = run[0] + v[0];
         run[0] += tot[0];
         run[1] += tot[1];
@@ -147,31 +113,6 @@ __global__ void __launch_bounds__(BZ_THREADS) sk_bgzf_scan_kernel(bz_args a)
 // ------------------------------------------------------------------------------------------
 // 3 pack
 // ------------------------------------------------------------------------------------------
-// the 16 bytes at p as a granule, from aligned 16-byte loads only (== load_window of sk_trim.hip with n = 16): both blocks
-// touched hold a byte of [p, p + 16), so nothing beyond the buffer that holds them is read, whatever p's alignment
-__device__ __forceinline__ bz_u4 bz_load_window(const uint8_t *p)
-{
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
-    const bz_u4 *blk = reinterpret_cast<const bz_u4 *>(ad & ~(uintptr_t)15);
-    const int sh = (int)(ad & 15);
-    const bz_u4 lo = blk[0];
-    if (sh == 0) return lo;
-    const bz_u4 hi = blk[1];
-    const int s4 = sh >> 2, sb = sh & 3;
-    const uint32_t x0 = lo.x, x1 = lo.y, x2 = lo.z, x3 = lo.w, x4 = hi.x, x5 = hi.y, x6 = hi.z, x7 = hi.w;
-    const uint32_t y0 = s4 == 0 ? x0 : s4 == 1 ? x1 : s4 == 2 ? x2 : x3;
-    const uint32_t y1 = s4 == 0 ? x1 : s4 == 1 ? x2 : s4 == 2 ? x3 : x4;
-    const uint32_t y2 = s4 == 0 ? x2 : s4 == 1 ? x3 : s4 == 2 ? x4 : x5;
-    const uint32_t y3 = s4 == 0 ? x3 : s4 == 1 ? x4 : s4 == 2 ? x5 : x6;
-    const uint32_t y4 = s4 == 0 ? x4 : s4 == 1 ? x5 : s4 == 2 ? x6 : x7;
-    bz_u4 r;
-    r.x = __builtin_amdgcn_alignbyte(y1, y0, sb);
-    r.y = __builtin_amdgcn_alignbyte(y2, y1, sb);
-    r.z = __builtin_amdgcn_alignbyte(y3, y2, sb);
-    r.w = __builtin_amdgcn_alignbyte(y4, y3, sb);
-    return r;
-}
-
 __global__ void __launch_bounds__(BZ_THREADS) sk_bgzf_pack_kernel(bz_args a)
 {
     if (!a.hdr[SK_BGZF_H_FIT]) return; // uniform: an image beyond the capacity leaves `out` untouched
@@ -189,7 +130,7 @@ __global__ void __launch_bounds__(BZ_THREADS) sk_bgzf_pack_kernel(bz_args a)
         const uint64_t off = e.off, end = off + m;
         for (uint64_t g = (off & ~15ull) + 16u * threadIdx.x; g < end; g += 16u * BZ_THREADS) {
             if (g >= off + head && g + 16 <= off + tail) { // the granule lies inside the body: the fast path
-                __builtin_nontemporal_store(bz_load_window(src + (g - off - head)), reinterpret_cast<bz_u4 *>(a.out + g));
+                __builtin_nontemporal_store(sk_load_window(src + (g - off - head), 16), reinterpret_cast<sk_u4 *>(a.out + g));
                 continue;
             }
             const uint64_t lo = max(g, off), hi = min(g + 16, end);

@@ -156,39 +156,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_trim(const
 // the lines of any text, valid or not: b bytes hold at most b lines, so b / 4 + 1 slots take every line of text i, and
 // the ordered calls, whose batches and counts are a matter of lines alone, see all of them (with (b + 1) / 8 + 1 slots
 // they stopped at the last slot of a text of empty lines).  The clamps at the slot count in the kernels never bite.
-#define SK_FQ_CHUNK_BYTES 65536u
-#define SK_FQ_BLOCK_READS 2048u
-#define SK_FQ_BLOCK_WORDS 8u
-// SK_FQ_HDR_WORDS and the header's words, SK_FQ_H_* and the piece calls' SK_FQP_H_*: sk_fastq_words.h (no HIP: the host reads them too)
+// SK_FQ_HDR_WORDS and the header's words, SK_FQ_H_* and the piece calls' SK_FQP_H_*, the sections (sk_fq_layout_of, SK_FQ_CHUNK_BYTES,
+// SK_FQ_BLOCK_READS) and the ordered calls' shifts: sk_fastq_words.h (no HIP: the host reads them too)
 struct sk_fq_clip_front;
-struct sk_fq_layout {
-    uint64_t chunks, desc, offsets, cuts, blocks, emit, qual, seq, total; // byte offsets of the sections, total size
-};
-static inline uint64_t sk_fq_slots(uint64_t bytes) { return bytes / 4 + 1; }
-// reads of the packed batch: the most valid records the text(s) can hold
-static inline uint64_t sk_fq_pack_reads(uint64_t bytes0, uint64_t bytes1, int mode)
-{
-    const uint64_t r0 = (bytes0 + 1) / 8, r1 = (bytes1 + 1) / 8;
-    return mode == SK_TRIM_PE_SPLIT ? 2 * (r0 < r1 ? r0 : r1) : r0;
-}
-static inline void sk_fq_layout_of(uint64_t text_bytes, int trunc_n, sk_fq_layout *L)
-{
-    const uint64_t H = (text_bytes + 2) / 16, S = 2 * ((text_bytes + 7) / 8) + 2, N = 2 * H + 2; // S >= b0 / 4 + b1 / 4 + 2
-    const uint64_t NC = text_bytes / SK_FQ_CHUNK_BYTES + 3, NB = (N + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
-    const uint64_t Q = 16 * ((text_bytes + 31) / 32);
-    L->chunks = 8 * SK_FQ_HDR_WORDS;
-    L->desc = L->chunks + 16 * NC;
-    L->offsets = L->desc + 40 * S;
-    L->cuts = L->offsets + 8 * (N + 2);
-    L->blocks = L->cuts + 8 * N;
-    L->emit = L->blocks + 64 * NB;
-    L->qual = L->emit + 16 * N;
-    L->seq = L->qual + Q;
-    L->total = L->seq + (trunc_n ? Q : 0);
-}
-// Ordered calls (sk_trim_fastq_ordered_device_async, sk_fastq_order.h): the same header (its words 21.. are theirs), then
-// the table of first units (8 * (batch_capacity + 1), rounded up to 16), then the sections above, shifted by the table.
-static inline uint64_t sk_fq_order_shift(uint64_t batch_capacity) { return (8 * (batch_capacity + 1) + 15) & ~15ull; }
 // order: NULL = read order (sk_trim_fastq_device_async).  lengths: NULL = in->bytes are the texts' lengths; else
 // (sk_trim_fastq_chained_device_async) in->bytes are bounds and the framing kernels, the only ones that look at a text's
 // length, take it from the device words: everything behind them reads lines and records from the header.
@@ -218,11 +188,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_emit
                                                                                  const sk_fastq_output *out, void *workspace,
                                                                                  const unsigned long long *errword, int cu_count,
                                                                                  hipStream_t stream);
-// Ordered pieces (sk_trim_fastq_ordered_piece_device_async): the header with the PIECE's words 21.. (SK_FQP_H_*), then an
-// extension block of 256 bytes that holds the order words at their usual indices and the piece's own (sk_fastq_order.h:
-// SK_FQOP_*), then the table of first units, then the sections, shifted by block and table.  state_in / state_out:
-// sk_fastq_order_state in device memory (state_in NULL = the start of a stream).
-static inline uint64_t sk_fq_order_piece_shift(uint64_t batch_capacity) { return 256 + sk_fq_order_shift(batch_capacity); }
+// Ordered pieces (sk_trim_fastq_ordered_piece_device_async; the workspace: sk_fq_order_piece_shift, sk_fastq_words.h).
+// state_in / state_out: sk_fastq_order_state in device memory (state_in NULL = the start of a stream).
 extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_order_piece_front(
     const sk_fastq_input *in, const sk_fastq_lengths *lengths, int mode, int trunc_n, int counted, const sk_fastq_order *order,
     const sk_fastq_piece *piece, const void *state_in, void *state_out, const unsigned long long *errword, void *workspace,

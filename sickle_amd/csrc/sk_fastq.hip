@@ -21,19 +21,18 @@
 // frame scan takes whole records (pairs) only when more text follows, and the emission's scan publishes what was consumed
 // and the ok word for the carry kernel of sk_fastq_piece.hip; everything else runs as it does for a whole text.
 // The workspace layout and the header words are in sk_device.h.  The gathers build aligned 16-byte granules from aligned
-// 16-byte loads funnel-shifted by v_alignbyte (fq_load_window, a copy of sk_trim.hip's load_window), so the text may
+// 16-byte loads funnel-shifted by v_alignbyte (sk_load_window, sk_device_prims.h), so the text may
 // have any alignment and no load touches a 16-byte block without a wanted byte.
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
+#include "sk_device_prims.h"
 #include "sk_fastq_clip.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_record.h"
 
 namespace {
 
-typedef unsigned fq_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned __int128 fq_u128;
 
 #define FQ_THREADS 256
 #define FQ_SUB (FQ_THREADS * 16u)                        // text bytes of one pass of a framing workgroup
@@ -108,8 +107,8 @@ __device__ __forceinline__ uint32_t fq_nl_mask(const fq_args &a, int i, uint64_t
 {
     const uint64_t span = (reinterpret_cast<uintptr_t>(a.text[i]) & 15) + n;
     if (q + 16 <= sh || q >= span) return 0;
-    const fq_u4 *blk = reinterpret_cast<const fq_u4 *>((reinterpret_cast<uintptr_t>(a.text[i]) & ~(uintptr_t)15) + q);
-    const fq_u4 v = __builtin_nontemporal_load(blk);
+    const sk_u4 *blk = reinterpret_cast<const sk_u4 *>((reinterpret_cast<uintptr_t>(a.text[i]) & ~(uintptr_t)15) + q);
+    const sk_u4 v = __builtin_nontemporal_load(blk);
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
     uint32_t m = 0;
 #pragma unroll
@@ -167,42 +166,6 @@ __device__ __forceinline__ void fq_scan2(uint64_t s, uint64_t m, uint64_t &s_ex,
     m_ex = max(bm, pm);
     s_tot = ts;
     m_tot = tm;
-    __syncthreads();
-}
-
-// exclusive prefix sums of N values over the workgroup; total[] = the sums over it.  lds: 4 * N words.  (== block_scan
-// of sk_trim.hip)
-template <int N>
-__device__ __forceinline__ void fq_block_scan(uint64_t (&v)[N], uint64_t (&total)[N], uint64_t *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) inc[i] = v[i];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const uint64_t t = __shfl_up(inc[i], d);
-            if (lane >= d) inc[i] += t;
-        }
-    }
-    if (lane == 63)
-#pragma unroll
-        for (int i = 0; i < N; ++i) lds[w * N + i] = inc[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        uint64_t base = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < FQ_THREADS / 64; ++ww) {
-            const uint64_t x = lds[ww * N + i];
-            base += ww < w ? x : 0;
-            tot += x;
-        }
-        v[i] = base + inc[i] - v[i];
-        total[i] = tot;
-    }
     __syncthreads();
 }
 
@@ -420,7 +383,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_count_kernel(fq_args a)
     uint64_t v[1] = {0}, tot[1];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j) v[0] += fq_pack_len(a, first + j, n_real, bad);
-    fq_block_scan<1>(v, tot, lds);
+    sk_block_scan<1, FQ_THREADS>(v, tot, lds);
     if (threadIdx.x == 0) a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS] = tot[0];
 }
 
@@ -435,7 +398,7 @@ __device__ __forceinline__ void fq_scan_blocks(const fq_args &a, uint64_t (&run)
         uint64_t v[N], tot[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) v[i] = b < a.n_blocks ? a.blk[b * SK_FQ_BLOCK_WORDS + i] : 0;
-        fq_block_scan<N>(v, tot, lds);
+        sk_block_scan<N, FQ_THREADS>(v, tot, lds);
         if (b < a.n_blocks)
 #pragma unroll
             for (int i = 0; i < N; ++i) a.blk[b * SK_FQ_BLOCK_WORDS + i] = run[i] + v[i];
@@ -471,7 +434,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_pack_place_kernel(fq_args a)
         len[j] = fq_pack_len(a, first + j, n_real, bad);
         v[0] += len[j];
     }
-    fq_block_scan<1>(v, tot, lds);
+    sk_block_scan<1, FQ_THREADS>(v, tot, lds);
     uint64_t b = v[0] + a.blk[blockIdx.x * SK_FQ_BLOCK_WORDS];
 #pragma unroll
     for (int j = 0; j < FQ_PER_THREAD; ++j) {
@@ -565,7 +528,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_count_kernel(fq_args a)
                 v[o] += 1;
                 v[3 + o] += rd[j].bytes;
             }
-    fq_block_scan<6>(v, tot, lds);
+    sk_block_scan<6, FQ_THREADS>(v, tot, lds);
     if (threadIdx.x < 6) {
         uint64_t x = 0;
 #pragma unroll
@@ -634,7 +597,7 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_place_kernel(fq_args a)
                 v[o] += 1;
                 v[3 + o] += rd[j].bytes;
             }
-    fq_block_scan<6>(v, tot, lds);
+    sk_block_scan<6, FQ_THREADS>(v, tot, lds);
     const uint64_t *blk = a.blk + blockIdx.x * SK_FQ_BLOCK_WORDS;
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] += blk[k];
@@ -657,57 +620,10 @@ __global__ void __launch_bounds__(FQ_THREADS) sk_fq_emit_place_kernel(fq_args a)
 // ------------------------------------------------------------------------------------------
 // 8, 12 gathers
 // ------------------------------------------------------------------------------------------
-// the n (1..16) bytes at p as the first bytes of a granule, from aligned 16-byte loads only (== load_window of
-// sk_trim.hip): both blocks touched hold a byte of [p, p + n)
-__device__ __forceinline__ fq_u4 fq_load_window(const uint8_t *p, int n)
-{
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
-    const fq_u4 *blk = reinterpret_cast<const fq_u4 *>(ad & ~(uintptr_t)15);
-    const int sh = (int)(ad & 15);
-    const fq_u4 lo = blk[0];
-    if (sh == 0) return lo;
-    const fq_u4 hi = sh + n > 16 ? blk[1] : lo;
-    const int s4 = sh >> 2, sb = sh & 3;
-    const uint32_t x0 = lo.x, x1 = lo.y, x2 = lo.z, x3 = lo.w, x4 = hi.x, x5 = hi.y, x6 = hi.z, x7 = hi.w;
-    const uint32_t y0 = s4 == 0 ? x0 : s4 == 1 ? x1 : s4 == 2 ? x2 : x3;
-    const uint32_t y1 = s4 == 0 ? x1 : s4 == 1 ? x2 : s4 == 2 ? x3 : x4;
-    const uint32_t y2 = s4 == 0 ? x2 : s4 == 1 ? x3 : s4 == 2 ? x4 : x5;
-    const uint32_t y3 = s4 == 0 ? x3 : s4 == 1 ? x4 : s4 == 2 ? x5 : x6;
-    const uint32_t y4 = s4 == 0 ? x4 : s4 == 1 ? x5 : s4 == 2 ? x6 : x7;
-    fq_u4 r;
-    r.x = __builtin_amdgcn_alignbyte(y1, y0, sb);
-    r.y = __builtin_amdgcn_alignbyte(y2, y1, sb);
-    r.z = __builtin_amdgcn_alignbyte(y3, y2, sb);
-    r.w = __builtin_amdgcn_alignbyte(y4, y3, sb);
-    return r;
-}
-
-__device__ __forceinline__ fq_u128 fq_to_u128(fq_u4 v)
-{
-    return (fq_u128)v.x | ((fq_u128)v.y << 32) | ((fq_u128)v.z << 64) | ((fq_u128)v.w << 96);
-}
-
-__device__ __forceinline__ fq_u4 fq_from_u128(fq_u128 v)
-{
-    fq_u4 r;
-    r.x = (uint32_t)v;
-    r.y = (uint32_t)(v >> 32);
-    r.z = (uint32_t)(v >> 64);
-    r.w = (uint32_t)(v >> 96);
-    return r;
-}
-
-// bytes [0, n) of x to bytes [d, d + n) of acc (d + n <= 16)
-__device__ __forceinline__ void fq_place(fq_u128 &acc, fq_u128 x, int d, int n)
-{
-    const fq_u128 m = n >= 16 ? ~(fq_u128)0 : (((fq_u128)1 << (8 * n)) - 1);
-    acc |= (x & m) << (8 * d);
-}
-
-__device__ __forceinline__ void fq_store_granule(uint8_t *dst, uint64_t g, fq_u128 x, int n)
+__device__ __forceinline__ void fq_store_granule(uint8_t *dst, uint64_t g, sk_u128 x, int n)
 {
     if (n == 16) {
-        __builtin_nontemporal_store(fq_from_u128(x), reinterpret_cast<fq_u4 *>(dst + g));
+        __builtin_nontemporal_store(sk_from_u128(x), reinterpret_cast<sk_u4 *>(dst + g));
     } else {
         for (int i = 0; i < n; ++i) dst[g + i] = (uint8_t)(x >> (8 * i));
     }
@@ -730,7 +646,7 @@ __device__ __forceinline__ void fq_pieces_at(const uint8_t *text, const fqr_piec
 // bytes [rel, rel + n) of a record made of NP pieces to bytes [d, d + n) of acc.  WIDE: an immediate may have more than one
 // byte (the N record's); else every immediate is one byte, a '\n'.
 template <int NP, bool WIDE>
-__device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, int d, int n, fq_u128 &acc)
+__device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, int d, int n, sk_u128 &acc)
 {
     uint64_t ps = 0;
 #pragma unroll
@@ -739,11 +655,11 @@ __device__ __forceinline__ void fq_fill(const fq_piece (&pc)[NP], uint64_t rel, 
         if (n > 0 && rel < pe && rel >= ps) {
             const int t = (int)min((uint64_t)n, pe - rel);
             if (pc[j].src)
-                fq_place(acc, fq_to_u128(fq_load_window(pc[j].src + (rel - ps), t)), d, t);
+                sk_put(acc, sk_to_u128(sk_load_window(pc[j].src + (rel - ps), t)), d, t);
             else if (WIDE)
-                fq_place(acc, (fq_u128)(pc[j].imm >> (8 * (rel - ps))), d, t);
+                sk_put(acc, (sk_u128)(pc[j].imm >> (8 * (rel - ps))), d, t);
             else
-                fq_place(acc, (fq_u128)pc[j].imm, d, 1);
+                sk_put(acc, (sk_u128)pc[j].imm, d, 1);
             rel += t;
             d += t;
             n -= t;
@@ -766,7 +682,7 @@ struct fq_job {
 // fqr_pieces has constant kinds, lengths and immediates where it always had them.
 template <bool COMBO>
 __device__ __forceinline__ void fq_record_bytes(const fq_args &a, const fq_job &j, uint64_t k, uint64_t rel, int d, int n,
-                                                fq_u128 &acc)
+                                                sk_u128 &acc)
 {
     if (j.kind < 2) {
         const fq_rec x = fq_record(a, k);
@@ -852,7 +768,7 @@ __device__ __forceinline__ void fq_gather(const fq_args &a, int emit)
                 }
                 k_last = k;
                 const uint64_t end = min(g + 16, j.total);
-                fq_u128 acc = 0;
+                sk_u128 acc = 0;
                 uint64_t pos = g;
                 while (pos < end) {
                     const uint64_t i = k - cur;
@@ -1073,7 +989,7 @@ __device__ __forceinline__ void fq_order_emit_count(const fq_args &a, const fq_o
                 v[k] += 1;
                 v[3 + k] += rd[j].bytes;
             }
-    fq_block_scan<6>(v, tot, lds);
+    sk_block_scan<6, FQ_THREADS>(v, tot, lds);
     if (threadIdx.x < 6) {
         uint64_t x = 0;
 #pragma unroll
@@ -1139,7 +1055,7 @@ __device__ __forceinline__ void fq_order_emit_place(const fq_args &a, const fq_o
                 v[k] += 1;
                 v[3 + k] += rd[j].bytes;
             }
-    fq_block_scan<6>(v, tot, lds);
+    sk_block_scan<6, FQ_THREADS>(v, tot, lds);
     const uint64_t *blk = a.blk + blockIdx.x * SK_FQ_BLOCK_WORDS;
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] += blk[k];

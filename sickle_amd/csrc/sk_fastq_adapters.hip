@@ -25,10 +25,10 @@
 //             registers over the wave's reads, then over the workgroup's waves in LDS, then one global atomic per non-zero
 //             word.  pos and overlap take one global atomic per hit, by lane 0; the clip words of a wave's 64 reads leave
 //             in one coalesced store, lane j's the word of read j.
-// Every workgroup takes the call's validity from the header (fqd_valid) and leaves at once when the call does not add.
-// Every descriptor index is bounded by the slots of the section, every offsets index by the reads the section holds, every
-// seq byte by in->bytes[i], a line's length by SK_MAX_READ_LEN: a source that names the wrong layout or the wrong texts
-// gives wrong numbers, no load outside the workspace and the texts, and no unbounded walk.
+// Every workgroup takes the call's validity from the header (fqs_valid) and leaves at once when the call does not add.
+// A source that names the wrong layout or the wrong texts gives wrong numbers, no load outside the workspace and the
+// texts, and no unbounded walk: the bounds and the seq line's clamps are the source view's (sk_fastq_source.h), fqd_raw
+// holds every seq byte to in->bytes[i], and a line's length is SK_MAX_READ_LEN at most.
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
@@ -37,6 +37,7 @@
 #include "sk_fastq_clip.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_report.h"
+#include "sk_fastq_source.h"
 
 namespace {
 
@@ -49,50 +50,14 @@ typedef unsigned long long fqd_ull;
 static_assert(FQD_WORDS <= 64, "a lane holds a word of the struct");
 
 struct fqd_args {
-    const uint64_t *hdr;
-    const uint64_t *order_words; // ordered kinds: where the SK_FQO_H_* words lie
-    const uint64_t *desc;        // 5 words per slot, input 0's slots first
-    const uint64_t *offsets;
-    const sk_cut_dev *cuts;
+    fqs_view s;    // the call behind
     uint64_t *res; // sk_fastq_adapters as FQD_WORDS words
     uint64_t *pos, *overlap;
     uint32_t *clip;
     uint64_t clip_capacity;
-    const uint8_t *text[2];
-    uint64_t bytes[2];
-    uint64_t slots0;     // input 0's slots: input 1's descriptors lie behind them
-    uint64_t slot_bound; // slots of the descriptor section
-    uint64_t n_bound;    // the most reads the packed batch can hold
     uint32_t pos_bins;
-    int32_t kind;
-    int32_t mode; // the call's framing mode
     fqd_codes codes;
 };
-
-__device__ __forceinline__ bool fqd_valid(const fqd_args &a)
-{
-    const uint64_t *h = a.hdr;
-    const bool piece = a.kind == SK_FQ_REPORT_PIECE || a.kind == SK_FQ_REPORT_ORDERED_PIECE;
-    const uint64_t range0 = piece ? h[SK_FQP_H_RANGE0] : ~0ull;
-    bool refused = false;
-    if (a.order_words) {
-        refused = a.order_words[SK_FQO_H_LONG] != ~0ull || a.order_words[SK_FQO_H_OVERFLOW] != 0;
-        if (a.kind == SK_FQ_REPORT_ORDERED_PIECE && a.order_words[SK_FQOP_X_INHERITED]) refused = true; // void
-    }
-    return (int64_t)h[SK_FQ_H_MODE] == (int64_t)a.mode && fqp_call_valid(h[SK_FQ_H_FMT], h[SK_FQ_H_RANGE], range0, refused);
-}
-
-__device__ __forceinline__ int fqd_input(const fqd_args &a, uint64_t r) { return a.mode == SK_TRIM_PE_SPLIT ? (int)(r & 1) : 0; }
-
-// where the seq line of read r starts in its text, never beyond the text; the text's length: no descriptor slot for it
-__device__ __forceinline__ uint64_t fqd_seq_start(const fqd_args &a, uint64_t r)
-{
-    const int i = fqd_input(a, r);
-    const uint64_t k = a.mode == SK_TRIM_PE_SPLIT ? r >> 1 : r;
-    const uint64_t slot = (i ? a.slots0 : 0) + k;
-    if (slot >= a.slot_bound) return a.bytes[i];
-    return min(min(a.desc[5 * slot + 1], a.bytes[i]) + 1, a.bytes[i]);
-}
 
 // a seq line as the wave sees it: wave-uniform
 struct fqd_line {
@@ -206,14 +171,14 @@ __global__ void __launch_bounds__(FQD_THREADS) sk_fq_adapters_kernel(fqd_args a)
 {
     __shared__ fqd_ull s_sum[FQD_WORDS];
     const int t = threadIdx.x, lane = t & 63;
-    const bool valid = fqd_valid(a); // uniform
+    const bool valid = fqs_valid(a.s); // uniform
     if (blockIdx.x == 0 && t == 0) atomicAdd(reinterpret_cast<fqd_ull *>(a.res + (valid ? FQD_W_CALLS : FQD_W_CALLS_FAILED)), 1ull);
     if (!valid) return;
-    const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    const uint64_t R = fqs_reads(a.s);
     if (R == 0) return;
     if (t < FQD_WORDS) s_sum[t] = 0;
     __syncthreads();
-    const bool pairs = a.mode != SK_TRIM_SE, split = a.mode == SK_TRIM_PE_SPLIT;
+    const bool pairs = a.s.mode != SK_TRIM_SE, split = a.s.mode == SK_TRIM_PE_SPLIT;
     const uint64_t groups = (R + 63) / 64; // 64 consecutive reads, whole pairs, a wave's turn
     const uint64_t wave = fqd_uniform((uint64_t)blockIdx.x * FQD_WAVES + (uint64_t)(t >> 6)), n_waves = (uint64_t)gridDim.x * FQD_WAVES;
     uint64_t acc = 0; // lane w: what the wave's reads add to word w
@@ -224,16 +189,16 @@ __global__ void __launch_bounds__(FQD_THREADS) sk_fq_adapters_kernel(fqd_args a)
         uint64_t my_L = 0, my_sq = 0;
         sk_cut_dev my_cut = {0, -1};
         if (mine < R) {
-            const uint64_t b = a.offsets[mine], e = a.offsets[mine + 1]; // mine < R <= n_bound
+            const uint64_t b = a.s.offsets[mine], e = a.s.offsets[mine + 1]; // mine < R <= n_bound
             my_L = e > b ? min(e - b, (uint64_t)SK_MAX_READ_LEN_DEV) : 0;
-            my_sq = fqd_seq_start(a, mine);
-            my_cut = a.cuts[mine];
+            my_sq = fqs_seq_start(a.s, mine);
+            my_cut = a.s.cuts[mine];
         }
         auto line = [&](int j) {
             const int i = split ? j & 1 : 0; // base is even: read base + j lies in input j & 1
             fqd_line ln;
-            ln.text = a.text[i];
-            ln.bytes = a.bytes[i];
+            ln.text = a.s.text[i];
+            ln.bytes = a.s.bytes[i];
             ln.sq = fqd_lane64(my_sq, j);
             ln.L = fqd_lane64(my_L, j);
             return ln;
@@ -381,12 +346,13 @@ __global__ void __launch_bounds__(FQD_THREADS) sk_fq_clip_kernel(fqc_args a)
     if (t >= FQC_W_READS && t < FQC_W_RESERVED && s_sum[t]) atomicAdd(reinterpret_cast<fqd_ull *>(a.stats + t), s_sum[t]);
 }
 
-// behind the emission, one workgroup: the call-local sums into the caller's struct iff the call adds (fqd_valid)
-__global__ void __launch_bounds__(64) sk_fq_clip_commit_kernel(fqd_args a, const uint64_t *local, uint64_t *stats)
+// behind the emission, one workgroup: the call-local sums into the caller's struct iff the call adds (fqs_valid; s: the
+// words the validity reads)
+__global__ void __launch_bounds__(64) sk_fq_clip_commit_kernel(fqs_view s, const uint64_t *local, uint64_t *stats)
 {
     const uint32_t w = threadIdx.x;
     if (w >= FQC_W_RESERVED) return;
-    const bool valid = fqd_valid(a); // uniform
+    const bool valid = fqs_valid(s); // uniform
     uint64_t add = 0;
     if (valid) add = w == FQC_W_CALLS ? 1 : w >= FQC_W_READS ? local[w] : 0;
     else add = w == FQC_W_CALLS_FAILED;
@@ -403,33 +369,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adap
                                                                                      const sk_fastq_adapters_out *out, int flags,
                                                                                      int cu_count, hipStream_t stream)
 {
-    sk_fq_layout L;
-    sk_fq_layout_of(src->text_bytes, src->trunc_n, &L);
-    const uint8_t *base = static_cast<const uint8_t *>(src->workspace);
-    uint64_t shift = 0;
     fqd_args a = {};
-    a.hdr = reinterpret_cast<const uint64_t *>(base);
-    if (src->kind == SK_FQ_REPORT_ORDERED) {
-        shift = sk_fq_order_shift(src->batch_capacity);
-        a.order_words = a.hdr;
-    } else if (src->kind == SK_FQ_REPORT_ORDERED_PIECE) {
-        shift = sk_fq_order_piece_shift(src->batch_capacity);
-        a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
-    }
-    a.desc = reinterpret_cast<const uint64_t *>(base + shift + L.desc);
-    a.offsets = reinterpret_cast<const uint64_t *>(base + shift + L.offsets);
-    a.cuts = reinterpret_cast<const sk_cut_dev *>(base + shift + L.cuts);
+    fqs_fill(src, in, mode, &a.s);
     a.res = reinterpret_cast<uint64_t *>(adapters_dev);
-    a.kind = (int32_t)src->kind;
-    a.mode = fqa_framing_mode(mode);
-    a.n_bound = 2 * ((src->text_bytes + 2) / 16) + 2; // N of sk_fq_layout_of: the offsets and cuts sections hold this many reads
-    a.slot_bound = (L.offsets - L.desc) / 40;
-    const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
-    for (int i = 0; i < n_in; ++i) {
-        a.text[i] = static_cast<const uint8_t *>(in->text[i]);
-        a.bytes[i] = in->text[i] ? in->bytes[i] : 0;
-    }
-    a.slots0 = sk_fq_slots(a.bytes[0]);
     if (out) {
         a.pos = out->pos;
         a.pos_bins = out->pos ? (uint32_t)out->pos_bins : 0;
@@ -446,7 +388,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_adap
     }
     // a wave a group of 64 reads, at most a few workgroups a CU: the rest of the groups in strides of the grid; block 0 counts
     // the call
-    uint64_t blocks = ((a.n_bound + 63) / 64 + FQD_WAVES - 1) / FQD_WAVES;
+    uint64_t blocks = ((a.s.n_bound + 63) / 64 + FQD_WAVES - 1) / FQD_WAVES;
     const uint64_t cap = cu_count > 0 ? min((uint64_t)cu_count * 16u, (uint64_t)FQD_MAX_BLOCKS) : FQD_MAX_BLOCKS;
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
@@ -506,14 +448,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_clip
                                                                                         sk_fastq_clip_stats *stats_dev,
                                                                                         hipStream_t stream)
 {
-    const uint8_t *base = static_cast<const uint8_t *>(workspace);
-    fqd_args a = {}; // the words fqd_valid reads
-    a.hdr = reinterpret_cast<const uint64_t *>(base);
-    if (kind == SK_FQ_REPORT_ORDERED) a.order_words = a.hdr;
-    else if (kind == SK_FQ_REPORT_ORDERED_PIECE) a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
-    a.kind = (int32_t)kind;
-    a.mode = fqa_framing_mode(mode);
-    hipLaunchKernelGGL(sk_fq_clip_commit_kernel, dim3(1), dim3(64), 0, stream, a, static_cast<const uint64_t *>(section),
+    fqs_view s = {};
+    fqs_fill_validity(workspace, kind, mode, &s);
+    hipLaunchKernelGGL(sk_fq_clip_commit_kernel, dim3(1), dim3(64), 0, stream, s, static_cast<const uint64_t *>(section),
                        reinterpret_cast<uint64_t *>(stats_dev));
     return hipGetLastError();
 }

@@ -128,9 +128,6 @@ FQA_FN uint32_t fqa_pair(const uint8_t *n1, uint64_t len1, const uint8_t *n2, ui
     return t1 == 2 && t2 == 1 ? FQA_SWAPPED : 0u;
 }
 
-// the framing mode of a call's mode: SK_TRIM_PE_COMBO_ALL frames as SK_TRIM_PE_INTERLEAVED
-FQA_FN int fqa_framing_mode(int mode) { return mode == SK_TRIM_PE_COMBO_ALL ? SK_TRIM_PE_INTERLEAVED : mode; }
-
 // A granule of 16 packed bytes (byte i in bits 8 (i & 3) of word[i >> 2]) of which only the first n (1 <= n < 16) are
 // quality bytes, the batch's last: the bytes behind them become copies of the first, which changes no extreme.
 FQA_FN void fqa_fill_tail(uint32_t *word, uint32_t n)

@@ -15,16 +15,17 @@
 //            of FQA_TABLES private LDS tables.
 //   3 fold   one lane: counts the call (calls / calls_failed) and folds the two reserved words into first_mismatch and
 //            pairs (fqa_fold).  It runs behind this call's passes and in front of the next call's, by the stream's order.
-// Every workgroup takes the call's validity from the header (fqa_valid) and leaves at once when the call does not add.
-// Blocks at or beyond SK_FQ_H_NREAL load nothing.  Every descriptor index is bounded by the slots of the section, every
-// name byte by in->bytes[i], every quality byte by the section and by offsets[NREAL]: a source that names the wrong
-// layout or the wrong texts gives wrong numbers, no load outside the workspace and the texts, and no unbounded walk.
+// Every workgroup takes the call's validity from the header (fqs_valid) and leaves at once when the call does not add.
+// Blocks at or beyond SK_FQ_H_NREAL load nothing.  A source that names the wrong layout or the wrong texts gives wrong
+// numbers, no load outside the workspace and the texts, and no unbounded walk: the bounds and the name line's clamps are
+// the source view's (sk_fastq_source.h).
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
 #include "sk_fastq_audit.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_report.h"
+#include "sk_fastq_source.h"
 
 namespace {
 
@@ -41,35 +42,10 @@ static_assert(FQA_CHUNK_BYTES % FQA_STEP == 0, "a chunk is whole steps");
 static_assert(FQA_THREADS % FQA_TABLES == 0, "every table has the same number of lanes");
 
 struct fqa_args {
-    const uint64_t *hdr;
-    const uint64_t *order_words; // ordered kinds: where the SK_FQO_H_* words lie
-    const uint64_t *desc;        // 5 words per slot, input 0's slots[0] slots first
-    const uint64_t *offsets;
-    const uint8_t *pq;
+    fqs_view s;     // the call behind
     uint64_t *aud;  // sk_fastq_audit as FQA_WORDS words
     uint64_t *hist; // [256] or NULL
-    const uint8_t *text[2];
-    uint64_t bytes[2];
-    uint64_t slots0;     // input 0's slots: input 1's descriptors lie behind them
-    uint64_t slot_bound; // slots of the descriptor section
-    int32_t kind;
-    int32_t mode;     // the call's framing mode
-    uint64_t n_bound; // the most reads the packed batch can hold
-    uint64_t q_bound; // bytes of the packed qual section
 };
-
-__device__ __forceinline__ bool fqa_valid(const fqa_args &a)
-{
-    const uint64_t *h = a.hdr;
-    const bool piece = a.kind == SK_FQ_REPORT_PIECE || a.kind == SK_FQ_REPORT_ORDERED_PIECE;
-    const uint64_t range0 = piece ? h[SK_FQP_H_RANGE0] : ~0ull;
-    bool refused = false;
-    if (a.order_words) {
-        refused = a.order_words[SK_FQO_H_LONG] != ~0ull || a.order_words[SK_FQO_H_OVERFLOW] != 0;
-        if (a.kind == SK_FQ_REPORT_ORDERED_PIECE && a.order_words[SK_FQOP_X_INHERITED]) refused = true; // void
-    }
-    return (int64_t)h[SK_FQ_H_MODE] == (int64_t)a.mode && fqp_call_valid(h[SK_FQ_H_FMT], h[SK_FQ_H_RANGE], range0, refused);
-}
 
 // ------------------------------------------------------------------------------------------
 // 0 reset
@@ -84,26 +60,12 @@ __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_reset_kernel(fqa_args
 // ------------------------------------------------------------------------------------------
 // 1 the names pass
 // ------------------------------------------------------------------------------------------
-// the name line of read r: its text, bounded by the text's bytes.  false: no descriptor slot for it.
-__device__ __forceinline__ bool fqa_name_line(const fqa_args &a, uint64_t r, const uint8_t *&p, uint64_t &len)
-{
-    const int i = a.mode == SK_TRIM_PE_SPLIT ? (int)(r & 1) : 0;
-    const uint64_t k = a.mode == SK_TRIM_PE_SPLIT ? r >> 1 : r;
-    const uint64_t slot = (i ? a.slots0 : 0) + k;
-    if (slot >= a.slot_bound) return false;
-    const uint64_t *d = a.desc + 5 * slot;
-    const uint64_t s = min(d[0], a.bytes[i]), e = max(min(d[1], a.bytes[i]), s);
-    p = a.text[i] + s;
-    len = e - s;
-    return true;
-}
-
 __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_names_kernel(fqa_args a)
 {
     __shared__ uint64_t s_red[FQA_THREADS / 64][4];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (!fqa_valid(a)) return; // uniform
-    const uint64_t n_real = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    if (!fqs_valid(a.s)) return; // uniform
+    const uint64_t n_real = fqs_reads(a.s);
     if ((uint64_t)blockIdx.x * SK_FQ_BLOCK_READS >= n_real) return; // uniform: nothing at or beyond the count is loaded
     // the lanes of a turn take neighbouring pairs, so that their descriptors and their name lines are neighbours too
     const uint64_t first = (uint64_t)blockIdx.x * SK_FQ_BLOCK_READS + 2u * (uint64_t)t;
@@ -111,10 +73,10 @@ __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_names_kernel(fqa_args
 #pragma unroll 1
     for (int j = 0; j < FQA_PER_THREAD / 2; ++j) {
         const uint64_t r = first + (uint64_t)j * (2u * FQA_THREADS);
-        if (!fqp_pair_at(a.mode, r, n_real)) break;
+        if (!fqp_pair_at(a.s.mode, r, n_real)) break;
         const uint8_t *n1 = nullptr, *n2 = nullptr;
         uint64_t len1 = 0, len2 = 0;
-        if (!fqa_name_line(a, r, n1, len1) || !fqa_name_line(a, r + 1, n2, len2)) break;
+        if (!fqs_name_line(a.s, r, n1, len1) || !fqs_name_line(a.s, r + 1, n2, len2)) break;
         const uint32_t f = fqa_pair(n1, len1, n2, len2);
         ++pairs;
         if (f & FQA_MISMATCH) {
@@ -160,10 +122,10 @@ __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_qual_kernel(fqa_args 
     __shared__ uint32_t s_tab[HIST ? FQA_TABLES * FQA_TABLE_STRIDE : 1];
     __shared__ uint32_t s_lo[FQA_THREADS / 64], s_hi[FQA_THREADS / 64];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (!fqa_valid(a)) return; // uniform
-    const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    if (!fqs_valid(a.s)) return; // uniform
+    const uint64_t R = fqs_reads(a.s);
     if (R == 0) return;
-    const uint64_t total = min(a.offsets[R], a.q_bound); // never beyond the section
+    const uint64_t total = min(a.s.offsets[R], a.s.q_bound); // never beyond the section
     const uint64_t c0 = (uint64_t)blockIdx.x * FQA_CHUNK_BYTES;
     if (c0 >= total) return; // uniform
     const uint64_t c1 = min(c0 + FQA_CHUNK_BYTES, total);
@@ -175,7 +137,7 @@ __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_qual_kernel(fqa_args 
     // minimum and maximum of the even and of the odd bytes, as two 16-bit halves each
     fqa_h2 lo = {0xff, 0xff}, hi = {0, 0};
     for (uint64_t g = c0 + 16u * t; g < c1; g += FQA_STEP) { // a granule with a byte below c1 <= offsets[NREAL]
-        const fqa_u4 v = __builtin_nontemporal_load(reinterpret_cast<const fqa_u4 *>(a.pq + g));
+        const fqa_u4 v = __builtin_nontemporal_load(reinterpret_cast<const fqa_u4 *>(a.s.pq + g));
         uint32_t word[4] = {v.x, v.y, v.z, v.w};
         const uint32_t n = (uint32_t)min((uint64_t)16, c1 - g);
         if (n < 16) fqa_fill_tail(word, n); // the batch's last granule
@@ -238,7 +200,7 @@ __global__ void __launch_bounds__(FQA_THREADS) sk_fq_audit_qual_kernel(fqa_args 
 __global__ void __launch_bounds__(64) sk_fq_audit_fold_kernel(fqa_args a, int names)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const bool valid = fqa_valid(a);
+    const bool valid = fqs_valid(a.s);
     a.aud[valid ? FQA_W_CALLS : FQA_W_CALLS_FAILED] += 1;
     if (valid && names) fqa_fold(a.aud);
 }
@@ -252,43 +214,16 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_audi
                                                                                   uint64_t *qual_hist_dev, int flags,
                                                                                   hipStream_t stream)
 {
-    sk_fq_layout L;
-    sk_fq_layout_of(src->text_bytes, src->trunc_n, &L);
-    const uint8_t *base = static_cast<const uint8_t *>(src->workspace);
-    uint64_t shift = 0;
     fqa_args a = {};
-    a.hdr = reinterpret_cast<const uint64_t *>(base);
-    if (src->kind == SK_FQ_REPORT_ORDERED) {
-        shift = sk_fq_order_shift(src->batch_capacity);
-        a.order_words = a.hdr;
-    } else if (src->kind == SK_FQ_REPORT_ORDERED_PIECE) {
-        shift = sk_fq_order_piece_shift(src->batch_capacity);
-        a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
-    }
-    a.desc = reinterpret_cast<const uint64_t *>(base + shift + L.desc);
-    a.offsets = reinterpret_cast<const uint64_t *>(base + shift + L.offsets);
-    a.pq = base + shift + L.qual;
+    fqs_fill(src, in, mode, &a.s);
     a.aud = reinterpret_cast<uint64_t *>(audit_dev);
     a.hist = qual_hist_dev;
-    a.kind = (int32_t)src->kind;
-    a.mode = fqa_framing_mode(mode);
-    a.n_bound = 2 * ((src->text_bytes + 2) / 16) + 2; // N of sk_fq_layout_of: the offsets section holds this many reads
-    a.slot_bound = (L.offsets - L.desc) / 40;
-    a.q_bound = L.seq - L.qual;
-    const bool names = in && a.mode != SK_TRIM_SE;
-    if (names) {
-        const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
-        for (int i = 0; i < n_in; ++i) {
-            a.text[i] = in->text[i];
-            a.bytes[i] = in->bytes[i];
-        }
-        a.slots0 = sk_fq_slots(a.bytes[0]);
-    }
+    const bool names = in && a.s.mode != SK_TRIM_SE; // (an SE call's texts are in the view and nothing looks at them)
     const dim3 threads(FQA_THREADS);
     if (flags & SK_FQ_AUDIT_RESET) hipLaunchKernelGGL(sk_fq_audit_reset_kernel, dim3(1), threads, 0, stream, a);
     if (names) {
-        uint64_t n_pack = sk_fq_pack_reads(a.bytes[0], a.bytes[1], a.mode);
-        if (n_pack > a.n_bound) n_pack = a.n_bound;
+        uint64_t n_pack = sk_fq_pack_reads(a.s.bytes[0], a.s.bytes[1], a.s.mode);
+        if (n_pack > a.s.n_bound) n_pack = a.s.n_bound;
         const uint64_t n_blocks = (n_pack + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
         if (n_blocks) hipLaunchKernelGGL(sk_fq_audit_names_kernel, dim3((unsigned)n_blocks), threads, 0, stream, a);
     }

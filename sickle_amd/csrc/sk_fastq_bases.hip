@@ -21,11 +21,10 @@
 //            first byte finishes it, or carries it into the next step.  The workgroup that holds a read's first byte owns
 //            its figures: it walks the part of the read beyond its chunk once more, all lanes, adding to nothing but that
 //            pair of words; at most one read per chunk is read twice, and the read's length bounds the walk.
-// Every workgroup takes the call's validity from the header (fqb_valid) and leaves at once when the call does not add.
-// Workgroups at or beyond offsets[NREAL] load nothing else.  Every descriptor index is bounded by the slots of the section,
-// every seq byte by in->bytes[i] (fqb_load16), every position by the section and by offsets[NREAL]: a source that names
-// the wrong layout or the wrong texts gives wrong numbers, no load outside the workspace and the texts, and no unbounded
-// walk.
+// Every workgroup takes the call's validity from the header (fqs_valid) and leaves at once when the call does not add.
+// Workgroups at or beyond offsets[NREAL] load nothing else.  A source that names the wrong layout or the wrong texts gives
+// wrong numbers, no load outside the workspace and the texts, and no unbounded walk: the bounds and the seq line's clamps
+// are the source view's (sk_fastq_source.h), and fqb_load16 holds every seq byte to in->bytes[i].
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
@@ -33,6 +32,7 @@
 #include "sk_fastq_bases.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_report.h"
+#include "sk_fastq_source.h"
 
 namespace {
 
@@ -50,52 +50,15 @@ static_assert(FQB_W_GC_NONE_OUT - FQB_W_READS + 1 == FQB_SCALARS, "the scalar re
 static_assert(SK_FQ_BASES_GC_BINS <= FQB_THREADS && FQB_REGS <= FQB_THREADS, "one lane flushes one word");
 
 struct fqb_args {
-    const uint64_t *hdr;
-    const uint64_t *order_words; // ordered kinds: where the SK_FQO_H_* words lie
-    const uint64_t *desc;        // 5 words per slot, input 0's slots first
-    const uint64_t *offsets;
-    const sk_cut_dev *cuts;
+    fqs_view s;    // the call behind
     uint64_t *bas; // sk_fastq_bases as FQB_WORDS words
     uint64_t *pos_in, *pos_out, *gc_in, *gc_out;
-    const uint8_t *text[2];
-    uint64_t bytes[2];
-    uint64_t slots0;     // input 0's slots: input 1's descriptors lie behind them
-    uint64_t slot_bound; // slots of the descriptor section
     uint32_t pos_bins;
-    int32_t kind;
-    int32_t mode;     // the call's framing mode
-    uint64_t n_bound; // the most reads the packed batch can hold
-    uint64_t q_bound; // bytes of a packed section
 };
-
-__device__ __forceinline__ bool fqb_valid(const fqb_args &a)
-{
-    const uint64_t *h = a.hdr;
-    const bool piece = a.kind == SK_FQ_REPORT_PIECE || a.kind == SK_FQ_REPORT_ORDERED_PIECE;
-    const uint64_t range0 = piece ? h[SK_FQP_H_RANGE0] : ~0ull;
-    bool refused = false;
-    if (a.order_words) {
-        refused = a.order_words[SK_FQO_H_LONG] != ~0ull || a.order_words[SK_FQO_H_OVERFLOW] != 0;
-        if (a.kind == SK_FQ_REPORT_ORDERED_PIECE && a.order_words[SK_FQOP_X_INHERITED]) refused = true; // void
-    }
-    return (int64_t)h[SK_FQ_H_MODE] == (int64_t)a.mode && fqp_call_valid(h[SK_FQ_H_FMT], h[SK_FQ_H_RANGE], range0, refused);
-}
 
 __device__ __forceinline__ void fqb_add(uint64_t *p, uint64_t v)
 {
     if (v) atomicAdd(reinterpret_cast<fqb_ull *>(p), (fqb_ull)v);
-}
-
-__device__ __forceinline__ int fqb_input(const fqb_args &a, uint64_t r) { return a.mode == SK_TRIM_PE_SPLIT ? (int)(r & 1) : 0; }
-
-// where the seq line of read r starts in its text, never beyond the text; the text's length: no descriptor slot for it
-__device__ __forceinline__ uint64_t fqb_seq_start(const fqb_args &a, uint64_t r)
-{
-    const int i = fqb_input(a, r);
-    const uint64_t k = a.mode == SK_TRIM_PE_SPLIT ? r >> 1 : r;
-    const uint64_t slot = (i ? a.slots0 : 0) + k;
-    if (slot >= a.slot_bound) return a.bytes[i];
-    return min(min(a.desc[5 * slot + 1], a.bytes[i]) + 1, a.bytes[i]);
 }
 
 // a shared read's pair of words: the sums are added, the flag is OR-ed (fqb_read_add, on LDS)
@@ -138,10 +101,10 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
     __shared__ uint32_t s_reg[FQB_REGS];
     __shared__ uint64_t *s_dst[5]; // where the flush adds: held in scalar registers across the loop they would cost spills
     const int t = threadIdx.x, lane = t & 63;
-    const bool valid = fqb_valid(a); // uniform
+    const bool valid = fqs_valid(a.s); // uniform
     if (blockIdx.x == 0 && t == 0) atomicAdd(reinterpret_cast<fqb_ull *>(a.bas + (valid ? FQB_W_CALLS : FQB_W_CALLS_FAILED)), 1ull);
     if (!valid) return;
-    const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    const uint64_t R = fqs_reads(a.s);
     if (R == 0) return;
     // The pass below walks packed positions and meets a read at its bytes, so a read of no bases is met nowhere.  No text
     // that passes the checks holds one, but a clipped call (sk_trim_fastq_clipped_device_async) packs one for every read
@@ -151,7 +114,7 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
         const uint64_t r0 = R / gridDim.x * blockIdx.x + min((uint64_t)blockIdx.x, R % gridDim.x);
         const uint64_t r1 = r0 + R / gridDim.x + (blockIdx.x < R % gridDim.x ? 1 : 0);
         uint32_t empty = 0;
-        for (uint64_t k = r0 + t; k < r1; k += FQB_THREADS) empty += a.offsets[k] == a.offsets[k + 1]; // k + 1 <= R
+        for (uint64_t k = r0 + t; k < r1; k += FQB_THREADS) empty += a.s.offsets[k] == a.s.offsets[k + 1]; // k + 1 <= R
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) empty += __shfl_xor(empty, d);
         if (lane == 0 && empty) {
@@ -161,7 +124,7 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
     }
     // == SK_FQ_H_PACKED: the reads behind the count are empty.  (Never beyond the section, and the walks below never leave
     // offsets[0 .. R]: a source that names the wrong layout gives wrong numbers, not loads outside the workspace.)
-    const uint64_t total = min(a.offsets[R], a.q_bound);
+    const uint64_t total = min(a.s.offsets[R], a.s.q_bound);
     const uint64_t c0 = (uint64_t)blockIdx.x * FQB_CHUNK_BYTES;
     if (c0 >= total) return; // uniform
     const uint64_t c1 = min(c0 + FQB_CHUNK_BYTES, total);
@@ -178,7 +141,7 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
         s_dst[3] = a.gc_in;
         s_dst[4] = a.gc_out;
     }
-    auto off = [&](uint64_t k) { return a.offsets[k]; }; // k <= R
+    auto off = [&](uint64_t k) { return a.s.offsets[k]; }; // k <= R
     // the read holding the chunk's first position: a 64-ary search by wave 0 (the last k < R with off(k) <= c0)
     if (t < 64) {
         uint64_t lo = 0, hi = R;
@@ -214,8 +177,8 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
     for (uint64_t s0 = c0; s0 < c1; s0 += FQB_STEP, ++step) {
         if (t <= FQB_WIN) s_off[t] = cur + t <= R ? off(cur + t) : ~0ull;
         if (t < FQB_WIN && cur + t < R) {
-            s_cut[t] = a.cuts[cur + t];
-            s_seq[t] = fqb_seq_start(a, cur + t);
+            s_cut[t] = a.s.cuts[cur + t];
+            s_seq[t] = fqs_seq_start(a.s, cur + t);
         }
         if (t == 0) s_tail = ~0ull;
         __syncthreads();
@@ -250,8 +213,8 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
                 const uint64_t i = k - cur;
                 b = i < FQB_WIN ? s_off[i] : off(k);
                 e = i < FQB_WIN ? s_off[i + 1] : off(k + 1);
-                c = i < FQB_WIN ? s_cut[i] : a.cuts[k];
-                sq = i < FQB_WIN ? s_seq[i] : fqb_seq_start(a, k);
+                c = i < FQB_WIN ? s_cut[i] : a.s.cuts[k];
+                sq = i < FQB_WIN ? s_seq[i] : fqs_seq_start(a.s, k);
             };
             load();
             const uint64_t g1 = min(g + 16, s1);
@@ -264,10 +227,10 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
                 if (at >= e || at < b) break; // only where offsets are no offsets
                 const uint64_t z = min(e, g1), p0 = at - b;
                 const uint32_t n = (uint32_t)(z - at), all = fqb_range16(0, n);
-                const int i = fqb_input(a, k);
+                const int i = fqs_input(a.s, k);
                 const bool kept = fqp_kept(c.three);
                 uint64_t w[2];
-                fqb_load16(a.text[i], a.bytes[i], sq + p0, w);
+                fqb_load16(a.s.text[i], a.s.bytes[i], sq + p0, w);
                 fqb_seg sg;
                 fqb_segment(w, n, p0, c.five, c.three, &sg);
 #pragma unroll
@@ -364,14 +327,14 @@ __global__ void __launch_bounds__(FQB_THREADS) sk_fq_bases_kernel(fqb_args a)
     if (tail < R) {
         const uint64_t b = off(tail), e = min(off(tail + 1), total);
         if (b >= c0 && b < c1) { // uniform
-            const sk_cut_dev c = a.cuts[tail];
-            const uint64_t sq = fqb_seq_start(a, tail);
-            const int i = fqb_input(a, tail);
+            const sk_cut_dev c = a.s.cuts[tail];
+            const uint64_t sq = fqs_seq_start(a.s, tail);
+            const int i = fqs_input(a.s, tail);
             uint64_t wi = 0, wo = 0;
             for (uint64_t q = c1 + 16u * t; q < e; q += FQB_STEP) { // bounded by the read's length
                 const uint32_t n = (uint32_t)min((uint64_t)16, e - q);
                 uint64_t w[2];
-                fqb_load16(a.text[i], a.bytes[i], sq + (q - b), w);
+                fqb_load16(a.s.text[i], a.s.bytes[i], sq + (q - b), w);
                 fqb_seg sg;
                 fqb_segment(w, n, q - b, c.five, c.three, &sg);
                 wi = fqb_read_add(wi, fqb_read_part(&sg, fqb_range16(0, n)));
@@ -446,34 +409,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_base
                                                                                   const sk_fastq_bases_hists *hists, int flags,
                                                                                   hipStream_t stream)
 {
-    sk_fq_layout L;
-    sk_fq_layout_of(src->text_bytes, src->trunc_n, &L);
-    const uint8_t *base = static_cast<const uint8_t *>(src->workspace);
-    uint64_t shift = 0;
     fqb_args a = {};
-    a.hdr = reinterpret_cast<const uint64_t *>(base);
-    if (src->kind == SK_FQ_REPORT_ORDERED) {
-        shift = sk_fq_order_shift(src->batch_capacity);
-        a.order_words = a.hdr;
-    } else if (src->kind == SK_FQ_REPORT_ORDERED_PIECE) {
-        shift = sk_fq_order_piece_shift(src->batch_capacity);
-        a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
-    }
-    a.desc = reinterpret_cast<const uint64_t *>(base + shift + L.desc);
-    a.offsets = reinterpret_cast<const uint64_t *>(base + shift + L.offsets);
-    a.cuts = reinterpret_cast<const sk_cut_dev *>(base + shift + L.cuts);
+    fqs_fill(src, in, mode, &a.s);
     a.bas = reinterpret_cast<uint64_t *>(bases_dev);
-    a.kind = (int32_t)src->kind;
-    a.mode = fqa_framing_mode(mode);
-    a.n_bound = 2 * ((src->text_bytes + 2) / 16) + 2; // N of sk_fq_layout_of: the offsets and cuts sections hold this many reads
-    a.slot_bound = (L.offsets - L.desc) / 40;
-    a.q_bound = L.seq - L.qual;
-    const int n_in = a.mode == SK_TRIM_PE_SPLIT ? 2 : 1;
-    for (int i = 0; i < n_in; ++i) {
-        a.text[i] = static_cast<const uint8_t *>(in->text[i]);
-        a.bytes[i] = in->text[i] ? in->bytes[i] : 0;
-    }
-    a.slots0 = sk_fq_slots(a.bytes[0]);
     if (hists) {
         a.pos_in = hists->pos_in;
         a.pos_out = hists->pos_out;

@@ -5,8 +5,8 @@
 // three >= 0; in the pair framings reads 2k and 2k + 1 are pair k.  Selected: every read that is not kept; with
 // SK_FQ_REJECTS_PAIRS both mates of every pair with a mate that is not kept.  A record is the input's own four lines,
 // bytes [s0, e3) of the record's text, and one '\n' that is never loaded: e3 - s0 + 1 bytes.  s0 and e3 come from the text
-// call's descriptors; fqj_span holds them to the text, so that whatever the descriptors say no byte at or beyond
-// text + bytes is asked for.
+// call's descriptors; the source view's fqs_record (sk_fastq_source.h) holds them to the text, so that whatever the
+// descriptors say no byte at or beyond text + bytes is asked for.
 // sk_fastq_rejects.hip calls these from its four kernels; tests/fastq_rejects/rejects_host.cpp walks them on the host in
 // the kernels' shape.
 #ifndef SK_FASTQ_REJECTS_H
@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "sickle_amd.h"
+#include "sk_fastq_source.h"
 
 #ifdef __HIPCC__
 #define FQJ_FN __host__ __device__ static inline
@@ -58,16 +59,8 @@ FQJ_FN bool fqj_kept(int32_t three) { return three >= 0; } // == fqr_kept, fqp_k
 FQJ_FN bool fqj_selected(bool kept, bool mate_kept, bool pairs) { return !kept || (pairs && !mate_kept); }
 
 // ---- the record -----------------------------------------------------------------------------------
-// [at, at + len) of a text of `bytes` bytes for a descriptor's s0 and e3: the record's own span in a call that is valid,
-// and a span inside the text whatever the two words hold
-FQJ_FN void fqj_span(uint64_t s0, uint64_t e3, uint64_t bytes, uint64_t *at, uint64_t *len)
-{
-    const uint64_t a = s0 < bytes ? s0 : bytes;
-    uint64_t e = e3 < bytes ? e3 : bytes;
-    if (e < a) e = a;
-    *at = a;
-    *len = e - a;
-}
+// fqs_span under the name tests/fastq_rejects/rejects_host.cpp walks it by
+FQJ_FN void fqj_span(uint64_t s0, uint64_t e3, uint64_t bytes, uint64_t *at, uint64_t *len) { fqs_span(s0, e3, bytes, at, len); }
 
 // bytes of the record: the span and its '\n'
 FQJ_FN uint64_t fqj_record_bytes(uint64_t span_len) { return span_len + 1; }
@@ -85,16 +78,7 @@ FQJ_FN void fqj_pieces(uint64_t at, uint64_t span_len, fqj_piece (&pc)[2])
     pc[1] = {FQJ_IMM, 1, (uint64_t)'\n'};
 }
 
-// ---- validity --------------------------------------------------------------------------------------
-// The audit's: no format verdict, no range verdict (range0: a piece's inherited one, ~0 for the other kinds), not refused
-// (SK_ELONGLINE, a full batch table, a void ordered piece), and the framing mode the text call recorded.
-FQJ_FN int fqj_framing_mode(int mode) { return mode == SK_TRIM_PE_COMBO_ALL ? SK_TRIM_PE_INTERLEAVED : mode; }
-
-FQJ_FN bool fqj_call_valid(uint64_t fmt, uint64_t range, uint64_t range0, bool refused, uint64_t recorded_mode, int mode)
-{
-    return fmt == ~0ull && range == ~0ull && range0 == ~0ull && !refused && (int64_t)recorded_mode == (int64_t)fqj_framing_mode(mode);
-}
-
+// ---- validity: the source view's fqs_valid (sk_fastq_source.h) --------------------------------------
 // the verdict of the scan kernel: what is written where
 FQJ_FN bool fqj_fits(bool valid, bool produced, uint64_t bytes, uint64_t capacity, bool index, uint64_t records, uint64_t record_capacity)
 {

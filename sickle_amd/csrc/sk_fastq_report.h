@@ -8,7 +8,7 @@
 // than SK_TRIM_SE) reads 2k and 2k + 1 are pair k; SK_TRIM_PE_COMBO_ALL frames as SK_TRIM_PE_INTERLEAVED, so its N records
 // are the reads that are not kept: 2 * pairs[0] + pairs[1] + pairs[2].  An interleaved text's odd last record
 // (dropped_unpaired) is checked and dropped by the framing: it is not in the packed batch and is in no count here.
-// Calls.  A call adds iff it has no format verdict and no range verdict (fqp_call_valid); one that does not add
+// Calls.  A call adds iff it has no format verdict and no range verdict (fqs_valid, sk_fastq_source.h); one that does not add
 // increments calls_failed and touches nothing else.  SK_ESPACE does not matter: the cuts are there either way.
 // sk_fastq_report.hip calls these from its two kernels; tests/fastq_report/report_host.cpp runs them on the host.
 #ifndef SK_FASTQ_REPORT_H
@@ -114,12 +114,6 @@ FQP_FN uint32_t fqp_slots(uint32_t bins) { return (bins + 31u) & ~31u; }
 // one position bin's LDS word: the count in the high half, the sum of raw bytes in the low half
 FQP_FN uint64_t fqp_qword(uint32_t q) { return (1ull << 32) | (q & 0xffu); }
 
-// Validity of the call behind a workspace, from its header words.  fmt: SK_FQ_H_FMT; range: SK_FQ_H_RANGE; range0: the
-// piece kinds' SK_FQP_H_RANGE0 (~0 for the others); refused: the ordered kinds' long-line word differs from ~0, or the
-// ordered call's table overflowed (0 for the others): such a call wrote nothing, as after a format verdict.
-FQP_FN bool fqp_call_valid(uint64_t fmt, uint64_t range, uint64_t range0, bool refused)
-{
-    return fmt == ~0ull && range == ~0ull && range0 == ~0ull && !refused;
-}
+// Validity of the call behind a workspace: fqs_valid of sk_fastq_source.h.
 
 #endif

@@ -14,14 +14,16 @@
 //            (1 << 32 | byte) to the 64-bit LDS word of the byte's position bin: the count in the high half, the sum in the
 //            low half, which cannot overflow (sk_fastq_report.h).  The last bin, which takes every position from
 //            pos_bins - 1 on, is summed in registers and added once per lane.  Non-zero halves go out as global atomics.
-// Every workgroup takes the call's validity from the header (fqp_call_valid) and leaves at once when the call does not
-// add.  Blocks at or beyond SK_FQ_H_NREAL load nothing; no offset or cut at or beyond the count is read but offsets[NREAL],
-// and no granule of the packed qual without a byte below offsets[NREAL].
+// Every workgroup takes the call's validity from the header (fqs_valid) and leaves at once when the call does not add.
+// Blocks at or beyond SK_FQ_H_NREAL load nothing; no offset or cut at or beyond the count is read but offsets[NREAL],
+// and no granule of the packed qual without a byte below offsets[NREAL].  A source that names the wrong layout gives wrong
+// numbers, no load outside the workspace: the bounds are the source view's (sk_fastq_source.h).
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
 #include "sk_fastq_order.h"
 #include "sk_fastq_report.h"
+#include "sk_fastq_source.h"
 
 namespace {
 
@@ -39,32 +41,12 @@ static_assert(2 * 4 * SK_FQ_REPORT_MAX_LEN_BINS + 2 * 8 * SK_FQ_REPORT_MAX_POS_B
 static_assert(SK_FQ_REPORT_MAX_POS_BINS % 32 == 0, "the largest table is whole groups of fqp_slot");
 
 struct fqp_args {
-    const uint64_t *hdr;
-    const uint64_t *order_words; // ordered kinds: where the SK_FQO_H_* words lie (the header, or a piece's extension block)
-    const uint64_t *offsets;
-    const sk_cut_dev *cuts;
-    const uint8_t *pq;
+    fqs_view s;    // the call behind; no mode: the report does not compare it
     uint64_t *rep; // sk_fastq_report as FQP_WORDS words
     uint64_t *len_in, *len_out;
     uint64_t *qsum_in, *qcnt_in, *qsum_out, *qcnt_out;
     uint32_t len_bins, pos_bins;
-    int32_t kind;
-    uint64_t n_bound; // the most reads the packed batch can hold
-    uint64_t q_bound; // bytes of the packed qual section
 };
-
-__device__ __forceinline__ bool fqp_valid(const fqp_args &a)
-{
-    const uint64_t *h = a.hdr;
-    const bool piece = a.kind == SK_FQ_REPORT_PIECE || a.kind == SK_FQ_REPORT_ORDERED_PIECE;
-    const uint64_t range0 = piece ? h[SK_FQP_H_RANGE0] : ~0ull;
-    bool refused = false;
-    if (a.order_words) {
-        refused = a.order_words[SK_FQO_H_LONG] != ~0ull || a.order_words[SK_FQO_H_OVERFLOW] != 0;
-        if (a.kind == SK_FQ_REPORT_ORDERED_PIECE && a.order_words[SK_FQOP_X_INHERITED]) refused = true; // void
-    }
-    return fqp_call_valid(h[SK_FQ_H_FMT], h[SK_FQ_H_RANGE], range0, refused);
-}
 
 __device__ __forceinline__ void fqp_add(uint64_t *p, uint64_t v)
 {
@@ -98,12 +80,12 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_reads_kernel(fqp_arg
     extern __shared__ uint32_t s_len[]; // len_in[len_bins], len_out[len_bins] (only with a length array)
     __shared__ uint64_t s_red[FQP_THREADS / 64][FQP_WORDS];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const bool valid = fqp_valid(a); // uniform
+    const bool valid = fqs_valid(a.s); // uniform
     if (blockIdx.x == 0 && t == 0) atomicAdd(reinterpret_cast<fqp_ull *>(a.rep + (valid ? FQP_W_CALLS : FQP_W_CALLS_FAILED)), 1ull);
     if (!valid) return;
-    const uint64_t n_real = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    const uint64_t n_real = fqs_reads(a.s);
     if ((uint64_t)blockIdx.x * SK_FQ_BLOCK_READS >= n_real) return; // uniform: nothing at or beyond the count is loaded
-    const int64_t mode = (int64_t)a.hdr[SK_FQ_H_MODE];
+    const int64_t mode = (int64_t)a.s.hdr[SK_FQ_H_MODE];
     const bool hist = a.len_in || a.len_out;
     if (hist) {
         for (uint32_t i = t; i < 2 * a.len_bins; i += FQP_THREADS) s_len[i] = 0;
@@ -115,14 +97,14 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_reads_kernel(fqp_arg
     for (int k = 0; k < FQP_WORDS; ++k) w[k] = 0;
     uint64_t max_in = 0, max_out = 0;
     if (first < n_real) {
-        uint64_t b = a.offsets[first];
+        uint64_t b = a.s.offsets[first];
         int32_t three_even = -1;
 #pragma unroll
         for (int j = 0; j < FQP_PER_THREAD; ++j) {
             const uint64_t r = first + j;
             if (r < n_real) {
-                const uint64_t e = a.offsets[r + 1], len = e - b;
-                const sk_cut_dev c = a.cuts[r];
+                const uint64_t e = a.s.offsets[r + 1], len = e - b;
+                const sk_cut_dev c = a.s.cuts[r];
                 fqp_add_read(len, c.five, c.three, w, &max_in, &max_out);
                 if (hist) {
                     atomicAdd(&s_len[fqp_bin(len, a.len_bins)], 1u);
@@ -174,19 +156,19 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_qual_kernel(fqp_args
     __shared__ sk_cut_dev s_cut[FQP_WIN];
     __shared__ uint64_t s_cur;
     const int t = threadIdx.x, lane = t & 63;
-    if (!fqp_valid(a)) return; // uniform
-    const uint64_t R = min(a.hdr[SK_FQ_H_NREAL], a.n_bound);
+    if (!fqs_valid(a.s)) return; // uniform
+    const uint64_t R = fqs_reads(a.s);
     if (R == 0) return;
     // == SK_FQ_H_PACKED: the reads behind the count are empty.  (Never beyond the section, and the walks below never leave
     // offsets[0 .. R]: a source that names the wrong layout gives wrong numbers, not loads outside the workspace.)
-    const uint64_t total = min(a.offsets[R], a.q_bound);
+    const uint64_t total = min(a.s.offsets[R], a.s.q_bound);
     const uint64_t c0 = (uint64_t)blockIdx.x * FQP_CHUNK_BYTES;
     if (c0 >= total) return; // uniform
     const uint64_t c1 = min(c0 + FQP_CHUNK_BYTES, total);
     const uint32_t PB = a.pos_bins, last = PB - 1, PS = fqp_slots(PB);
     uint64_t *s_in = s_pos, *s_out = s_pos + PS;
     for (uint32_t i = t; i < 2 * PS; i += FQP_THREADS) s_pos[i] = 0;
-    auto off = [&](uint64_t k) { return a.offsets[k]; }; // k <= R
+    auto off = [&](uint64_t k) { return a.s.offsets[k]; }; // k <= R
     // the read holding the chunk's first byte: a 64-ary search by wave 0 (the last k < R with off(k) <= c0)
     if (t < 64) {
         uint64_t lo = 0, hi = R;
@@ -203,7 +185,7 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_qual_kernel(fqp_args
     uint64_t tail_in = 0, tail_out = 0; // the last bin, count << 32 | sum, over the lane's granules of the whole chunk
     for (uint64_t s0 = c0; s0 < c1; s0 += FQP_STEP) {
         if (t <= FQP_WIN) s_off[t] = cur + t <= R ? off(cur + t) : ~0ull;
-        if (t < FQP_WIN && cur + t < R) s_cut[t] = a.cuts[cur + t];
+        if (t < FQP_WIN && cur + t < R) s_cut[t] = a.s.cuts[cur + t];
         __syncthreads();
         const uint64_t g = s0 + 16u * t;
         uint64_t k = cur;
@@ -225,7 +207,7 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_qual_kernel(fqp_args
             } else {
                 k = R - 1;
             }
-            const fqp_u4 v = __builtin_nontemporal_load(reinterpret_cast<const fqp_u4 *>(a.pq + g));
+            const fqp_u4 v = __builtin_nontemporal_load(reinterpret_cast<const fqp_u4 *>(a.s.pq + g));
             const uint32_t word[4] = {v.x, v.y, v.z, v.w};
             const int n = (int)min((uint64_t)16, c1 - g);
             // read k's bounds and cut; the reads that end at or before g (empty ones) are stepped over
@@ -235,7 +217,7 @@ __global__ void __launch_bounds__(FQP_THREADS) sk_fq_report_qual_kernel(fqp_args
                 const uint64_t i = k - cur;
                 b = i < FQP_WIN ? s_off[i] : off(k);
                 e = i < FQP_WIN ? s_off[i + 1] : off(k + 1);
-                c = i < FQP_WIN ? s_cut[i] : a.cuts[k];
+                c = i < FQP_WIN ? s_cut[i] : a.s.cuts[k];
             };
             load();
 #pragma unroll
@@ -283,26 +265,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_repo
                                                                                    const sk_fastq_report_hists *hists, int flags,
                                                                                    hipStream_t stream)
 {
-    sk_fq_layout L;
-    sk_fq_layout_of(src->text_bytes, src->trunc_n, &L);
-    const uint8_t *base = static_cast<const uint8_t *>(src->workspace);
-    uint64_t shift = 0;
     fqp_args a = {};
-    a.hdr = reinterpret_cast<const uint64_t *>(base);
-    if (src->kind == SK_FQ_REPORT_ORDERED) {
-        shift = sk_fq_order_shift(src->batch_capacity);
-        a.order_words = a.hdr;
-    } else if (src->kind == SK_FQ_REPORT_ORDERED_PIECE) {
-        shift = sk_fq_order_piece_shift(src->batch_capacity);
-        a.order_words = reinterpret_cast<const uint64_t *>(base + SK_FQOP_EXT_BYTES_AT);
-    }
-    a.offsets = reinterpret_cast<const uint64_t *>(base + shift + L.offsets);
-    a.cuts = reinterpret_cast<const sk_cut_dev *>(base + shift + L.cuts);
-    a.pq = base + shift + L.qual;
+    fqs_fill(src, nullptr, FQS_NO_MODE, &a.s);
     a.rep = reinterpret_cast<uint64_t *>(report_dev);
-    a.kind = (int32_t)src->kind;
-    a.n_bound = 2 * ((src->text_bytes + 2) / 16) + 2; // N of sk_fq_layout_of: the offsets and cuts sections hold this many reads
-    a.q_bound = L.seq - L.qual;
     if (hists) {
         const bool has_len = hists->len_in || hists->len_out;
         const bool has_pos = hists->qsum_in || hists->qcnt_in || hists->qsum_out || hists->qcnt_out;
@@ -322,7 +287,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t sk_launch_fastq_repo
         if (a.pos_bins > words) words = a.pos_bins;
         hipLaunchKernelGGL(sk_fq_report_reset_kernel, dim3((words + FQP_THREADS - 1) / FQP_THREADS), threads, 0, stream, a);
     }
-    const uint64_t n_blocks = (a.n_bound + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
+    const uint64_t n_blocks = (a.s.n_bound + SK_FQ_BLOCK_READS - 1) / SK_FQ_BLOCK_READS;
     hipLaunchKernelGGL(sk_fq_report_reads_kernel, dim3((unsigned)n_blocks), threads, 2 * 4 * a.len_bins, stream, a);
     if (a.pos_bins) {
         // the packed qual is at most half the text

@@ -13,8 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sk_device.h"
-
-typedef unsigned sk_u4 __attribute__((ext_vector_type(4)));
+#include "sk_device_prims.h"
 
 #define SK_TRIM_THREADS 256
 #define SK_TRIM_PER_THREAD (SK_TRIM_BLOCK_READS / SK_TRIM_THREADS) // consecutive reads of one lane (even: pairs stay whole)
@@ -94,41 +93,6 @@ __device__ __forceinline__ void trim_load(const sk_trim_args &a, uint64_t first,
 // bytes of a kept record (0 for an invalid cut: the counts are then not used)
 __device__ __forceinline__ uint64_t trim_bytes(const trim_read &r) { return r.bad ? 0 : (uint64_t)(r.three - r.five); }
 
-// exclusive prefix sums of N values over the workgroup; total[] = the sums over it.  lds: 4 * N words.
-template <int N>
-__device__ __forceinline__ void block_scan(uint64_t (&v)[N], uint64_t (&total)[N], uint64_t *lds)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t inc[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) inc[i] = v[i];
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const uint64_t t = __shfl_up(inc[i], d);
-            if (lane >= d) inc[i] += t;
-        }
-    }
-    if (lane == 63)
-#pragma unroll
-        for (int i = 0; i < N; ++i) lds[w * N + i] = inc[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        uint64_t base = 0, tot = 0;
-#pragma unroll
-        for (int ww = 0; ww < SK_TRIM_THREADS / 64; ++ww) {
-            const uint64_t x = lds[ww * N + i];
-            base += ww < w ? x : 0;
-            tot += x;
-        }
-        v[i] = base + inc[i] - v[i];
-        total[i] = tot;
-    }
-    __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------
 // 1 count
 // ------------------------------------------------------------------------------------------
@@ -136,7 +100,7 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_count_kernel(sk_trim_
 {
     __shared__ uint64_t lds[4 * 6];
     __shared__ unsigned long long bad_min;
-    if (threadIdx.x == 0) bad_min = ~0ull; // ordered before the atomics by block_scan's barriers
+    if (threadIdx.x == 0) bad_min = ~0ull; // ordered before the atomics by sk_block_scan's barriers
     const uint64_t first = (uint64_t)blockIdx.x * SK_TRIM_BLOCK_READS + threadIdx.x * SK_TRIM_PER_THREAD;
     trim_read rd[SK_TRIM_PER_THREAD];
     trim_load(a, first, rd);
@@ -152,7 +116,7 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_count_kernel(sk_trim_
                 v[3 + o] += trim_bytes(rd[i]);
             }
     }
-    block_scan<6>(v, tot, lds);
+    sk_block_scan<6, SK_TRIM_THREADS>(v, tot, lds);
     if (bad != ~0ull) atomicMin(&bad_min, (unsigned long long)bad);
     __syncthreads();
     if (threadIdx.x < 7) {
@@ -181,7 +145,7 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_scan_kernel(sk_trim_a
 #pragma unroll
         for (int i = 0; i < 6; ++i) v[i] = b < a.n_blocks ? blk[b * SK_TRIM_BLOCK_WORDS + i] : 0;
         if (b < a.n_blocks) bad = min(bad, blk[b * SK_TRIM_BLOCK_WORDS + 6]);
-        block_scan<6>(v, tot, lds);
+        sk_block_scan<6, SK_TRIM_THREADS>(v, tot, lds);
         if (b < a.n_blocks)
 #pragma unroll
             for (int i = 0; i < 6; ++i) blk[b * SK_TRIM_BLOCK_WORDS + i] = run[i] + v[i];
@@ -228,7 +192,7 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_place_kernel(sk_trim_
                 v[o] += 1;
                 v[3 + o] += trim_bytes(rd[i]);
             }
-    block_scan<6>(v, tot, lds);
+    sk_block_scan<6, SK_TRIM_THREADS>(v, tot, lds);
     const uint64_t *blk = a.ws + SK_TRIM_HDR_WORDS + blockIdx.x * SK_TRIM_BLOCK_WORDS;
 #pragma unroll
     for (int i = 0; i < 6; ++i) v[i] += blk[i];
@@ -252,53 +216,10 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_place_kernel(sk_trim_
 // ------------------------------------------------------------------------------------------
 // 4 gather
 // ------------------------------------------------------------------------------------------
-// the n (1..16) bytes at p as the first bytes of a granule, from aligned 16-byte loads only: both blocks touched hold a
-// byte of [p, p + n), so nothing beyond the caller's buffer is read, whatever p's alignment
-__device__ __forceinline__ sk_u4 load_window(const uint8_t *p, int n)
-{
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
-    const sk_u4 *blk = reinterpret_cast<const sk_u4 *>(ad & ~(uintptr_t)15);
-    const int sh = (int)(ad & 15);
-    const sk_u4 lo = blk[0];
-    if (sh == 0) return lo;
-    const sk_u4 hi = sh + n > 16 ? blk[1] : lo;
-    const int s4 = sh >> 2, sb = sh & 3;
-    // words s4 .. s4 + 4 of {lo, hi}, then the byte shift
-    const uint32_t x0 = lo.x, x1 = lo.y, x2 = lo.z, x3 = lo.w, x4 = hi.x, x5 = hi.y, x6 = hi.z, x7 = hi.w;
-    const uint32_t y0 = s4 == 0 ? x0 : s4 == 1 ? x1 : s4 == 2 ? x2 : x3;
-    const uint32_t y1 = s4 == 0 ? x1 : s4 == 1 ? x2 : s4 == 2 ? x3 : x4;
-    const uint32_t y2 = s4 == 0 ? x2 : s4 == 1 ? x3 : s4 == 2 ? x4 : x5;
-    const uint32_t y3 = s4 == 0 ? x3 : s4 == 1 ? x4 : s4 == 2 ? x5 : x6;
-    const uint32_t y4 = s4 == 0 ? x4 : s4 == 1 ? x5 : s4 == 2 ? x6 : x7;
-    sk_u4 r;
-    r.x = __builtin_amdgcn_alignbyte(y1, y0, sb);
-    r.y = __builtin_amdgcn_alignbyte(y2, y1, sb);
-    r.z = __builtin_amdgcn_alignbyte(y3, y2, sb);
-    r.w = __builtin_amdgcn_alignbyte(y4, y3, sb);
-    return r;
-}
-
-typedef unsigned __int128 sk_u128;
-
-__device__ __forceinline__ sk_u128 to_u128(sk_u4 v)
-{
-    return (sk_u128)v.x | ((sk_u128)v.y << 32) | ((sk_u128)v.z << 64) | ((sk_u128)v.w << 96);
-}
-
-__device__ __forceinline__ sk_u4 from_u128(sk_u128 v)
-{
-    sk_u4 r;
-    r.x = (uint32_t)v;
-    r.y = (uint32_t)(v >> 32);
-    r.z = (uint32_t)(v >> 64);
-    r.w = (uint32_t)(v >> 96);
-    return r;
-}
-
 // bytes [0, n) of v to bytes [d, d + n) of acc (d + n <= 16)
 __device__ __forceinline__ void place(sk_u128 &acc, sk_u4 v, int d, int n)
 {
-    const sk_u128 x = to_u128(v);
+    const sk_u128 x = sk_to_u128(v);
     const sk_u128 m = n >= 16 ? ~(sk_u128)0 : (((sk_u128)1 << (8 * n)) - 1);
     acc |= (x & m) << (8 * d);
 }
@@ -308,7 +229,7 @@ __device__ __forceinline__ void store_granule(uint8_t *dst, uint64_t g, sk_u4 v,
     if (n == 16) {
         __builtin_nontemporal_store(v, reinterpret_cast<sk_u4 *>(dst + g));
     } else {
-        const sk_u128 x = to_u128(v);
+        const sk_u128 x = sk_to_u128(v);
         for (int i = 0; i < n; ++i) dst[g + i] = (uint8_t)(x >> (8 * i));
     }
 }
@@ -392,18 +313,18 @@ __global__ void __launch_bounds__(SK_TRIM_THREADS) sk_trim_gather_kernel(sk_trim
                     const uint64_t pe = min(e, end), src = pos + (i < SK_TRIM_WIN ? s_delta[i] : delta[k]);
                     const int d = (int)(pos - g), n = (int)(pe - pos);
                     if (n == 16) { // the granule lies inside one record: the fast path
-                        if (qual) vq = load_window(qual + src, 16);
-                        if (seq) vs = load_window(seq + src, 16);
+                        if (qual) vq = sk_load_window(qual + src, 16);
+                        if (seq) vs = sk_load_window(seq + src, 16);
                         whole = true;
                     } else {
-                        if (qual) place(aq, load_window(qual + src, n), d, n);
-                        if (seq) place(as, load_window(seq + src, n), d, n);
+                        if (qual) place(aq, sk_load_window(qual + src, n), d, n);
+                        if (seq) place(as, sk_load_window(seq + src, n), d, n);
                     }
                     pos = pe;
                 }
                 if (!whole) {
-                    vq = from_u128(aq);
-                    vs = from_u128(as);
+                    vq = sk_from_u128(aq);
+                    vs = sk_from_u128(as);
                 }
                 const int n = (int)(end - g);
                 if (qual) store_granule(out.qual, g, vq, n);
