@@ -398,6 +398,16 @@ class FastqAdaptersOut(C.Structure):
                 ("clip_capacity", C.c_uint64)]
 
 
+def _decode_clip_words(words):
+    """clip words (an int32 tensor, a word per read) -> (clip, adapter): int64 tensors with the start per read and the
+    adapter's number, each -1 where the word is SK_FQ_CLIP_NONE"""
+    import torch
+    words = words.to(torch.int64) & 0xFFFFFFFF
+    none = words == SK_FQ_CLIP_NONE
+    return (torch.where(none, torch.full_like(words, -1), words & 0xFFFFFF),
+            torch.where(none, torch.full_like(words, -1), words >> 24))
+
+
 class _AdaptersBuffers:
     """The set and the device words of one adapters=dict(seqs=[..], min_overlap=3, max_mismatch_permille=100,
     pos_bins=None, overlap=False, clip=False) of a driver: the sk_fastq_adapters, then pos and overlap where asked for, in
@@ -448,11 +458,7 @@ class _AdaptersBuffers:
         if self.overlap:
             d["overlap"] = w[at:at + 8 * SK_FQ_ADAPTERS_OVERLAP_BINS].reshape(8, SK_FQ_ADAPTERS_OVERLAP_BINS).copy()
         if self.clip is not None:
-            import torch
-            words = self.clip[:d["reads"]].to(torch.int64) & 0xFFFFFFFF
-            none = words == SK_FQ_CLIP_NONE
-            d["clip"] = torch.where(none, torch.full_like(words, -1), words & 0xFFFFFF)
-            d["adapter"] = torch.where(none, torch.full_like(words, -1), words >> 24)
+            d["clip"], d["adapter"] = _decode_clip_words(self.clip[:d["reads"]])
         return d
 
 
@@ -526,6 +532,109 @@ def _rejects_flags(rejects):
     if isinstance(rejects, int) and not isinstance(rejects, bool):
         return rejects
     raise ValueError("rejects: False, True or \"pairs\", not %r" % (rejects,))
+
+
+class _SideCalls:
+    """What one call of a driver runs beside its text call, from the driver's own keywords: the buffer objects of report=,
+    audit=, bases=, adapters= and clip_adapters= (rep, aud, bas, adp, clp: None where the option is off, and nothing is
+    allocated for it) and the flags of rejects= (rej_flags: None where off).  Built in front of everything a driver
+    allocates or enqueues, so a bad option raises its ValueError with nothing in flight.  clip_ok: whether the driver hands
+    clip words out (trim_fastq alone does); mode: the driver's."""
+
+    def __init__(self, dev, clip_ok, mode, report=False, audit=False, bases=False, rejects=False, adapters=False,
+                 clip_adapters=None):
+        self.mode = mode
+        self.clp = _ClipBuffers(clip_adapters, dev, clip_ok=clip_ok) if clip_adapters is not None else None
+        self.rep = _ReportBuffers(report, dev) if report else None
+        self.aud = _AuditBuffers(dev) if audit else None
+        self.bas = _BasesBuffers(bases, dev) if bases else None
+        self.adp = _AdaptersBuffers(adapters, dev, clip_ok=clip_ok) if adapters else None
+        self.rej_flags = _rejects_flags(rejects) if rejects else None
+        if rejects and self.rej_flags & SK_FQ_REJECTS_PAIRS and mode == "se":
+            raise ValueError("rejects=\"pairs\" needs a pair mode")
+
+    def rewind(self):
+        """in front of a driver's second run (_with_batch_table): what the first run left in the objects goes, as if they
+        had been built anew; what accumulates on the device is zeroed by the run's own reset"""
+        if self.clp:
+            self.clp.reset, self.clp.words_ptr = True, None
+        if self.adp and self.adp.clip is not None:
+            self.adp.clip = None
+            self.adp._out()
+
+    def enqueue(self, ctx, ws_ptr, ptrs, bounds, trunc_n, kind, order, reset, stream, writing=True, rejects_ws=None,
+                rejects_out=None):
+        """What follows a driver's text call on its stream, over its workspace and its texts: behind a writing pass the
+        report, the audit and the bases, then the rejects, then the adapter search (writing=False: a counting pass, which
+        only the rejects follow).  rejects_ws: the rejects call's workspace tensor (None: no rejects call), rejects_out: its
+        FastqOutput or None (it only counts).  kind: "plain" or "piece"; order: the text call's FastqOrder or None; reset:
+        zero what accumulates (not the rejects, which do not).  The audit does without the names when a text is empty (no
+        pointer); the bases, the rejects and the adapters, which need `in`, give an empty text their own buffer's address
+        with the bound 0, of which no byte is loaded."""
+        kind, cap = _source_kind(kind, order)
+        total, mode = sum(bounds), self.mode
+        own = lambda ptr: ([ptr if p is None else p for p in ptrs], [0 if p is None else b for p, b in zip(ptrs, bounds)])
+        rep, aud, bas, adp = (self.rep, self.aud, self.bas, self.adp) if writing else (None,) * 4
+        if rep:
+            ctx.trim_fastq_report_device_async(ws_ptr, total, trunc_n, rep.ptr, kind=kind, batch_capacity=cap, hists=rep.hists,
+                                               reset=reset, stream=stream)
+        if aud:
+            ctx.trim_fastq_audit_device_async(ws_ptr, total, trunc_n, aud.ptr,
+                                              text_ptrs=None if any(p is None for p in ptrs) else ptrs, text_bounds=bounds,
+                                              mode=mode, kind=kind, batch_capacity=cap, qual_hist_ptr=aud.hist_ptr, reset=reset,
+                                              stream=stream)
+        if bas:
+            p, b = own(bas.ptr)
+            ctx.trim_fastq_bases_device_async(ws_ptr, total, trunc_n, bas.ptr, p, b, mode=mode, kind=kind, batch_capacity=cap,
+                                              hists=bas.hists, reset=reset, stream=stream)
+        if rejects_ws is not None:
+            p, b = own(rejects_ws.data_ptr())
+            ctx.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, p, b, rejects_out, rejects_ws.data_ptr(),
+                                                rejects_ws.numel(), mode=mode, kind=kind, batch_capacity=cap,
+                                                pairs=self.rej_flags, stream=stream)
+        if adp:
+            p, b = own(adp.ptr)
+            ctx.trim_fastq_adapters_device_async(ws_ptr, total, trunc_n, adp.ptr, p, b, adp.set, mode=mode, kind=kind,
+                                                 batch_capacity=cap, out=adp.out, reset=reset, stream=stream)
+
+    def collect(self, counts):
+        """once the stream has been waited for: the audit, the bases, the adapters and the clip stats into counts, each
+        under its option's name where the option is on; -> the report as a dict, or None"""
+        for key, b in (("audit", self.aud), ("bases", self.bas), ("adapters", self.adp), ("clip", self.clp)):
+            if b:
+                counts[key] = b.read()
+        return self.rep.read() if self.rep else None
+
+
+class _Writers:
+    """The BGZF writers behind a text call whose outputs are sized without a look at the text: per used output the
+    trimmed text's buffer of `cap` bytes (outs: the call's FastqOutput entries over them) and, with gz, its image and
+    its writer's workspace.  alloc(n): a uint8 device tensor of n bytes (16 at least)."""
+
+    def __init__(self, used, cap, search, alloc, gz=True):
+        self.cap, self.search = cap, search
+        new = lambda n: [alloc(n) if o in used else None for o in range(3)]
+        self.text = new(cap)
+        if gz:
+            self.bound = lib().sk_bgzf_bound(cap, SK_BGZF_EOF)
+            self.ws_bytes = lib().sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
+            self.images, self.ws = new(self.bound), new(self.ws_bytes)
+        self.outs = [FastqOutput() if t is None else FastqOutput(t.data_ptr(), cap, None, 0) for t in self.text]
+
+    def enqueue(self, ctx, workspace_ptr, stream, eof=True, words=None):
+        """a writer per used output, in output order, fed by the device words of the trim whose workspace this is (words:
+        trim_fastq_rejects_output_words where it is a rejects call's, whose one text is output 0)"""
+        for o, t in enumerate(self.text):
+            if t is not None:
+                nbytes, written = words(workspace_ptr) if words else ctx.trim_fastq_output_words(workspace_ptr, o)
+                ctx.bgzf_device_async(t.data_ptr(), self.cap, self.images[o].data_ptr(), self.bound, self.ws[o].data_ptr(),
+                                      self.ws_bytes, eof=eof, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream,
+                                      search=self.search)
+
+    def finish(self, ctx, stream):
+        """the writers' finishes -> the three images narrowed to their bytes (None where the output is not used)"""
+        return tuple(None if im is None else im[:ctx.bgzf_device_finish(w.data_ptr(), stream)["bytes_out"]]
+                     for im, w in zip(self.images, self.ws))
 
 
 class FastqPiece(C.Structure):
@@ -914,6 +1023,17 @@ def _source_kind(kind, order):
     if order is None:
         return kind, 0
     return {"plain": "ordered", "piece": "ordered_piece"}[kind], order.batch_capacity
+
+
+def _text_ptrs(texts):
+    """texts (uint8 tensors) -> (ptrs, sizes) as the text calls take them: an empty text has no pointer"""
+    return [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
+
+
+def _alloc_on(dev):
+    """-> alloc(n): an uninitialised uint8 tensor of n bytes, 16 at least, on dev"""
+    import torch
+    return lambda n: torch.empty(max(n, 16), dtype=torch.uint8, device=dev)
 
 
 def _fastq_ws_bytes(sizes, trunc_n, order, clip=None):
@@ -1418,9 +1538,9 @@ class Context:
         clip_adapters=dict(seqs=[..], ..) as trim_fastq's, without clip: every piece is the clipped call of its kind
         (sk_trim_fastq_clipped_device_async), and the stats of the whole file are read back once into .clip (None until then,
         and after a failure).  None: the pieces are the calls they were, and nothing is allocated."""
+        side = _SideCalls("cuda", False, mode, report, audit, bases, rejects, adapters, clip_adapters)
         srcs = [_TextSource(chunks)] + ([] if chunks2 is None else [_TextSource(chunks2)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects, adapters, clip_adapters)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, side)
 
     def trim_gz_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, room=None, gz=True, search=False,
                        max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False, rejects=False,
@@ -1432,9 +1552,9 @@ class Context:
         offsets count within the group) and what trim_fastq_stream raises.  Plain gzip cannot be cut at members: ValueError
         (use trim_gz).  order, batch_capacity, report, audit, bases, rejects, adapters, clip_adapters: as in
         trim_fastq_stream."""
+        side = _SideCalls("cuda", False, mode, report, audit, bases, rejects, adapters, clip_adapters)
         srcs = [_BgzfSource(image, piece_bytes)] + ([] if image2 is None else [_BgzfSource(image2, piece_bytes)])
-        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                           audit, bases, rejects, adapters, clip_adapters)
+        return FastqStream(self, params, srcs, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, side)
 
     def trim_gzip_stream(self, params, image, image2=None, mode="se", piece_bytes=64 << 20, window_bytes=None, room=None, gz=True,
                          search=False, max_read_len=0, order=None, batch_capacity=None, report=False, audit=False, bases=False,
@@ -1450,10 +1570,10 @@ class Context:
         piece, so piece_bytes of twice the largest stretch's text is enough); neither is retried.  The host learns of
         the stream's end from a finished reader piece, so the last FASTQ piece is an empty closing one.  order,
         batch_capacity, report, audit, bases, rejects, adapters, clip_adapters: as in trim_fastq_stream."""
+        side = _SideCalls("cuda", False, mode, report, audit, bases, rejects, adapters, clip_adapters)
         window = max(piece_bytes // 3, 1) if window_bytes is None else window_bytes
         sources = [_GzipPieceSource(im, window, piece_bytes) for im in ([image] if image2 is None else [image, image2])]
-        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, report,
-                         audit, bases, rejects, adapters, clip_adapters)
+        st = FastqStream(self, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, side)
         st.device_bytes += sum(s.device_bytes for s in sources)
         return st
 
@@ -1472,8 +1592,9 @@ class Context:
         threads, batch_len = order
         return [FastqOrder(threads, 0, batch_len, cap, 0) for cap in (sum(sizes) // batch_len + 16, max(sizes) // 4 + 2)]
 
-    def _with_batch_table(self, order, sizes, call):
-        """call(FastqOrder or None); once more with the larger table if the first one was too small"""
+    def _with_batch_table(self, order, sizes, call, side):
+        """call(FastqOrder or None); once more with the larger table if the first one was too small, behind side.rewind():
+        side is the _SideCalls the call uses in both runs"""
         if order is None:
             return call(None)
         first, second = self._order_tables(order, sizes)
@@ -1484,6 +1605,7 @@ class Context:
             if e.rc != SK_ESPACE or "order" not in e.counts or e.counts["order"]["batches"] != first.batch_capacity + 1 or \
                     second.batch_capacity <= first.batch_capacity:
                 raise
+        side.rewind()
         return call(second)
 
     def trim_fastq(self, params, text, text2=None, mode="se", max_read_len=0, record_index=False, order=None, report=False,
@@ -1528,79 +1650,41 @@ class Context:
         trim, and everything above describes the clipped reads.  counts["clip"] holds sk_fastq_clip_stats's members of the
         writing pass as ints (hits: eight); with clip=True also clip and adapter, int64 tensors as adapters=dict(clip=True)'s.
         None: nothing is launched, nothing extra is allocated, and the calls are the ones they were."""
-        if order is not None:
-            sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
-            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq(params, text, text2, mode, max_read_len,
-                                                                                  record_index, o, report, audit, bases,
-                                                                                  rejects, adapters, clip_adapters))
-        return self._trim_fastq(params, text, text2, mode, max_read_len, record_index, None, report, audit, bases, rejects,
-                                adapters, clip_adapters)
-
-    def _enqueue_behind(self, ws_ptr, ptrs, bounds, trunc_n, mode, kind, order, reset, stream, rep=None, aud=None, bas=None,
-                        rej=None, adp=None):
-        """What follows a driver's text call on its stream, over its workspace and its texts: the report, the audit, the
-        bases, then the rejects, then the adapter search, each where its buffers are given (rep, aud, bas, adp: the
-        drivers' buffer objects; rej: the rejects call's workspace tensor, its FastqOutput or None, its flags).  kind: "plain" or "piece"; order: the text
-        call's FastqOrder or None; reset: zero what accumulates (not the rejects, which do not).  The audit does without the
-        names when a text is empty (no pointer); the bases and the rejects, which need `in`, give an empty text their own
-        buffer's address with the bound 0, of which no byte is loaded."""
-        kind, cap = _source_kind(kind, order)
-        total = sum(bounds)
-        own = lambda ptr: ([ptr if p is None else p for p in ptrs], [0 if p is None else b for p, b in zip(ptrs, bounds)])
-        if rep:
-            self.trim_fastq_report_device_async(ws_ptr, total, trunc_n, rep.ptr, kind=kind, batch_capacity=cap, hists=rep.hists,
-                                                reset=reset, stream=stream)
-        if aud:
-            self.trim_fastq_audit_device_async(ws_ptr, total, trunc_n, aud.ptr,
-                                               text_ptrs=None if any(p is None for p in ptrs) else ptrs, text_bounds=bounds,
-                                               mode=mode, kind=kind, batch_capacity=cap, qual_hist_ptr=aud.hist_ptr, reset=reset,
-                                               stream=stream)
-        if bas:
-            p, b = own(bas.ptr)
-            self.trim_fastq_bases_device_async(ws_ptr, total, trunc_n, bas.ptr, p, b, mode=mode, kind=kind, batch_capacity=cap,
-                                               hists=bas.hists, reset=reset, stream=stream)
-        if rej:
-            rws, out, flags = rej
-            p, b = own(rws.data_ptr())
-            self.trim_fastq_rejects_device_async(ws_ptr, total, trunc_n, p, b, out, rws.data_ptr(), rws.numel(), mode=mode,
-                                                 kind=kind, batch_capacity=cap, pairs=flags, stream=stream)
-        if adp:
-            p, b = own(adp.ptr)
-            self.trim_fastq_adapters_device_async(ws_ptr, total, trunc_n, adp.ptr, p, b, adp.set, mode=mode, kind=kind,
-                                                  batch_capacity=cap, out=adp.out, reset=reset, stream=stream)
-
-    def _trim_fastq(self, params, text, text2, mode, max_read_len, record_index, order, report=False, audit=False, bases=False,
-                    rejects=False, adapters=False, clip_adapters=None):
-        import torch
-        dev = text.device
+        side = _SideCalls(text.device, True, mode, report, audit, bases, rejects, adapters, clip_adapters)
         texts = [text] if text2 is None else [text, text2]
-        ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
+        return self._with_batch_table(order, [t.numel() for t in texts],
+                                      lambda o: self._trim_fastq(params, texts, mode, max_read_len, record_index, o, side), side)
+
+    def _text_async(self, params, ptrs, sizes, order, outs, workspace_ptr, workspace_bytes, **kw):
+        """a driver's whole-text call: trim_fastq_device_async, or with order (a FastqOrder) the ordered one"""
+        if order is None:
+            return self.trim_fastq_device_async(params, ptrs, sizes, outs, workspace_ptr, workspace_bytes, **kw)
+        return self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, workspace_ptr, workspace_bytes, **kw)
+
+    def _text_finish(self, order, workspace_ptr, stream):
+        """the finish of _text_async's call, and of the chained call of that order"""
+        finish = self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish
+        return finish(workspace_ptr, stream)
+
+    def _trim_fastq(self, params, texts, mode, max_read_len, record_index, order, side):
+        import torch
+        dev = texts[0].device
+        ptrs, sizes = _text_ptrs(texts)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        clp = _ClipBuffers(clip_adapters, dev, clip_ok=True) if clip_adapters is not None else None
-        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, clp)
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, side.clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        rep = _ReportBuffers(report, dev) if report else None
-        aud = _AuditBuffers(dev) if audit else None
-        bas = _BasesBuffers(bases, dev) if bases else None
-        adp = _AdaptersBuffers(adapters, dev, clip_ok=True) if adapters else None
-        rej_out = [None]
+        rejects, rws, rej_out = side.rej_flags is not None, None, [None]
         if rejects:
-            rej_flags = _rejects_flags(rejects)
             rws = torch.empty(lib().sk_trim_fastq_rejects_workspace_bytes(sum(sizes)), dtype=torch.uint8, device=dev)
 
         def run(outs, final=False):
-            if order is None:
-                self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                             max_read_len=max_read_len, stream=stream, clip=clp)
-            else:
-                self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                     max_read_len=max_read_len, stream=stream, clip=clp)
+            self._text_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode, max_read_len=max_read_len,
+                             stream=stream, clip=side.clp)
             # the report, the audit and the bases go behind the writing pass's emission and in front of its finish, which
             # is the wait; the rejects: a counting call behind the counting pass, the writing one behind the writing pass
-            self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream,
-                                 rep=final and rep, aud=final and aud, bas=final and bas,
-                                 rej=(rws, rej_out[0], rej_flags) if rejects else None, adp=final and adp)
-            return (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
+            side.enqueue(self, ws.data_ptr(), ptrs, sizes, params.trunc_n, "plain", order, True, stream, writing=final,
+                         rejects_ws=rws, rejects_out=rej_out[0])
+            return self._text_finish(order, ws.data_ptr(), stream)
         counts = run([FastqOutput() for _ in range(3)])
         if rejects:
             need = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
@@ -1616,33 +1700,24 @@ class Context:
             idx = torch.empty(max(R, 1), dtype=torch.int64, device=dev) if record_index else None
             bufs[o] = (t, idx)
             outs[o] = FastqOutput(t.data_ptr(), B, idx.data_ptr() if record_index else None, R)
-        if adp and adp.want_clip:  # the counting pass has told the reads: a record of each input is a read at most
-            adp.with_clip(sum(counts["records_in"]))
+        if side.adp and side.adp.want_clip:  # the counting pass has told the reads: a record of each input is a read at most
+            side.adp.with_clip(sum(counts["records_in"]))
         counts = run(outs, True)
         res = [None] * 3
         for o in used:
             t, idx = bufs[o]
             R, B = counts["records"][o], counts["bytes"][o]
             res[o] = (t[:B], idx[:R]) if record_index else t[:B]
-        if aud:
-            counts["audit"] = aud.read()
-        if bas:
-            counts["bases"] = bas.read()
-        if adp:
-            counts["adapters"] = adp.read()
-        if clp:  # every call zeroed the stats first: these are the writing pass's
-            counts["clip"] = clp.read()
-            if clp.want_clip:  # the words lie in the workspace: a copy that outlives it
-                at = clp.words_ptr - ws.data_ptr()
-                words = ws[at:at + 4 * counts["clip"]["reads"]].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-                none = words == SK_FQ_CLIP_NONE
-                counts["clip"]["clip"] = torch.where(none, torch.full_like(words, -1), words & 0xFFFFFF)
-                counts["clip"]["adapter"] = torch.where(none, torch.full_like(words, -1), words >> 24)
+        report = side.collect(counts)  # every call zeroed the clip stats first: they are the writing pass's
+        if side.clp and side.clp.want_clip:  # the words lie in the workspace: a copy that outlives it
+            at = side.clp.words_ptr - ws.data_ptr()
+            counts["clip"]["clip"], counts["clip"]["adapter"] = \
+                _decode_clip_words(ws[at:at + 4 * counts["clip"]["reads"]].view(torch.int32))
         if rejects:
             got = self.trim_fastq_rejects_device_finish(rws.data_ptr(), stream)
             counts["rejects"] = {"text": rej_text[:got["bytes"]], "index": rej_idx[:got["records"]] if record_index else None,
                                  "records": got["records"], "bytes": got["bytes"], "reads": got["reads"]}
-        return (tuple(res), counts, rep.read()) if rep else (tuple(res), counts)
+        return (tuple(res), counts) if report is None else (tuple(res), counts, report)
 
     # ---- BGZF on the device -------------------------------------------------------------------
     def bgzf_device_async(self, text_ptr, text_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, eof=True,
@@ -1687,63 +1762,30 @@ class Context:
         as bgzf's.  report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as
         trim_fastq's, counts["bases"].  adapters: as trim_fastq's, counts["adapters"], without clip.  clip_adapters: as
         trim_fastq's, counts["clip"], without clip."""
-        if order is not None:
-            sizes = [text.numel()] + ([] if text2 is None else [text2.numel()])
-            return self._with_batch_table(order, sizes, lambda o: self._trim_fastq_gz(params, text, text2, mode, max_read_len, o,
-                                                                                     search, report, audit, bases, adapters,
-                                                                                     clip_adapters))
-        return self._trim_fastq_gz(params, text, text2, mode, max_read_len, None, search, report, audit, bases, adapters,
-                                   clip_adapters)
+        side = _SideCalls(text.device, False, mode, report, audit, bases, False, adapters, clip_adapters)
+        return self._trim_fastq_gz(params, [text] if text2 is None else [text, text2], mode, max_read_len, order, search, side)
 
-    def _trim_fastq_gz(self, params, text, text2, mode, max_read_len, order, search=False, report=False, audit=False,
-                       bases=False, adapters=False, clip_adapters=None):
+    def _trim_fastq_gz(self, params, texts, mode, max_read_len, order, search, side):
+        """trim_fastq_gz behind its keywords; order: the pair, or None"""
+        return self._with_batch_table(order, [t.numel() for t in texts],
+                                      lambda o: self._trim_fastq_gz_pass(params, texts, mode, max_read_len, o, search, side), side)
+
+    def _trim_fastq_gz_pass(self, params, texts, mode, max_read_len, order, search, side):
         import torch
-        dev = text.device
-        texts = [text] if text2 is None else [text, text2]
-        ptrs, sizes = [t.data_ptr() if t.numel() else None for t in texts], [t.numel() for t in texts]
+        dev = texts[0].device
+        ptrs, sizes = _text_ptrs(texts)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
-        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, clp)
+        ws_bytes = _fastq_ws_bytes(sizes, params.trunc_n, order, side.clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        used = TRIM_OUTPUTS[mode]
-        cap = fastq_output_bound(sum(sizes), mode)
-        bound = lib().sk_bgzf_bound(cap, SK_BGZF_EOF)
-        zws_bytes = lib().sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
-        outs, trimmed, images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
-        for o in used:
-            trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
-            outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
-        if order is None:
-            self.trim_fastq_device_async(params, ptrs, sizes, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                         max_read_len=max_read_len, stream=stream, clip=clp)
-        else:
-            self.trim_fastq_ordered_device_async(params, ptrs, sizes, order, outs, ws.data_ptr(), ws_bytes, mode=mode,
-                                                 max_read_len=max_read_len, stream=stream, clip=clp)
-        rep = _ReportBuffers(report, dev) if report else None
-        aud = _AuditBuffers(dev) if audit else None
-        bas = _BasesBuffers(bases, dev) if bases else None
-        adp = _AdaptersBuffers(adapters, dev) if adapters else None
-        self._enqueue_behind(ws.data_ptr(), ptrs, sizes, params.trunc_n, mode, "plain", order, True, stream, rep, aud, bas,
-                             adp=adp)
-        for o in used:
-            images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
-            zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
-            nbytes, written = self.trim_fastq_output_words(ws.data_ptr(), o)
-            self.bgzf_device_async(trimmed[o].data_ptr(), cap, images[o].data_ptr(), bound, zws[o].data_ptr(), zws_bytes,
-                                   eof=True, bytes_dev_ptr=nbytes, valid_dev_ptr=written, stream=stream, search=search)
-        sizes_out = [None if images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
-                     for o in range(3)]
-        counts = (self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish)(ws.data_ptr(), stream)
-        res = tuple(None if images[o] is None else images[o][:sizes_out[o]] for o in range(3))
-        if aud:
-            counts["audit"] = aud.read()
-        if bas:
-            counts["bases"] = bas.read()
-        if adp:
-            counts["adapters"] = adp.read()
-        if clp:
-            counts["clip"] = clp.read()
-        return (res, counts, rep.read()) if rep else (res, counts)
+        writers = _Writers(TRIM_OUTPUTS[mode], fastq_output_bound(sum(sizes), mode), search, _alloc_on(dev))
+        self._text_async(params, ptrs, sizes, order, writers.outs, ws.data_ptr(), ws_bytes, mode=mode, max_read_len=max_read_len,
+                         stream=stream, clip=side.clp)
+        side.enqueue(self, ws.data_ptr(), ptrs, sizes, params.trunc_n, "plain", order, True, stream)
+        writers.enqueue(self, ws.data_ptr(), stream)
+        res = writers.finish(self, stream)
+        counts = self._text_finish(order, ws.data_ptr(), stream)
+        report = side.collect(counts)
+        return (res, counts) if report is None else (res, counts, report)
 
     # ---- BGZF read on the device --------------------------------------------------------------
     def bgzf_inflate_device_async(self, image_ptr, image_bytes, out_ptr, capacity, workspace_ptr, workspace_bytes, stream=None):
@@ -1909,8 +1951,7 @@ class Context:
         head = bytes(image[:16].cpu().tolist())
         return "bgzf" if head[:4] == b"\x1f\x8b\x08\x04" and head[12:16] == b"BC\x02\x00" else "gzip"
 
-    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, report=False, audit=False,
-                         bases=False, adapters=False, clip_adapters=None):
+    def _trim_gz_chained(self, params, images, capacities, kinds, mode, max_read_len, order, search, side):
         """One pass: a decoding reader call per image into a buffer of its capacity, the chained trim fed by the readers'
         words, the BGZF writers fed by the trim's words, and only then the finishes: readers, writers, trim."""
         import torch
@@ -1934,33 +1975,15 @@ class Context:
             readers.append((fin, rws))
             nbytes.append(b)
             valid.append(w)
-        clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
-        ws_bytes = _fastq_ws_bytes(capacities, params.trunc_n, order, clp)
+        ws_bytes = _fastq_ws_bytes(capacities, params.trunc_n, order, side.clp)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        used = TRIM_OUTPUTS[mode]
-        cap = fastq_output_bound(sum(capacities), mode)
-        bound = L.sk_bgzf_bound(cap, SK_BGZF_EOF)
-        zws_bytes = L.sk_bgzf_workspace_bytes_flags(cap, SK_BGZF_SEARCH if search else 0)
-        outs, trimmed, out_images, zws = [FastqOutput() for _ in range(3)], [None] * 3, [None] * 3, [None] * 3
-        for o in used:
-            trimmed[o] = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
-            outs[o] = FastqOutput(trimmed[o].data_ptr(), cap, None, 0)
-        self.trim_fastq_chained_device_async(params, [t.data_ptr() for t in texts], capacities, outs, ws.data_ptr(), ws_bytes,
+        writers = _Writers(TRIM_OUTPUTS[mode], fastq_output_bound(sum(capacities), mode), search, _alloc_on(dev))
+        ptrs = [t.data_ptr() for t in texts]
+        self.trim_fastq_chained_device_async(params, ptrs, capacities, writers.outs, ws.data_ptr(), ws_bytes,
                                              bytes_dev_ptrs=nbytes, valid_dev_ptrs=valid, mode=mode, order=order,
-                                             max_read_len=max_read_len, stream=stream, clip=clp)
-        rep = _ReportBuffers(report, dev) if report else None
-        aud = _AuditBuffers(dev) if audit else None
-        bas = _BasesBuffers(bases, dev) if bases else None
-        adp = _AdaptersBuffers(adapters, dev) if adapters else None
-        self._enqueue_behind(ws.data_ptr(), [t.data_ptr() for t in texts], capacities, params.trunc_n, mode, "plain", order, True,
-                             stream, rep, aud, bas, adp=adp)
-        for o in used:
-            out_images[o] = torch.empty(max(bound, 16), dtype=torch.uint8, device=dev)
-            zws[o] = torch.empty(max(zws_bytes, 16), dtype=torch.uint8, device=dev)
-            b, w = self.trim_fastq_output_words(ws.data_ptr(), o)
-            self.bgzf_device_async(trimmed[o].data_ptr(), cap, out_images[o].data_ptr(), bound, zws[o].data_ptr(), zws_bytes,
-                                   eof=True, bytes_dev_ptr=b, valid_dev_ptr=w, stream=stream, search=search)
-        trim_finish = self.trim_fastq_device_finish if order is None else self.trim_fastq_ordered_device_finish
+                                             max_read_len=max_read_len, stream=stream, clip=side.clp)
+        side.enqueue(self, ws.data_ptr(), ptrs, capacities, params.trunc_n, "plain", order, True, stream)
+        writers.enqueue(self, ws.data_ptr(), stream)
         failed, reader_counts = None, []
         for fin, rws in readers:  # GzDataError, or TrimError (SK_ESPACE) whose counts["bytes_out"] is the need
             try:
@@ -1970,24 +1993,15 @@ class Context:
                 reader_counts.append(e.counts)
         if failed is not None:
             try:  # the trim saw an empty text for that image; its finish still reads and clears the stream's error word
-                trim_finish(ws.data_ptr(), stream)
+                self._text_finish(order, ws.data_ptr(), stream)
             except SickleError:
                 pass
             failed.readers = reader_counts  # every image's counts, so that two short capacities are learnt in one call
             raise failed
-        sizes_out = [None if out_images[o] is None else self.bgzf_device_finish(zws[o].data_ptr(), stream)["bytes_out"]
-                     for o in range(3)]
-        counts = trim_finish(ws.data_ptr(), stream)
-        res = tuple(None if out_images[o] is None else out_images[o][:sizes_out[o]] for o in range(3))
-        if aud:
-            counts["audit"] = aud.read()
-        if bas:
-            counts["bases"] = bas.read()
-        if adp:
-            counts["adapters"] = adp.read()
-        if clp:
-            counts["clip"] = clp.read()
-        return (res, counts, rep.read()) if rep else (res, counts)
+        res = writers.finish(self, stream)
+        counts = self._text_finish(order, ws.data_ptr(), stream)
+        report = side.collect(counts)
+        return (res, counts) if report is None else (res, counts, report)
 
     def trim_gz(self, params, image, image2=None, mode="se", max_read_len=0, order=None, search=False, text_capacity=None,
                 kind=None, report=False, audit=False, bases=False, adapters=False, clip_adapters=None):
@@ -2010,6 +2024,7 @@ class Context:
         report: as trim_fastq's, a third entry.  audit: as trim_fastq's, counts["audit"].  bases: as trim_fastq's,
         counts["bases"].  adapters: as trim_fastq_gz's, counts["adapters"].  clip_adapters: as trim_fastq_gz's,
         counts["clip"]."""
+        side = _SideCalls(image.device, False, mode, report, audit, bases, False, adapters, clip_adapters)
         if text_capacity is not None:
             images = [image] if image2 is None else [image, image2]
             caps = [int(text_capacity)] * len(images) if np.isscalar(text_capacity) else [int(c) for c in text_capacity]
@@ -2020,12 +2035,9 @@ class Context:
             if any(k not in ("bgzf", "gzip") for k in kinds):
                 raise SickleError("trim_gz: kind is \"bgzf\", \"gzip\" or None")
             return self._with_batch_table(order, caps, lambda o: self._trim_gz_chained(params, images, caps, kinds, mode,
-                                                                                       max_read_len, o, search, report, audit,
-                                                                                       bases, adapters, clip_adapters))
-        text = self._gunzip_any(image)
-        text2 = None if image2 is None else self._gunzip_any(image2)
-        return self.trim_fastq_gz(params, text, text2, mode=mode, max_read_len=max_read_len, order=order, search=search,
-                                  report=report, audit=audit, bases=bases, adapters=adapters, clip_adapters=clip_adapters)
+                                                                                       max_read_len, o, search, side), side)
+        texts = [self._gunzip_any(im) for im in ([image] if image2 is None else [image, image2])]
+        return self._trim_fastq_gz(params, texts, mode, max_read_len, order, search, side)
 
     @staticmethod
     def trim_fastq_output_words(fastq_workspace_ptr, output):
@@ -2154,8 +2166,8 @@ class _GzipPieceSource:
 class FastqStream:
     """What Context.trim_fastq_stream / trim_gz_stream return: an iterator over the pieces' outputs, see there."""
 
-    def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order=None,
-                 batch_capacity=None, report=False, audit=False, bases=False, rejects=False, adapters=False, clip_adapters=None):
+    def __init__(self, ctx, params, sources, mode, piece_bytes, room, gz, search, max_read_len, order, batch_capacity, side):
+        """side: the _SideCalls of the entry point's keywords, built in front of the sources"""
         import torch
         if mode not in TRIM_MODES or len(sources) != (2 if mode == "pe_split" else 1):
             raise SickleError("trim_fastq_stream: mode \"pe_split\" takes two inputs, the other modes one")
@@ -2188,48 +2200,25 @@ class FastqStream:
             self.ws_bytes = L.sk_trim_fastq_ordered_piece_workspace_bytes(n_in * cap_in, params.trunc_n, cap)
         else:
             self.ws_bytes = L.sk_trim_fastq_workspace_bytes(n_in * cap_in, params.trunc_n)
-        self.clip = None
-        self._clp = _ClipBuffers(clip_adapters, dev) if clip_adapters is not None else None
-        if self._clp:  # every piece's clip section lies behind ITS kind's bytes, which its bounds make no more than these
+        self._side = side  # (its buffers' few words are not in device_bytes)
+        self.report = self.audit = self.bases = self.adapters = self.clip = self.rejects = None
+        if side.clp:  # every piece's clip section lies behind ITS kind's bytes, which its bounds make no more than these
             self.ws_bytes += L.sk_trim_fastq_clip_extra_bytes(n_in * cap_in)
         self.ws = [alloc(self.ws_bytes) for _ in range(2)]
-        self.out_cap = fastq_output_bound(n_in * cap_in, mode)
-        self.out = [[alloc(self.out_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
+        # per slot: the outputs sized by the one-pass rule and, with gz, their images and writer workspaces
+        self.out = [_Writers(self.used, fastq_output_bound(n_in * cap_in, mode), search, alloc, gz) for _ in range(2)]
         self.words = torch.zeros((n_in, 2, 4), dtype=torch.int64, device=dev)
         self.device_bytes += self.words.numel() * 8
-        if gz:
-            self.img_cap = L.sk_bgzf_bound(self.out_cap, SK_BGZF_EOF)
-            self.zws_bytes = L.sk_bgzf_workspace_bytes_flags(self.out_cap, SK_BGZF_SEARCH if search else 0)
-            self.img = [[alloc(self.img_cap) if o in self.used else None for o in range(3)] for _ in range(2)]
-            self.zws = [[alloc(self.zws_bytes) if o in self.used else None for o in range(3)] for _ in range(2)]
         if sources[0].compressed:
             self.rws_bytes = L.sk_bgzf_inflate_workspace_bytes(sources[0].group_cap)
             self.comp = [[alloc(sources[0].group_cap) for _ in range(2)] for _ in range(n_in)]
             self.rws = [[alloc(self.rws_bytes) for _ in range(2)] for _ in range(n_in)]
         self.stream = torch.cuda.current_stream().cuda_stream
-        self.report = None
-        self._rep = _ReportBuffers(report, dev) if report else None  # (its few words are not in device_bytes)
-        self.audit = None
-        self._aud = _AuditBuffers(dev) if audit else None
-        self.bases = None
-        self._bas = _BasesBuffers(bases, dev) if bases else None
-        self.adapters = None
-        self._adp = _AdaptersBuffers(adapters, dev) if adapters else None
-        self.rejects = None
-        self._rej = bool(rejects)
-        if rejects:  # a workspace and a text buffer (an image, a writer workspace) per slot, sized by the slot's text buffers
-            self._rej_flags = _rejects_flags(rejects)
-            if self._rej_flags & SK_FQ_REJECTS_PAIRS and mode == "se":
-                raise ValueError("rejects=\"pairs\" needs a pair mode")
+        self._rej = side.rej_flags is not None
+        if self._rej:  # a workspace and a text buffer (an image, a writer workspace) per slot, sized by the slot's text buffers
             self._rej_sum = {"records": 0, "bytes": 0}
             self.jws = [alloc(L.sk_trim_fastq_rejects_workspace_bytes(n_in * cap_in)) for _ in range(2)]
-            self.jcap = L.sk_trim_fastq_rejects_bound(n_in * cap_in)
-            self.jout = [alloc(self.jcap) for _ in range(2)]
-            if gz:
-                self.jimg_cap = L.sk_bgzf_bound(self.jcap, SK_BGZF_EOF)
-                self.jzws_bytes = L.sk_bgzf_workspace_bytes_flags(self.jcap, SK_BGZF_SEARCH if search else 0)
-                self.jimg = [alloc(self.jimg_cap) for _ in range(2)]
-                self.jzws = [alloc(self.jzws_bytes) for _ in range(2)]
+            self.jout = [_Writers((0,), L.sk_trim_fastq_rejects_bound(n_in * cap_in), search, alloc, gz) for _ in range(2)]
         self._gen = self._run()
 
     def __iter__(self):
@@ -2291,41 +2280,30 @@ class FastqStream:
             bounds.append(self.room + chunk)
         self._bounds = bounds
         more = any(s.more() for s in self.src)
-        outs = [FastqOutput(t.data_ptr(), self.out_cap, None, 0) if t is not None else FastqOutput() for t in self.out[slot]]
+        outs, side = self.out[slot].outs, self._side
         words = dict(bytes_dev_ptrs=[self._words_ptr(i, slot) + 8 for i in range(n_in)],
                      valid_dev_ptrs=[self._words_ptr(i, slot) + 16 for i in range(n_in)],
                      start_dev_ptrs=[self._words_ptr(i, slot) for i in range(n_in)], more=more, mode=self.mode,
                      max_read_len=self.max_read_len, stream=self.stream)
-        if self._clp:  # the stats are zeroed in front of the first piece only
-            self._clp.reset = k == 0
-            words["clip"] = self._clp
+        if side.clp:  # the stats are zeroed in front of the first piece only
+            side.clp.reset = k == 0
+            words["clip"] = side.clp
+        ptrs, ws_ptr = [self.text[i][slot].data_ptr() for i in range(n_in)], self.ws[slot].data_ptr()
         if self.order is None:
-            c.trim_fastq_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds, outs,
-                                            self.ws[slot].data_ptr(), self.ws_bytes, **words)
+            c.trim_fastq_piece_device_async(self.params, ptrs, bounds, outs, ws_ptr, self.ws_bytes, **words)
         else:  # piece k starts from the state piece k - 1 wrote
-            c.trim_fastq_ordered_piece_device_async(self.params, [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
-                                                    self.order, self.states[k & 1].data_ptr(),
-                                                    self.states[(k + 1) & 1].data_ptr(), outs, self.ws[slot].data_ptr(),
-                                                    self.ws_bytes, **words)
+            c.trim_fastq_ordered_piece_device_async(self.params, ptrs, bounds, self.order, self.states[k & 1].data_ptr(),
+                                                    self.states[(k + 1) & 1].data_ptr(), outs, ws_ptr, self.ws_bytes, **words)
         # Behind the piece's emission, over its workspace (whose sections lie where ITS bounds put them, which a short chunk
         # makes less than the workspace's) and the slot's text buffers, which piece k + 2 fills again behind these calls.
         # What accumulates is zeroed in front of the first piece only; the rejects go into the slot's own workspace and text
         # buffer (and through its words into the writer).
-        rej = (self.jws[slot], FastqOutput(self.jout[slot].data_ptr(), self.jcap, None, 0), self._rej_flags) if self._rej else None
-        c._enqueue_behind(self.ws[slot].data_ptr(), [self.text[i][slot].data_ptr() for i in range(n_in)], bounds,
-                          self.params.trunc_n, self.mode, "piece", self.order, k == 0, self.stream, self._rep, self._aud,
-                          self._bas, rej, self._adp)
+        side.enqueue(c, ws_ptr, ptrs, bounds, self.params.trunc_n, "piece", self.order, k == 0, self.stream,
+                     rejects_ws=self.jws[slot] if self._rej else None, rejects_out=self.jout[slot].outs[0] if self._rej else None)
         if self._rej and self.gz:
-            b, w = c.trim_fastq_rejects_output_words(self.jws[slot].data_ptr())
-            c.bgzf_device_async(self.jout[slot].data_ptr(), self.jcap, self.jimg[slot].data_ptr(), self.jimg_cap,
-                                self.jzws[slot].data_ptr(), self.jzws_bytes, eof=not more, bytes_dev_ptr=b, valid_dev_ptr=w,
-                                stream=self.stream, search=self.search)
+            self.jout[slot].enqueue(c, self.jws[slot].data_ptr(), self.stream, eof=not more, words=c.trim_fastq_rejects_output_words)
         if self.gz:
-            for o in self.used:
-                b, w = c.trim_fastq_output_words(self.ws[slot].data_ptr(), o)
-                c.bgzf_device_async(self.out[slot][o].data_ptr(), self.out_cap, self.img[slot][o].data_ptr(), self.img_cap,
-                                    self.zws[slot][o].data_ptr(), self.zws_bytes, eof=not more, bytes_dev_ptr=b,
-                                    valid_dev_ptr=w, stream=self.stream, search=self.search)
+            self.out[slot].enqueue(c, ws_ptr, self.stream, eof=not more)
         return {"k": k, "slot": slot, "more": more, "readers": readers, "taken": taken}
 
     def _finish(self, p):
@@ -2353,13 +2331,11 @@ class FastqStream:
         c._check_fastq(rc, raw, counts, record_base=per_input, read_base=0 if counts["piece"]["inherited_range"] else base_reads)
         if any(status):
             raise SickleError("fastq stream: piece %d follows a failed carry (status %r)" % (p["k"], status))
-        res = [None] * 3
-        for o in self.used:
-            if self.gz:
-                n = c.bgzf_device_finish(self.zws[slot][o].data_ptr(), self.stream)["bytes_out"]
-                res[o] = self.img[slot][o][:n].cpu().numpy().tobytes()
-            else:
-                res[o] = self.out[slot][o][:counts["bytes"][o]].cpu().numpy().tobytes()
+        host = lambda t: None if t is None else t.cpu().numpy().tobytes()
+        if self.gz:
+            res = [host(im) for im in self.out[slot].finish(c, self.stream)]
+        else:
+            res = [host(t if t is None else t[:counts["bytes"][o]]) for o, t in enumerate(self.out[slot].text)]
         for key in ("records_in", "records", "bytes"):
             self.counts[key] = [a + b for a, b in zip(self.counts[key], counts[key])]
         self.counts["tail_lines"], self.counts["dropped_unpaired"] = counts["tail_lines"], counts["dropped_unpaired"]
@@ -2381,11 +2357,7 @@ class FastqStream:
         self._carried_in = carried
         if self._rej:
             got = c.trim_fastq_rejects_device_finish(self.jws[slot].data_ptr(), self.stream)
-            if self.gz:
-                n = c.bgzf_device_finish(self.jzws[slot].data_ptr(), self.stream)["bytes_out"]
-                res.append(self.jimg[slot][:n].cpu().numpy().tobytes())
-            else:
-                res.append(self.jout[slot][:got["bytes"]].cpu().numpy().tobytes())
+            res.append(host(self.jout[slot].finish(c, self.stream)[0] if self.gz else self.jout[slot].text[0][:got["bytes"]]))
             self._rej_sum["records"] += got["records"]
             self._rej_sum["bytes"] += got["bytes"]
         return tuple(res)
@@ -2412,16 +2384,9 @@ class FastqStream:
 
     def _run(self):
         yield from self._run_pieces()
-        if self._rep:  # every piece has been finished: the stream has been waited for
-            self.report = self._rep.read()
-        if self._aud:
-            self.audit = self._aud.read()
-        if self._bas:
-            self.bases = self._bas.read()
-        if self._adp:
-            self.adapters = self._adp.read()
-        if self._clp:
-            self.clip = self._clp.read()
+        got = {}  # every piece has been finished: the stream has been waited for
+        self.report = self._side.collect(got)
+        self.audit, self.bases, self.adapters, self.clip = [got.get(key) for key in ("audit", "bases", "adapters", "clip")]
         if self._rej:
             self.rejects = dict(self._rej_sum)
 

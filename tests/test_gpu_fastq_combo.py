@@ -368,3 +368,39 @@ def test_drawn_texts(sk_ctx):
         assert np.array_equal(outs[0][1].cpu().numpy(), order) and counts["order"]["batches"] == oc["batches"]
     print("pair classes drawn:", dict(hit))
     assert all(hit[c] > 0 for c in cm.CLASSES)
+
+
+# ---- 12 a bad option raises in front of everything ----------------------------------------------------------------------
+FOUR = b"".join(b"@r%d\n%s\n+\n%s\n" % (i, b"ACGT" * (6 + i), b"I" * (20 + 4 * i) + b"#" * 4) for i in range(4))
+
+
+def test_a_bad_option_raises_with_nothing_in_flight(sk_ctx, monkeypatch):
+    """A bad behind-call option of the .gz drivers and of a stream raises its ValueError before the library is called once,
+    and the next good call on the same context and stream gives what a fresh context gives: nothing was left unfinished"""
+    params = capi.make_params("sanger", 20, 20)
+    host = lambda res: ([None if im is None else bytes(im.cpu().numpy()) for im in res[0]], res[1])
+
+    def good(ctx):
+        parts = list(ctx.trim_fastq_stream(params, FOUR, mode="se", piece_bytes=40, room=128, gz=True))
+        return host(ctx.trim_fastq_gz(params, to_device(FOUR), mode="se")), parts
+    fresh = capi.Context(device=0, slots=2)
+    want, want_parts = good(fresh)
+    fresh.close()
+    assert want[1]["records_in"] == [4, 0] and gzip.decompress(want[0][0]) == fm.expected(("sanger", 20, 20), [FOUR], "se")["texts"][0]
+    assert len(want_parts) > 1 and gzip.decompress(b"".join(p[0] for p in want_parts)) == gzip.decompress(want[0][0])
+    image = sk_ctx.bgzf(to_device(FOUR))
+    calls, check = [], capi.Context._check
+    monkeypatch.setattr(capi.Context, "_check", lambda self, rc, err=None: (calls.append(rc), check(self, rc, err))[1])
+    bad = dict(bases={"len_bins": 4})
+    for run in (lambda: sk_ctx.trim_fastq_gz(params, to_device(FOUR), mode="se", **bad),
+                lambda: sk_ctx.trim_gz(params, image, mode="se", text_capacity=len(FOUR) + 64, **bad),
+                lambda: sk_ctx.trim_gz(params, image, mode="se", order=(2, 64), text_capacity=len(FOUR) + 64, **bad),
+                lambda: sk_ctx.trim_gz(params, image, mode="se", **bad),
+                lambda: sk_ctx.trim_fastq_stream(params, FOUR, mode="se", piece_bytes=40, room=128, rejects="pairs"),
+                lambda: sk_ctx.trim_gz_stream(params, bytes(image.cpu().numpy()), mode="se", piece_bytes=65536, **bad)):
+        del calls[:]
+        with pytest.raises(ValueError) as e:
+            run()
+        assert calls == [] and str(e.value) in ("bases: unknown keys ['len_bins']", "rejects=\"pairs\" needs a pair mode")
+        got, got_parts = good(sk_ctx)
+        assert got == want and got_parts == want_parts and len(calls) > 4
